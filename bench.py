@@ -15,16 +15,26 @@ rules, auto-reset on (BASELINE.json configs[2]; configs[3] = the same per-GPU sh
 scaling is weak.  Envs never communicate: ranks shard the global env ids (msnake.make_sharded) with
 no data-path collective; the one collective is msnake.gather_stats after the timed regions (RCCL).
 
-Timing ("warm-up, time K steps, repeats, median"): after W warm-up steps the K-step
-region is timed R = max(5, ceil(2048 / K)) times.  Every repeat is bracketed by barrier +
-torch.cuda.synchronize() on both sides and timed with HIP events recorded on the launch stream
-right around its K launches (the first event is queued behind one untimed msnake_render launch, so
-the region does not start on an idle queue); per repeat the MAX over ranks is taken, and `value`, `ms_per_step` and
-`roofline` all come from the MEDIAN repeat -- one clock for all three, independent of K.  The host
-wall clock around the same region (it adds the launch latency of the first step and the wake-up
-after the final synchronize, a fixed 30-40 us per region) is reported as `wall_ms_per_step`.
+Timing: after W warm-up steps the K-step region is timed once (--repeats R: R times; --full: by
+default R = max(5, ceil(2048 / K)), SURVEY 8(d): "warm-up, time K steps, repeats, median").  Every
+repeat is bracketed by barrier + torch.cuda.synchronize() on both sides and timed with HIP events
+recorded on the launch stream right around its K launches (the first event is queued behind one
+untimed msnake_render launch, so the region does not start on an idle queue); per repeat the MAX
+over ranks is taken, and `value`, `ms_per_step` and `roofline` all come from the MEDIAN repeat --
+one clock for all three, independent of K.  The host wall clock around the same region (it adds the
+launch latency of the first step and the wake-up after the final synchronize, a fixed 30-40 us per
+region) is reported as `wall_ms_per_step`.
 
-Prints ONE JSON line (rank 0).  Extra keys beside the driver's contract:
+--dump-outputs DIR: after the timed steps, what the last of them wrote (rank 0's shard) goes to
+DIR/<name>.npy as float32 -- reward, done, ep_return, ep_len, num_snakes, flags of every env (of a
+sample above 786 432 envs) and the observations of a fixed, seeded sample of envs (all of them would
+be 65 MB at the bench batch), with the env indices as float64 -- at most 56 MiB.  Same arguments,
+same inputs, same files.
+
+A plain run does only what the headline needs.  --full adds everything else: the repeats above,
+the secondary legs below (rollout_tape, per_step_strided, selfplay_rollout) and cpu_baseline.
+
+Prints ONE JSON line (rank 0).  Extra keys beside the driver's contract (the last four with --full):
   roofline     : dominant kernel vs the HBM roofline (algorithmic bytes per launch from
                  msnake_algorithmic_bytes_per_env_step() x envs, duration = the median above;
                  `traffic` = PMC bytes per launch of the newest committed profiles/hbm_traffic_*.json,
@@ -144,6 +154,29 @@ def selfplay_rollout_leg(dev, n=4096, nsteps=16):
             "env_errors": int(st["errors"])}
 
 
+def _env_sample(n, budget, bytes_per_env):
+    """All n env indices if their bytes fit the budget, else a fixed seeded sample of them that does."""
+    k = min(n, budget // bytes_per_env)
+    return np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, obs, rew, done, info):
+    """The step's outputs as a caller receives them (msnake_info split into its fields), float32 .npy files; the
+    budgets (observations 32 MiB, per-env scalars 24 MiB, indices included) keep them within 56 MiB at any batch."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = obs.shape[0]
+    obs_idx = _env_sample(n, 32 << 20, obs[0].numel() * 4 + 8)
+    env_idx = _env_sample(n, 24 << 20, 6 * 4 + 8)
+    info_h = info.cpu().numpy()[env_idx]
+    out = {"obs": obs[torch.from_numpy(obs_idx).to(obs.device)].cpu().numpy(), "obs_env_index": obs_idx.astype(np.float64),
+           "reward": rew.cpu().numpy()[env_idx], "done": done.cpu().numpy()[env_idx],
+           "ep_return": info_h[:, 0].copy().view(np.float32), "ep_len": info_h[:, 1], "num_snakes": info_h[:, 2],
+           "flags": info_h[:, 3], "env_index": env_idx.astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def load_pmc_traffic(bytes_per_launch):
     """(HBM bytes per launch, source) from the newest committed PMC pass of THIS workload
     (profiles/hbm_traffic_*.json: separate FETCH_SIZE / WRITE_SIZE passes of this same command,
@@ -199,7 +232,12 @@ def main():
     ap.add_argument("--steps", type=int, default=2048)
     ap.add_argument("--warmup", type=int, default=128)
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
-    ap.add_argument("--repeats", type=int, default=0, help="timed repeats of the K-step region (default max(5, ceil(2048/K)))")
+    ap.add_argument("--repeats", type=int, default=0,
+                    help="timed repeats of the K-step region (default 1; with --full max(5, ceil(2048/K)))")
+    ap.add_argument("--full", action="store_true",
+                    help="also the repeats, the secondary legs and the CPU baseline (a plain run times the K steps once)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--python-loop", action="store_true", help="issue launches from Python instead of msnake_step_tape")
     ap.add_argument("--no-rollout", action="store_true",
@@ -213,7 +251,7 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo + MSNAKE_BENCH_ONE_DEVICE=1 rehearses the N>1 path with every rank on cuda:0")
     args = ap.parse_args()
-    legs = set() if args.no_rollout or args.python_loop else {x for x in args.legs.split(",") if x}
+    legs = set() if not args.full or args.no_rollout or args.python_loop else {x for x in args.legs.split(",") if x}
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -244,7 +282,7 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device())
     n = args.envs_per_gpu
     K, Wm = args.steps, args.warmup
-    R = args.repeats if args.repeats > 0 else max(5, math.ceil(2048 / max(1, K)))
+    R = args.repeats if args.repeats > 0 else max(5, math.ceil(2048 / max(1, K))) if args.full else 1
 
     # rank r owns the global env ids [r*n, (r+1)*n): the shipped sharding API, not a hand-rolled one
     env = msnake.make_sharded(n * world, rank, world, device=dev, dim=DIM, n_snakes=N_SNAKES, rules="snake_env", seed=0,
@@ -314,6 +352,8 @@ def main():
 
     st = env.stats()
     assert st["errors"] == 0 and st["env_steps"] == R * K * n, st
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, obs, rew, done, info)
 
     # secondary figure: the same K steps through msnake_rollout_tape (ONE persistent launch per tape
     # chunk, env state kept in registers across steps).  Only usable when the actions of several
@@ -448,7 +488,7 @@ def main():
         out["collective"] = {"backend": total.get("backend"), "record_device": total.get("record_device"), "ranks": len(per_rank)}
         if world == 1 and "selfplay" in legs:
             out["selfplay_rollout"] = selfplay_rollout_leg(dev)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(tape_h)
         print(json.dumps(out), flush=True)
     env.close()

@@ -1,4 +1,5 @@
 """Helpers to read tests/golden/ (written by tools/gen_golden.py from the running reference)."""
+import hashlib
 import json
 import os
 import zlib
@@ -61,3 +62,15 @@ def blob_to_obs(blob):
 
 def crc_rows(obs):
     return np.array([zlib.crc32(np.ascontiguousarray(o).tobytes()) for o in obs], np.uint32)
+
+
+def feed_step(h, obs, states, rules):
+    """Feed one vec step as the reference returned it into the running hash `h` (hashlib.blake2b): the observation
+    array (shape and every byte) and the state of every env projected by state_view.  Returns the 32-bit tag of the
+    hash so far, which names the first step at which two runs part; the full digest at the end covers every step.
+    tools/gen_golden.py records tags and digest, the tests recompute them."""
+    obs = np.ascontiguousarray(obs, np.uint8)
+    h.update(json.dumps([list(obs.shape), [state_view(st, rules) for st in states]], sort_keys=True,
+                        separators=(",", ":")).encode())
+    h.update(obs.tobytes())
+    return np.uint32(int.from_bytes(h.copy().digest()[:4], "little"))

@@ -190,3 +190,36 @@ def test_bench_self_launch_command(monkeypatch):
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     assert cmd[-6:] == ["--gpus", "4", "--steps", "20", "--warmup", "5"] and cmd[-7].endswith("bench.py")
     assert env["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_bench_dump_outputs_are_float_bounded_and_repeatable(tmp_path):
+    """`bench.py --dump-outputs DIR` at the bench batch: float32 / float64 files within 64 MB, the same seeded env sample
+    every time, and msnake_info split into the fields a caller reads (step_wait: ep_return, ep_len, num_snakes)."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = bench.ENVS_PER_GPU
+    rs = np.random.default_rng(5)
+    obs = rs.integers(0, 256, (n, 21, 21, 9), dtype=np.uint8)
+    rew = rs.standard_normal(n).astype(np.float32)
+    done = rs.integers(0, 2, n).astype(np.uint8)
+    info = np.stack([rs.standard_normal(n).astype(np.float32).view(np.int32), rs.integers(0, 2000, n),
+                     rs.integers(0, 4, n), rs.integers(0, 2, n)], 1).astype(np.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), *(torch.from_numpy(x) for x in (obs, rew, done, info)))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and all(f.endswith(".npy") for f in names)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64e6
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in names}
+    for f in names:
+        assert got[f[:-4]].dtype in (np.float32, np.float64), f
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f)), f
+    oi, ei = got["obs_env_index"].astype(np.int64), got["env_index"].astype(np.int64)
+    assert 0 < len(oi) < n and np.all(np.diff(oi) > 0) and np.array_equal(ei, np.arange(n))
+    assert np.array_equal(got["obs"], obs[oi].astype(np.float32))
+    assert np.array_equal(got["reward"], rew) and np.array_equal(got["done"], done)
+    assert np.array_equal(got["ep_return"], info[:, 0].view(np.float32))
+    for k, c in (("ep_len", 1), ("num_snakes", 2), ("flags", 3)):
+        assert np.array_equal(got[k], info[:, c]), k

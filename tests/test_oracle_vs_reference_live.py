@@ -1,68 +1,52 @@
-"""The oracle against the RUNNING reference, beyond the committed fixtures: configurations and action streams drawn at
-random (fixed seeds), every observation byte, reward, done, num_snakes, episode return / length and the full state after
-every step.  Runs only where /root/reference exists (the build container; the reference cannot travel to the GPU box):
-there it re-pins oracle/snake_oracle.c to the reference itself on inputs no fixture holds.  The reference is loaded like
-tools/gen_golden.py loads it (source text by path, gym stubbed in memory, the Philox shim injected as np_random); nothing
-of it is copied or written."""
-import importlib.util
+"""The oracle against the reference beyond the tapes: configurations and action streams drawn at random (fixed seeds),
+every observation byte, reward, done, num_snakes, episode return / length and the full state after every step.  The
+reference's side is tests/golden/random_configs.npz, recorded by tools/gen_golden.py (gen_random_configs) running the
+reference itself the way the tapes are recorded (source text by path, gym stubbed in memory, the Philox shim injected
+as np_random): the actions it chose from the reference's state, the scalars it returned for them, and its observations
+and states as one BLAKE2b-256 per configuration with a 32-bit tag after every step (golden_util.feed_step)."""
+import hashlib
+import json
 import os
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+from golden_util import GOLDEN, feed_step
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src", "gym-snake")),
-                                reason="the reference tree is not present on this machine")
+FIXTURE = os.path.join(GOLDEN, "random_configs.npz")
 
 
-@pytest.fixture(scope="module")
-def gg():
-    spec = importlib.util.spec_from_file_location("gen_golden_live", os.path.join(ROOT, "tools", "gen_golden.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)  # (loads the reference modules; writes nothing: only main() writes fixtures)
-    return mod
+def _load():
+    with np.load(FIXTURE) as z:
+        return json.loads(str(z["meta"])), {k: z[k] for k in z.files if k != "meta"}
 
 
-def _configs(k, seed):
-    rs = np.random.default_rng(seed)
-    out = []
-    for i in range(k):
-        rules = i % 3
-        ns = int(rs.integers(1, 5 if rules == 1 else 4))
-        nf = int(rs.integers(0, 10)) if rules == 1 else ns
-        out.append(dict(rules=rules, dim=int(rs.integers(3, 24)), n_snakes=ns, n_fruits=nf, seed=int(rs.integers(0, 2**31)),
-                        env_id_base=int(rs.integers(0, 2**40)), num_envs=int(rs.integers(2, 7)), auto_reset=bool(rs.integers(0, 2)),
-                        eps=float(rs.choice([0.1, 0.5, 1.0]))))
-    return out
+META, REC = _load()
 
 
-@pytest.mark.parametrize("cfg", _configs(150, 777), ids=lambda c: f"{['S', 'N', 'A'][c['rules']]}-{c['dim']}x{c['n_snakes']}x{c['n_fruits']}-"
-                                                                    f"ar{int(c['auto_reset'])}-eps{c['eps']}")
-def test_oracle_equals_the_running_reference(gg, cfg):
+@pytest.mark.parametrize("case", list(enumerate(META["configs"])),
+                         ids=lambda ic: f"{['S', 'N', 'A'][ic[1]['rules']]}-{ic[1]['dim']}x{ic[1]['n_snakes']}x"
+                                        f"{ic[1]['n_fruits']}-ar{int(ic[1]['auto_reset'])}-eps{ic[1]['eps']}")
+def test_oracle_equals_the_running_reference(case):
     from oracle.snake_oracle import Oracle
+    i, cfg = case
+    ref = {k: v[i] for k, v in REC.items()}
     rules, E, ns = cfg["rules"], cfg["num_envs"], cfg["n_snakes"]
-    ref = gg.VecHarness(rules, cfg["dim"], ns, cfg["n_fruits"], cfg["seed"], E, env_id_base=cfg["env_id_base"],
-                        auto_reset=cfg["auto_reset"])
     ora = Oracle(E, dim=cfg["dim"], n_snakes=ns, n_fruits=cfg["n_fruits"], rules=rules, seed=cfg["seed"],
                  env_id_base=cfg["env_id_base"], auto_reset=cfg["auto_reset"])
-    assert np.array_equal(ref.reset(), ora.reset())
-    rs = np.random.default_rng(cfg["seed"] % 9973)
-    keys = ["snakes", "fruits", "vels", "grow_to", "t", "ctr"] + (["alive", "in_dead"] if rules == 1 else []) + (["spare_fruits"] if rules == 2 else [])
-    for t in range(70):
+    h = hashlib.blake2b(digest_size=32)
+    states = lambda: [ora.get_state(e) for e in range(E)]  # noqa: E731
+    nr = 0
+    assert feed_step(h, ora.reset(), states(), rules) == ref["reset_tag"][nr], "reset observation or state"
+    for t in range(META["steps"]):
         # eps-greedy walk towards the nearest fruit (eats, long bodies, collisions), with invalid action codes mixed in
-        acts = np.array([gg.policy_actions(e, ns, rs, cfg["eps"]) for e in ref.envs], np.int32)
-        if t % 11 == 5:
-            acts[rs.integers(0, E), rs.integers(0, ns)] = int(rs.choice([-1, 5, 7]))
-        r_obs, r_rew, r_done, r_ns, r_er, r_el = ref.step(acts)
-        o_obs, o_rew, o_done, o_ns, o_er, o_el = ora.step(acts)
-        assert np.array_equal(o_rew, r_rew) and np.array_equal(o_done, r_done), t
-        assert np.array_equal(o_ns, r_ns) and np.array_equal(o_er, r_er) and np.array_equal(o_el, r_el), t
-        assert np.array_equal(o_obs, r_obs), t
-        for e in range(E):
-            want = gg.canon_state(ref.envs[e])
-            got = ora.get_state(e)
-            assert {k: got[k] for k in keys} == {k: want[k] for k in keys}, (t, e)
+        o_obs, o_rew, o_done, o_ns, o_er, o_el = ora.step(ref["actions"][t, :E, :ns].astype(np.int32))
+        assert np.array_equal(o_rew, ref["reward"][t, :E]) and np.array_equal(o_done, ref["done"][t, :E]), t
+        assert np.array_equal(o_ns, ref["num_snakes"][t, :E]) and np.array_equal(o_er, ref["ep_return"][t, :E]), t
+        assert np.array_equal(o_el, ref["ep_len"][t, :E]), t
+        assert feed_step(h, o_obs, states(), rules) == ref["tag"][t], f"observation or state differs at step {t}"
         if not cfg["auto_reset"] and t % 25 == 24:  # a bare gym loop resets by hand
-            assert np.array_equal(ref.reset(), ora.reset())
+            nr += 1
+            assert feed_step(h, ora.reset(), states(), rules) == ref["reset_tag"][nr], f"reset after step {t}"
+    assert not ref["reset_tag"][nr + 1:].any()
+    assert h.digest() == ref["digest"].tobytes(), "observations or states differ from the reference's"

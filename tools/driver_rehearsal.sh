@@ -9,7 +9,7 @@ timeout -k 10 900 python -m pytest tests -x -q -m gpu > $OUT/gpu_tests.log 2>&1 
 tail -1 $OUT/gpu_tests.log; echo "gpu tests $((SECONDS-t0)) s"; t0=$SECONDS
 timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err || { tail -5 $OUT/bench_steps20.err; exit 1; }
 echo "bench --steps 20: $((SECONDS-t0)) s"; t0=$SECONDS
-timeout -k 10 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
 echo "bench defaults: $((SECONDS-t0)) s"
 python - <<'PY'
 import json

@@ -30,7 +30,7 @@ MSNAKE_LIB=$PKG/libmsnake_dbg.so timeout -k 10 300 python tools/span_gap.py 4096
 MSNAKE_LIB=$PKG/libmsnake_span.so timeout -k 10 300 python tools/span_gap.py 4096 512 > $OUT/span_gap_light.json 2> $OUT/span_gap_light.err
 echo "span/gap done"
 # the collective path on RCCL with the one rank a one-GPU box can give it
-timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --backend nccl --steps 1024 --warmup 64 --no-cpu-baseline 2> $OUT/bench_1rank_rccl.err | grep "^{\"metric\"" > $OUT/bench_1rank_rccl.json
+timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --backend nccl --steps 1024 --warmup 64 --no-cpu-baseline 2> $OUT/bench_1rank_rccl.err | grep "^{\"metric\"" > $OUT/bench_1rank_rccl.json
 cut -c1-200 $OUT/bench_1rank_rccl.json
-MSNAKE_BENCH_ONE_DEVICE=1 timeout -k 10 300 python bench.py --gpus 2 --backend gloo --steps 1024 --warmup 64 2> $OUT/bench_2rank.err | grep "^{\"metric\"" > $OUT/bench_2rank_gloo_one_device.json
+MSNAKE_BENCH_ONE_DEVICE=1 timeout -k 10 300 python bench.py --full --gpus 2 --backend gloo --steps 1024 --warmup 64 2> $OUT/bench_2rank.err | grep "^{\"metric\"" > $OUT/bench_2rank_gloo_one_device.json
 cut -c1-300 $OUT/bench_2rank_gloo_one_device.json

@@ -25,7 +25,7 @@ not installed (TF / mpi4py / cloudpickle imports in baselines/__init__ chain).
 Usage: python tools/gen_golden.py            (rewrites tests/golden/*)
 """
 import contextlib
-
+import hashlib
 import io
 import json
 import os
@@ -683,6 +683,65 @@ def gen_philox_kat():
     print("philox_kat.json written")
 
 
+# ----------------------------------------------------------------------------- random configurations
+def random_configs(k, seed):
+    """k configurations drawn at random (fixed seed): rules, grid, snakes, fruits, env ids, batch, auto-reset, eps."""
+    rs = np.random.default_rng(seed)
+    out = []
+    for i in range(k):
+        rules = i % 3
+        ns = int(rs.integers(1, 5 if rules == 1 else 4))
+        nf = int(rs.integers(0, 10)) if rules == 1 else ns
+        out.append(dict(rules=rules, dim=int(rs.integers(3, 24)), n_snakes=ns, n_fruits=nf, seed=int(rs.integers(0, 2**31)),
+                        env_id_base=int(rs.integers(0, 2**40)), num_envs=int(rs.integers(2, 7)), auto_reset=bool(rs.integers(0, 2)),
+                        eps=float(rs.choice([0.1, 0.5, 1.0]))))
+    return out
+
+
+RANDOM_STEPS = 70
+
+
+def gen_random_configs(k=150, seed=777):
+    """random_configs.npz: k configurations, each the vec harness run through RANDOM_STEPS steps of an eps-greedy walk
+    towards the nearest fruit, invalid action codes mixed in, and (auto_reset off) a reset by hand every 25 steps.
+    Stored per configuration [i] and step [t], padded to 6 envs x 4 snakes: the actions, reward, done, num_snakes and
+    episode r/l; the observations and states the reference returned (resets included) go through golden_util.feed_step
+    into one BLAKE2b-256 per configuration: its digest and the 32-bit tag after every reset and step."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from golden_util import feed_step
+    cfgs = random_configs(k, seed)
+    T, EM, SM, RM = RANDOM_STEPS, 6, 4, 1 + RANDOM_STEPS // 25
+    out = dict(actions=np.zeros((k, T, EM, SM), np.int8), reward=np.zeros((k, T, EM), np.float32),
+               done=np.zeros((k, T, EM), np.uint8), num_snakes=np.zeros((k, T, EM), np.int8),
+               ep_return=np.zeros((k, T, EM), np.float32), ep_len=np.zeros((k, T, EM), np.int32),
+               tag=np.zeros((k, T), np.uint32), reset_tag=np.zeros((k, RM), np.uint32), digest=np.zeros((k, 32), np.uint8))
+    for i, cfg in enumerate(cfgs):
+        rules, E, ns = cfg["rules"], cfg["num_envs"], cfg["n_snakes"]
+        vec = VecHarness(rules, cfg["dim"], ns, cfg["n_fruits"], cfg["seed"], E, env_id_base=cfg["env_id_base"],
+                         auto_reset=cfg["auto_reset"])
+        h = hashlib.blake2b(digest_size=32)
+        nr = 0
+        out["reset_tag"][i, nr] = feed_step(h, vec.reset(), [canon_state(e) for e in vec.envs], rules)
+        rs = np.random.default_rng(cfg["seed"] % 9973)
+        for t in range(T):
+            a = np.array([policy_actions(e, ns, rs, cfg["eps"]) for e in vec.envs], np.int32)
+            if t % 11 == 5:
+                a[rs.integers(0, E), rs.integers(0, ns)] = int(rs.choice([-1, 5, 7]))
+            ob, r, d, n_, er, el = vec.step(a)
+            out["actions"][i, t, :E, :ns] = a
+            for key, v in zip(("reward", "done", "num_snakes", "ep_return", "ep_len"), (r, d, n_, er, el)):
+                out[key][i, t, :E] = v
+            out["tag"][i, t] = feed_step(h, ob, [canon_state(e) for e in vec.envs], rules)
+            if not cfg["auto_reset"] and t % 25 == 24:
+                nr += 1
+                out["reset_tag"][i, nr] = feed_step(h, vec.reset(), [canon_state(e) for e in vec.envs], rules)
+        out["digest"][i] = np.frombuffer(h.digest(), np.uint8)
+    out["meta"] = np.array(json.dumps(dict(configs=cfgs, steps=T)))
+    path = os.path.join(OUT, "random_configs.npz")
+    np.savez_compressed(path, **out)
+    print(f"random_configs.npz: {k} configurations x {T} steps, {os.path.getsize(path) / 1024:.0f} KiB")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     gen_philox_kat()
@@ -708,6 +767,7 @@ def main():
     gen_tape("tape_N_13x13_2_f0", N, 13, 2, 0, seed=12, num_envs=8, steps=64)
     gen_tape("tape_A_6x6_3", A, 6, 3, 3, seed=13, num_envs=12, steps=96)
     gen_tape("tape_A_19x19_1", A, 19, 1, 1, seed=14, num_envs=8, steps=64)
+    gen_random_configs()
 
 
 if __name__ == "__main__":

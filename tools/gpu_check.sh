@@ -16,8 +16,8 @@ fi
 rc=$?
 tail -15 $OUT/pytest.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench_k20.json 2> $OUT/bench_k20.err || { tail -5 $OUT/bench_k20.err; exit 1; }
-timeout -k 10 300 python bench.py --steps 1024 --warmup 64 --no-cpu-baseline > $OUT/bench_k1024.json 2> $OUT/bench_k1024.err || { tail -5 $OUT/bench_k1024.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_k20.json 2> $OUT/bench_k20.err || { tail -5 $OUT/bench_k20.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 1024 --warmup 64 --no-cpu-baseline > $OUT/bench_k1024.json 2> $OUT/bench_k1024.err || { tail -5 $OUT/bench_k1024.err; exit 1; }
 python - <<PY
 import json
 for f in ("bench_k20", "bench_k1024"):

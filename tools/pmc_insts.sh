@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-ARGS="--steps 512 --warmup 64 --repeats 3 --envs-per-gpu $ENVS --no-cpu-baseline"
+ARGS="--full --steps 512 --warmup 64 --repeats 3 --envs-per-gpu $ENVS --no-cpu-baseline"
 python3 $R/bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_WAVES SQ_INSTS_SMEM SQ_INSTS_BRANCH --output-format csv -d $OUT/pmc_insts -- python3 $R/bench.py $ARGS --no-rollout > $OUT/pmc.log 2>&1 || echo "pmc pass failed"
 python3 - <<PY

@@ -18,8 +18,8 @@ guard timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>
 tail -6 $OUT/pytest.log
 [ $rc -ne 0 ] && { grep -E "Error|assert|FAILED" $OUT/pytest.log | head -20; exit $rc; }
 echo "== bench"
-guard timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $OUT/bench_k20.json 2> $OUT/bench_k20.err || { tail -5 $OUT/bench_k20.err; exit 1; }
-guard timeout -k 10 400 python bench.py --steps 1024 --warmup 64 --no-cpu-baseline > $OUT/bench_k1024.json 2> $OUT/bench_k1024.err || { tail -5 $OUT/bench_k1024.err; exit 1; }
+guard timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_k20.json 2> $OUT/bench_k20.err || { tail -5 $OUT/bench_k20.err; exit 1; }
+guard timeout -k 10 400 python bench.py --full --steps 1024 --warmup 64 --no-cpu-baseline > $OUT/bench_k1024.json 2> $OUT/bench_k1024.err || { tail -5 $OUT/bench_k1024.err; exit 1; }
 python - <<PY
 import json
 for f in ("bench_k20", "bench_k1024"):
@@ -63,6 +63,6 @@ for l in open("$OUT/proc_mode.jsonl"):
         d = json.loads(l); print(d["us_per_step"], d["first_launch_us"], d["tiny_kernel_us"], d["stream_handle"], d["obs_ptr"], d["smi_before"].get("sclk_mhz"), d["smi_during"].get("sclk_mhz"), d["smi_during"].get("power_w"))
 PY
 echo "== 1-rank RCCL bench under torchrun"
-guard timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --backend nccl --steps 1024 --warmup 64 --no-cpu-baseline > $OUT/bench_1rank_rccl.json 2> $OUT/bench_1rank_rccl.err || tail -5 $OUT/bench_1rank_rccl.err
+guard timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --backend nccl --steps 1024 --warmup 64 --no-cpu-baseline > $OUT/bench_1rank_rccl.json 2> $OUT/bench_1rank_rccl.err || tail -5 $OUT/bench_1rank_rccl.err
 grep -o '"collective": {[^}]*}' $OUT/bench_1rank_rccl.json
 echo "session done"
