@@ -21,6 +21,9 @@
  *                      envs/snake_multiple_env_new.py:35-50) / SnakeAdversarial.step
  *                      (envs/snake_adversarial_env.py:166-201), including the observation render
  *                      get_multi_snake_ob (snake_multiple_test.py:35-58,93-95)
+ *   msnake_reset_envs <- the worker's `ob = env.reset()` on done (subproc_vec_env.py:13-16), for the envs a mask
+ *                      selects, plus what that line drops: the terminal observation and whether the time cap
+ *                      ended the episode (gymnasium's reset_mask, envpool's reset(env_ids))
  *   msnake_destroy  <- SubprocVecEnv.close (subproc_vec_env.py:73-83)
  *   msnake_get_state / msnake_set_state / msnake_get_state_all / msnake_set_state_all: no reference
  *                      counterpart (env state is never checkpointed there); used by
@@ -127,6 +130,22 @@ int msnake_obs_shape(msnake_handle h, int32_t* H, int32_t* W, int32_t* C);
 /* Reset every env; writes observations if obs_dev != NULL.  Asynchronous on `stream`
  * (a hipStream_t passed as void*, NULL = the default stream). */
 int msnake_reset(msnake_handle h, uint8_t* obs_dev, void* stream);
+
+/* Reset only the envs that mask_dev (uint8 [num_envs], non-zero = selected; a step's done_dev can be passed
+ * as it is) selects.  Extends the auto-reset of subproc_vec_env.py:13-16, which drops the last observation of an
+ * episode: with final_obs_dev != NULL every selected env's current, pre-reset observation is first rendered into
+ * its row of final_obs_dev, then the selected envs are reset and their reset observations written to obs_dev
+ * (if non-NULL).  Rows of unselected envs are left untouched in both.  truncated_dev (uint8 [num_envs], may be
+ * NULL) is written for every env: 1 iff the env is selected, its episode has ended, t >= max_steps and the rule
+ * set's own end condition does not hold (snake_env / adversarial: the main snake is dead; new_world: the main
+ * snake's alive bit, the reference's done = snake.alive), i.e. the time cap alone ended it.  A selected env whose
+ * episode had not ended is abandoned: it is not counted in msnake_get_stats, as with msnake_reset.
+ * msnake_step on a handle with auto_reset = 0 followed by msnake_reset_envs(done_dev, obs_dev, ...) on the same
+ * stream gives exactly what auto_reset = 1 gives, plus the terminal observations and the truncation flags.
+ * mask_dev NULL is MSNAKE_E_ARG (msnake_reset resets every env).  Both observation pointers need 4-byte
+ * alignment at obs_scale 4 / 7 (MSNAKE_E_ALIGN).  Asynchronous; adds nothing to env_steps. */
+int msnake_reset_envs(msnake_handle h, const uint8_t* mask_dev, uint8_t* obs_dev, uint8_t* final_obs_dev,
+                      uint8_t* truncated_dev, void* stream);
 
 /* One lockstep step of every env.  actions_dev: int32 [num_envs][action_stride], entry s of a
  * row is snake s's action in {0..4}; action_stride >= n_snakes, surplus entries are ignored

@@ -287,10 +287,12 @@ int msnake_obs_shape(msnake_handle h, int32_t* H, int32_t* W, int32_t* C) {
 }
 
 static int launch(msnake_handle h, int mode, const int32_t* actions, int32_t action_stride, uint8_t* obs, float* rew,
-                  uint8_t* done, msnake_info* info, void* stream) {
+                  uint8_t* done, msnake_info* info, void* stream, const uint8_t* env_mask = nullptr,
+                  uint8_t* truncated = nullptr) {
     msnake::StepParams p = h->p;
     p.actions = actions; p.action_stride = action_stride;
     p.obs = obs; p.rest.rew = rew; p.rest.done = done; p.rest.info = info;
+    p.rest.env_mask = env_mask; p.rest.truncated = truncated;  // (MODE 1 / 2 only; msnake_reset_envs)
     DeviceGuard guard(h->cfg.device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (obs && p.obs_scale > 1 && ((uintptr_t)obs & 3))  // the fused x4 / x7 copy-out stores dwords
@@ -307,6 +309,19 @@ static int launch(msnake_handle h, int mode, const int32_t* actions, int32_t act
 int msnake_reset(msnake_handle h, uint8_t* obs_dev, void* stream) {
     if (int rc = check(h)) return rc;
     return launch(h, 1, nullptr, 0, obs_dev, nullptr, nullptr, nullptr, stream);
+}
+
+int msnake_reset_envs(msnake_handle h, const uint8_t* mask_dev, uint8_t* obs_dev, uint8_t* final_obs_dev,
+                      uint8_t* truncated_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    if (!mask_dev) return fail(MSNAKE_E_ARG, "msnake_reset_envs: mask_dev is NULL (msnake_reset resets every env)");
+    // both observation pointers are checked before anything is launched
+    if (h->p.obs_scale > 1 && (((uintptr_t)obs_dev | (uintptr_t)final_obs_dev) & 3))
+        return fail(MSNAKE_E_ALIGN, "obs_dev and final_obs_dev must be 4-byte aligned when obs_scale > 1");
+    // the selected envs' terminal observations first (a masked render), then the masked reset on the same stream
+    if (final_obs_dev)
+        if (int rc = launch(h, 2, nullptr, 0, final_obs_dev, nullptr, nullptr, nullptr, stream, mask_dev)) return rc;
+    return launch(h, 1, nullptr, 0, obs_dev, nullptr, nullptr, nullptr, stream, mask_dev, truncated_dev);
 }
 
 int msnake_render(msnake_handle h, uint8_t* obs_dev, void* stream) {

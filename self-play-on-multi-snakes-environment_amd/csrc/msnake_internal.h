@@ -77,6 +77,9 @@ struct StepRest {
     uint64_t obs_step_stride;    // MODE 3: bytes between consecutive steps' observations (0 = overwrite)
     uint64_t scalar_step_stride; // MODE 3: elements between consecutive steps' rew/done/info
     uint32_t stream_obs;         // (host copy; the kernel gets it in pk2)
+    // appended behind the fields above, so their offsets (and the preloaded arguments) stay put
+    const uint8_t* env_mask;     // MODE 1 / 2 (msnake_reset_envs): non-NULL -> only envs with env_mask[e] != 0 are reset / rendered
+    uint8_t* truncated;          // MODE 1 (msnake_reset_envs): per env, 1 = the episode was cut by max_steps (may be NULL)
 };
 
 // pk2: flag bits preloaded with the other kernel arguments

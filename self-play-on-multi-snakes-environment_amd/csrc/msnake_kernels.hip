@@ -258,6 +258,12 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     b = (b & ~63u) | ((b & 7u) << 3) | ((b >> 3) & 7u);
     const int e = (int)(b * epb) + wave;
     if (e >= nenv) return;
+    // msnake_reset_envs: the wave of an env the mask does not select leaves before it loads anything; its state and its
+    // observation row stay as they are (MODE 1 reports it as not truncated)
+    if ((MODE == 1 || MODE == 2) && p.env_mask && uni(p.env_mask[e]) == 0u) {
+        if (MODE == 1 && p.truncated && lane == 0) p.truncated[e] = 0;
+        return;
+    }
 
     // pk0 = dim | n_fruits<<6 | action_stride<<12 | auto_reset<<15 | max_steps<<16 ; pk1 = S | cap<<16
     // pk2 = PK2_* flags
@@ -703,6 +709,15 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     };
 
     if (MODE == 1) {
+        if (p.truncated) {
+            // msnake_reset_envs: the episode was cut by the time limit iff it has ended, t >= max_steps and the rule set's own
+            // end condition does not hold -- [S]/[A]: the main snake is dead (a dead snake's body is cleared, len 0);
+            // [N]: the main snake's alive bit, the reference's done = snake.alive ([N]:107, sic; done0 in the step)
+            const uint32_t fl = rdlane(hv, HDR_FLAGS);
+            const bool ended = RULES == MSNAKE_RULES_NEW_WORLD ? (fl & 1u) != 0u : (rdlane(hv, SN_A(0)) >> 16) == 0u;
+            const bool cut = (fl & HDR_FLAG_FINISHED) != 0u && rdlane(hv, HDR_T) >= max_steps && !ended;
+            if (lane == 0) p.truncated[e] = cut ? 1 : 0;
+        }
         do_reset();
         HV_SET_C(HDR_EP_RETURN, 0u);
         HV_SET_C(HDR_EP_LEN, 0u);

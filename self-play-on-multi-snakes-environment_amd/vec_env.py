@@ -45,6 +45,28 @@ def normalize_actions(actions, num_envs, n_snakes):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def normalize_mask(mask, num_envs):
+    """Env selection for a masked reset -> uint8 [num_envs] (1 = reset).
+
+    A NumPy bool array is the mask itself (gymnasium's reset_mask, e.g. the `done` array step() returns); anything
+    else is a sequence of env indices (envpool's reset(env_ids)).  Device tensors are handled by the env itself.
+    """
+    if isinstance(mask, np.ndarray) and mask.dtype == np.bool_:
+        if mask.shape != (num_envs,):
+            raise ValueError(f"a bool mask must have shape ({num_envs},), got {mask.shape}")
+        return mask.astype(np.uint8)
+    idx = np.asarray(mask)
+    if idx.size == 0:
+        idx = idx.reshape(0).astype(np.int64)
+    if idx.ndim != 1 or not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError(f"mask must be a bool array of shape ({num_envs},) or a sequence of env indices, got {mask!r}")
+    if ((idx < 0) | (idx >= num_envs)).any():
+        raise ValueError(f"env indices must lie in [0, {num_envs})")
+    m = np.zeros(num_envs, np.uint8)
+    m[idx] = 1
+    return m
+
+
 class LazyInfos:
     """Sequence of per-env info dicts, materialised on access.
 
@@ -52,10 +74,16 @@ class LazyInfos:
     Monitor's info['episode'] = {'r','l','t'} on the step an episode ends (monitor.py:61-78).
     Building 4096 dicts per step would dominate the step time, so they are built on demand;
     `episodes()` is the fast path for the `info.get('episode')` scan at ppo_multi_agent.py:187-190.
+    With `terminal` = (final_obs rows of the done envs in env order, truncated flags of every env) -- a
+    terminal_obs=True env -- done envs also get Stable-Baselines3's "terminal_observation" and
+    "TimeLimit.truncated".
     """
 
-    def __init__(self, done, num_snakes, ep_return, ep_len, t_elapsed):
+    def __init__(self, done, num_snakes, ep_return, ep_len, t_elapsed, terminal=None):
         self._done, self._ns, self._r, self._l, self._t = done, num_snakes, ep_return, ep_len, t_elapsed
+        self._terminal = terminal
+        if terminal is not None:
+            self._row = np.cumsum(done) - 1  # env i's row among the done envs' terminal observations
 
     def __len__(self):
         return len(self._done)
@@ -70,6 +98,9 @@ class LazyInfos:
         info = {"ale.lives": 1, "num_snakes": int(self._ns[i])}
         if self._done[i]:
             info["episode"] = {"r": round(float(self._r[i]), 6), "l": int(self._l[i]), "t": self._t}
+            if self._terminal is not None:
+                info["terminal_observation"] = self._terminal[0][self._row[i]]
+                info["TimeLimit.truncated"] = bool(self._terminal[1][i])
         return info
 
     def __iter__(self):
@@ -88,7 +119,11 @@ class MultiSnakeVecEnv:
     def __init__(self, num_envs, dim=19, n_snakes=3, n_fruits=None, rules="snake_env", seed=0,
                  env_id_base=0, device=None, max_steps=2000, auto_reset=True, obs_scale=1,
                  declared_channels=6, host_views=False, envs_per_block=0, record_policy="auto",
-                 obs_store_policy="auto", tape_store_policy="auto"):
+                 obs_store_policy="auto", tape_store_policy="auto", terminal_obs=False):
+        """terminal_obs=True (needs auto_reset=True): the handle runs without the in-kernel auto reset and every
+        step_device() follows the step with msnake_reset_envs(done) on the same stream -- the same results, plus the
+        terminal observation of every episode (`final_obs`, valid where done) and whether the time cap ended it
+        (`truncated`).  One or two more launches per step; rollout_device() is not available then."""
         import torch  # device memory and streams only
 
         if not torch.cuda.is_available():
@@ -104,11 +139,15 @@ class MultiSnakeVecEnv:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         rules_id = _capi.RULES[rules] if isinstance(rules, str) else int(rules)
+        self.terminal_obs = bool(terminal_obs)
+        if self.terminal_obs and not auto_reset:
+            raise ValueError("terminal_obs=True needs auto_reset=True (it replaces the in-kernel auto reset)")
         if n_fruits is None:
             n_fruits = n_snakes
         self.cfg = _capi.MsnakeConfig(ctypes.sizeof(_capi.MsnakeConfig), self.device.index or 0, int(num_envs),
                                       int(dim), int(n_snakes), int(n_fruits), rules_id, int(max_steps),
-                                      int(bool(auto_reset)), int(obs_scale), int(seed), int(env_id_base),
+                                      int(bool(auto_reset) and not self.terminal_obs), int(obs_scale), int(seed),
+                                      int(env_id_base),
                                       # launch tuning (msnake_config, ABI 3): how the work is laid out, never a result
                                       int(envs_per_block), _capi.RECORD_POLICY[record_policy],
                                       _capi.STORE_POLICY[obs_store_policy], _capi.STORE_POLICY[tape_store_policy])
@@ -129,6 +168,11 @@ class MultiSnakeVecEnv:
             self._rew = torch.zeros(self.num_envs, dtype=torch.float32, device=self.device)
             self._done = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
             self._info = torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.device)
+            # terminal_obs=True: overwritten by every step (final_obs rows are valid where done)
+            self.final_obs = self.truncated = None
+            if self.terminal_obs:
+                self.final_obs = torch.zeros((self.num_envs,) + self.obs_shape, dtype=torch.uint8, device=self.device)
+                self.truncated = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
         # NumPy-returning calls copy device -> host.  Default: fresh arrays every call, like the
         # reference's np.stack (pageable copy, ~10 GB/s).  host_views=True returns views of pinned
         # staging buffers instead (~5x faster, but OVERWRITTEN by the next call: copy what you keep,
@@ -145,6 +189,9 @@ class MultiSnakeVecEnv:
         self._p_obs, self._p_rew = self._obs.data_ptr(), self._rew.data_ptr()
         self._p_done, self._p_info = self._done.data_ptr(), self._info.data_ptr()
         self._step_fn = self._L.msnake_step
+        self._reset_envs_fn = self._L.msnake_reset_envs
+        if self.terminal_obs:
+            self._p_final, self._p_trunc = self.final_obs.data_ptr(), self.truncated.data_ptr()
         self._cur_stream = torch.cuda.current_stream
 
     # ------------------------------------------------------------------ device-side API
@@ -163,9 +210,41 @@ class MultiSnakeVecEnv:
             raise ValueError(f"out must be a contiguous uint8 tensor of shape {want} on {self.device}")
         return out
 
-    def reset_device(self, out=None):
+    def _mask(self, mask):
+        """mask -> contiguous uint8 [num_envs] tensor on this device (a tensor that already is one is used as it is)."""
+        torch = self._torch
+        if isinstance(mask, torch.Tensor):
+            if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (self.num_envs,):
+                raise ValueError(f"a mask tensor must be bool or uint8 of shape ({self.num_envs},), got {mask.dtype} "
+                                 f"{tuple(mask.shape)}")
+            if mask.dtype == torch.uint8 and mask.device == self.device and mask.is_contiguous():
+                return mask
+            return mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        return torch.from_numpy(normalize_mask(mask, self.num_envs)).to(self.device)
+
+    def _flags_out(self, out):
+        torch = self._torch
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device or
+                tuple(out.shape) != (self.num_envs,) or not out.is_contiguous()):
+            raise ValueError(f"truncated_out must be a contiguous uint8 tensor of shape ({self.num_envs},) on {self.device}")
+        return out
+
+    def reset_device(self, mask=None, out=None, final_out=None, truncated_out=None):
+        """mask=None: reset every env.  Otherwise reset only the envs `mask` selects (a bool / uint8 tensor or NumPy
+        bool array of shape [num_envs], or a sequence of env indices): their reset observations go to `out`, their
+        pre-reset observations to `final_out` (if given), the truncation flag of every env to `truncated_out` (if
+        given); rows of unselected envs are left untouched.  Returns `out`; nothing is synchronised."""
         obs = self._out(out)
-        _capi.check(self._L.msnake_reset(self._h, obs.data_ptr(), self._stream()), "msnake_reset")
+        if mask is None:
+            if final_out is not None or truncated_out is not None:
+                raise ValueError("final_out / truncated_out need a mask (a full reset has no terminal observations)")
+            _capi.check(self._L.msnake_reset(self._h, obs.data_ptr(), self._stream()), "msnake_reset")
+            return obs
+        m = self._mask(mask)
+        p_final = self._out(final_out).data_ptr() if final_out is not None else None
+        p_trunc = self._flags_out(truncated_out).data_ptr() if truncated_out is not None else None
+        _capi.check(self._reset_envs_fn(self._h, m.data_ptr(), obs.data_ptr(), p_final, p_trunc, self._stream()),
+                    "msnake_reset_envs")
         return obs
 
     def step_device(self, actions, out=None):
@@ -187,6 +266,11 @@ class MultiSnakeVecEnv:
                            self._cur_stream(self.device).cuda_stream)
         if rc < 0:
             _capi.check(rc, "msnake_step")
+        if self.terminal_obs:  # the auto reset, as a masked reset that keeps the terminal observations
+            rc = self._reset_envs_fn(self._h, self._p_done, p_obs, self._p_final, self._p_trunc,
+                                     self._cur_stream(self.device).cuda_stream)
+            if rc < 0:
+                _capi.check(rc, "msnake_reset_envs")
         return obs, self._rew, self._done, self._info
 
     def rollout_device(self, tape, persistent=True, keep_obs=True):
@@ -198,6 +282,9 @@ class MultiSnakeVecEnv:
         only the last step's [n, H, W, C] when keep_obs is False --, rew f32 [T, n], done u8 [T, n],
         info i32 [T, n, 4]); nothing is synchronised."""
         torch = self._torch
+        if self.terminal_obs:
+            raise ValueError("rollout_device() is not available with terminal_obs=True: the tape paths have no per-step "
+                             "masked reset")
         if tape.dtype != torch.int32 or tape.device != self.device or not tape.is_contiguous():
             tape = tape.to(device=self.device, dtype=torch.int32).contiguous()
         if tape.dim() != 3 or tape.shape[1] != self.num_envs or tape.shape[2] < self.n_snakes or tape.shape[0] < 1:
@@ -228,9 +315,12 @@ class MultiSnakeVecEnv:
         self._torch.cuda.current_stream(self.device).synchronize()
         return self._pinned[0].numpy()
 
-    def reset(self):
-        self._tstart = time.time()
-        return self._obs_to_host(self.reset_device())
+    def reset(self, mask=None):
+        """mask=None: reset every env.  Otherwise only the selected envs (see reset_device); the returned array is
+        the full observation batch, in which unselected envs keep their last observation (gymnasium's reset_mask)."""
+        if mask is None:
+            self._tstart = time.time()
+        return self._obs_to_host(self.reset_device(mask))
 
     def step_async(self, actions):
         torch = self._torch
@@ -253,8 +343,11 @@ class MultiSnakeVecEnv:
         else:
             obs_h, rew_h, done_u8, info_h = obs.cpu().numpy(), rew.cpu().numpy(), done.cpu().numpy(), info.cpu().numpy()
         done_h = done_u8.astype(bool)
+        terminal = None
+        if self.terminal_obs:  # (the copies above have synchronised the stream)
+            terminal = (self.final_obs[done.bool()].cpu().numpy(), self.truncated.cpu().numpy())
         infos = LazyInfos(done_h, info_h[:, 2].copy(), info_h[:, 0].copy().view(np.float32), info_h[:, 1].copy(),
-                          round(time.time() - self._tstart, 6))
+                          round(time.time() - self._tstart, 6), terminal)
         return obs_h, rew_h, done_h, infos
 
     def step(self, actions):
