@@ -1,5 +1,6 @@
 /* Sanitizer run of the CPU oracle (test infrastructure): gcc -fsanitize=address,undefined.
- * Steps every rule set with random actions, with and without auto-reset, export/import round trips. */
+ * Steps every rule set with random actions, with and without auto-reset, export/import round trips, and masked
+ * resets (orc_reset_envs) with all-zero, all-one, mixed and done masks, with and without the optional pointers. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -24,6 +25,8 @@ int main(void) {
         float* rew = malloc(sizeof(float) * n); uint8_t* done = malloc(n);
         int32_t* ns = malloc(4 * n); float* er = malloc(4 * n); int32_t* el = malloc(4 * n);
         int32_t* act = malloc(4 * n * 4);
+        uint8_t* fin = malloc((size_t)n * H * W * C); uint8_t* trunc = malloc(n); uint8_t* mask = malloc(n);
+        long masked = 0, cut = 0;
         orc_reset(h, obs);
         long episodes = 0;
         for (int t = 0; t < 400; ++t) {
@@ -37,10 +40,23 @@ int main(void) {
                 if (orc_import_state(h, (t + 1) % n, buf, need) != 0) { printf("import failed\n"); return 1; }
                 free(buf);
             }
+            if (t % 5 == 3) {  /* masked reset: all-zero, all-one, mixed and the step's own done; NULL for what is optional */
+                const int kind = (t / 5) % 4;
+                for (int i = 0; i < n; ++i)
+                    mask[i] = kind == 0 ? 0 : kind == 1 ? 1 : kind == 2 ? (uint8_t)(lcg(&seed) % 3 == 0 ? 0x80 : 0) : done[i];
+                const int nul = (t / 20) % 4;  /* 0: every pointer, 1: no obs, 2: no final_obs / truncated, 3: none */
+                orc_reset_envs(h, mask, nul == 1 || nul == 3 ? NULL : obs, nul >= 2 ? NULL : fin, nul >= 2 ? NULL : trunc);
+                for (int i = 0; i < n; ++i) {
+                    masked += mask[i] != 0;
+                    if (nul < 2) cut += trunc[i];
+                    if (mask[i] && orc_finished(h, i)) { printf("finished survived a masked reset\n"); return 1; }
+                }
+            }
         }
         orc_render(h, obs);
-        printf("cfg %u (rules %d dim %d ns %d nf %d auto %d): %ld episode ends, ok\n", c, cfgs[c][0], cfgs[c][1], cfgs[c][2],
-               cfgs[c][3], cfgs[c][4], episodes);
+        printf("cfg %u (rules %d dim %d ns %d nf %d auto %d): %ld episode ends, %ld masked resets, %ld cut by the cap, ok\n", c,
+               cfgs[c][0], cfgs[c][1], cfgs[c][2], cfgs[c][3], cfgs[c][4], episodes, masked, cut);
+        free(fin); free(trunc); free(mask);
         free(obs); free(rew); free(done); free(ns); free(er); free(el); free(act);
         orc_destroy(h);
     }

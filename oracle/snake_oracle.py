@@ -46,6 +46,9 @@ def lib():
         L.orc_obs_shape.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int32)] * 3
         L.orc_reset.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.orc_render.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.orc_reset_envs.argtypes = [ctypes.c_void_p] * 5
+        L.orc_finished.restype = ctypes.c_int32
+        L.orc_finished.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.orc_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_void_p] * 6
         L.orc_step_mt.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_void_p] * 6
         L.orc_rollout_mt.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 6
@@ -160,6 +163,34 @@ class Oracle:
     def render(self):
         self.L.orc_render(self.h, self.obs.ctypes.data)
         return self.obs
+
+    def reset_envs(self, mask, obs=True, final_obs=True, truncated=True):
+        """orc_reset_envs: the masked reset of include/msnake.h (msnake_reset_envs) on the oracle.  `mask`: [num_envs],
+        non-zero = selected.  obs / final_obs / truncated: True = this object's own buffer (self.obs, self.final_obs,
+        self.truncated), None = not wanted (NULL), or a C-contiguous uint8 array to write into.  Only the rows of
+        selected envs are written in obs and final_obs; every entry of truncated is.  Returns the three."""
+        m = np.asarray(mask)
+        m = np.ascontiguousarray(m if m.dtype == np.uint8 else m != 0, dtype=np.uint8)  # (uint8 bytes go in as they are)
+        assert m.shape == (self.num_envs,)
+        if final_obs is True:
+            if not hasattr(self, "final_obs"):
+                self.final_obs = np.zeros_like(self.obs)
+            final_obs = self.final_obs
+        if truncated is True:
+            if not hasattr(self, "truncated"):
+                self.truncated = np.zeros(self.num_envs, np.uint8)
+            truncated = self.truncated
+        if obs is True:
+            obs = self.obs
+        for a, shape in ((obs, self.obs.shape), (final_obs, self.obs.shape), (truncated, (self.num_envs,))):
+            assert a is None or (a.dtype == np.uint8 and a.shape == shape and a.flags.c_contiguous)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        self.L.orc_reset_envs(self.h, m.ctypes.data, ptr(obs), ptr(final_obs), ptr(truncated))
+        return obs, final_obs, truncated
+
+    def finished(self, env):
+        """The env's episode has ended (done with auto_reset off) and it was not reset since."""
+        return bool(self.L.orc_finished(self.h, env))
 
     def step(self, actions, threads=1, want_obs=True):
         a = np.ascontiguousarray(actions, dtype=np.int32)

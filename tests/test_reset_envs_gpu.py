@@ -2,8 +2,9 @@
 
 * terminal_obs=True (msnake_step on a handle without auto reset, then msnake_reset_envs(done)) reproduces the in-kernel
   auto reset byte for byte, and adds the terminal observation and the truncation flag of every episode;
-* both are checked against the CPU oracle run without auto reset, on which the masked reset is emulated with its
-  state export / import (the unselected envs' words survive a full reset);
+* both are checked against the CPU oracle run without auto reset and its own masked reset (Oracle.reset_envs, pinned to
+  the reference's recordings by tests/test_oracle_reset_envs.py); one test also keeps the older emulation of it by state
+  export / import (the unselected envs' words survive a full reset), which lives in that CPU test;
 * a masked reset leaves the rows and the state of unselected envs alone, and an all-one mask is msnake_reset.
 Bit-exact throughout: this is integer / byte work."""
 import numpy as np
@@ -22,36 +23,6 @@ def _mk(**kw):
 def _oracle(**kw):
     from oracle.snake_oracle import Oracle
     return Oracle(**kw)
-
-
-def _raw_words(ora, e):
-    L = ora.L
-    n = L.orc_export_state(ora.h, e, None, 0)
-    buf = np.zeros(n, np.int32)
-    L.orc_export_state(ora.h, e, buf.ctypes.data, n)
-    return buf
-
-
-def _import_words(ora, e, words):
-    assert ora.L.orc_import_state(ora.h, e, words.ctypes.data, len(words)) == 0
-
-
-def _cut_by_time(words, rules, max_steps):
-    """The truncation flag of a FINISHED episode from its canonical words: t >= max_steps and the rule set's own end
-    condition does not hold ([S]/[A]: the main snake is dead = its body is empty; [N]: its alive bit, done = alive)."""
-    k = 8 + 2 * int(words[6])  # snake 0: len, v0, v1, grow_to, alive, in_dead
-    ended = bool(words[k + 4]) if rules == "new_world" else int(words[k]) == 0
-    return int(words[0]) >= max_steps and not ended
-
-
-def _masked_reset_oracle(ora, mask):
-    """msnake_reset_envs on the oracle: the unselected envs' raw words are exported, every env is reset, and the
-    saved words are imported again; then every row is re-rendered."""
-    keep = {e: _raw_words(ora, e) for e in range(ora.num_envs) if not mask[e]}
-    ora.reset()
-    for e, w in keep.items():
-        _import_words(ora, e, w)
-    return ora.render().copy()
 
 
 @pytest.mark.parametrize("scale", [1, 4])
@@ -95,9 +66,8 @@ def test_terminal_obs_and_truncation_against_the_oracle(rules, dim, ns):
         obs, rew, done, infos = env.step(act)
         o_obs, o_rew, o_done = (x.copy() for x in ora.step(act)[:3])
         assert np.array_equal(rew, o_rew) and np.array_equal(done, o_done.astype(bool)), f"rew/done differ at step {t}"
-        want_trunc = np.zeros(n, np.uint8)
-        for e in np.nonzero(done)[0]:
-            want_trunc[e] = _cut_by_time(_raw_words(ora, e), rules, max_steps)
+        want_obs, _, want_trunc = ora.reset_envs(o_done)  # (into ora.obs: the done envs' rows become their reset rows)
+        want_trunc = want_trunc.copy()
         final, trunc = env.final_obs.cpu().numpy(), env.truncated.cpu().numpy()
         assert np.array_equal(final[done], o_obs[done]), f"terminal observations differ at step {t}"
         assert np.array_equal(trunc, want_trunc), f"truncation flags differ at step {t}"
@@ -107,7 +77,6 @@ def test_terminal_obs_and_truncation_against_the_oracle(rules, dim, ns):
         assert all("terminal_observation" not in infos[e] for e in np.nonzero(~done)[0][:8])
         n_trunc += int(want_trunc.sum())
         n_term += int(done.sum()) - int(want_trunc.sum())
-        want_obs = _masked_reset_oracle(ora, done)
         assert np.array_equal(obs, want_obs), f"reset observations differ at step {t}"
     assert n_trunc > 0 and n_term > 0, (n_trunc, n_term)
     env.close()
@@ -117,9 +86,11 @@ def test_masked_reset_without_auto_reset():
     import torch
     n, ns, dim, max_steps, sentinel = 40, 3, 10, 12, 0xA5
     kw = dict(num_envs=n, dim=dim, n_snakes=ns, rules="snake_env", seed=8, max_steps=max_steps)
+    from test_oracle_reset_envs import cut_by_time, emulated_masked_reset
     env = _mk(auto_reset=False, **kw)
     ora = _oracle(auto_reset=False, **kw)
-    env.reset(); ora.reset()
+    emu = _oracle(auto_reset=False, **kw)  # the same oracle, on which the masked reset is emulated by state export / import
+    env.reset(); ora.reset(); emu.reset()
     rs = np.random.default_rng(11)
 
     def advance(k):
@@ -127,6 +98,7 @@ def test_masked_reset_without_auto_reset():
             act = rs.integers(0, 5, (n, ns)).astype(np.int32)
             obs, rew, done, _ = env.step(act)
             o_obs, o_rew, o_done = ora.step(act)[:3]
+            emu.step(act)
             assert np.array_equal(obs, o_obs) and np.array_equal(rew, o_rew) and np.array_equal(done, o_done.astype(bool))
 
     one = np.zeros(n, bool)
@@ -142,13 +114,17 @@ def test_masked_reset_without_auto_reset():
         before = [env.get_state_words(e) for e in range(n)]
         before_blob = env.get_state_all()
         final_want = ora.render().copy()
+        assert [bool(before[e][7] & 0x100) for e in range(n)] == [ora.finished(e) for e in range(n)], i
         out = torch.full(shape, sentinel, dtype=torch.uint8, device=env.device)
         final_out = torch.full(shape, sentinel, dtype=torch.uint8, device=env.device)
         trunc_out = torch.full((n,), sentinel, dtype=torch.uint8, device=env.device)
-        trunc_want = np.array([mask[e] and bool(before[e][7] & 0x100) and _cut_by_time(before[e], "snake_env", max_steps)
-                               for e in range(n)], np.uint8)
+        trunc_emu = np.array([mask[e] and bool(before[e][7] & 0x100) and cut_by_time(before[e], "snake_env", max_steps)
+                              for e in range(n)], np.uint8)
         env.reset_device(form(mask), out=out, final_out=final_out, truncated_out=trunc_out)
-        want = _masked_reset_oracle(ora, mask)
+        trunc_want = ora.reset_envs(mask)[2].copy()
+        want = ora.render().copy()
+        assert np.array_equal(ora.final_obs[mask], final_want[mask]), i
+        assert np.array_equal(emulated_masked_reset(emu, mask), want) and np.array_equal(trunc_emu, trunc_want), i
         out, final_out, trunc = out.cpu().numpy(), final_out.cpu().numpy(), trunc_out.cpu().numpy()
         assert np.array_equal(out[mask], want[mask]), i
         assert np.array_equal(final_out[mask], final_want[mask]), i
