@@ -23,6 +23,7 @@ src/baselines/bench/monitor.py:57-78, because those files need packages that are
 not installed (TF / mpi4py / cloudpickle imports in baselines/__init__ chain).
 
 Usage: python tools/gen_golden.py            (rewrites tests/golden/*)
+       python tools/gen_golden.py long_play  (only tests/golden/long_play.npz)
 """
 import contextlib
 import hashlib
@@ -742,8 +743,56 @@ def gen_random_configs(k=150, seed=777):
     print(f"random_configs.npz: {k} configurations x {T} steps, {os.path.getsize(path) / 1024:.0f} KiB")
 
 
+# ----------------------------------------------------------------------------- long scripted play
+def gen_long_play():
+    """long_play.npz: the runs of tests/scripted_play.py FIXTURE_RUNS.  The reference plays under the scripted policies
+    (Hamiltonian cycle / safe greedy), which choose every action from the REFERENCE's canonical state, for thousands
+    of steps: boards fill up, bodies pass 64 cells, episodes run into the 2000-step cap, the adversarial fruit list
+    passes 64 entries.  Per run <name>: <name>_actions, _reward, _done, _num_snakes, _ep_return, _ep_len per step and
+    env; observations and states as one running BLAKE2b-256 (golden_util.feed_step): _tag after every step,
+    _reset_tag after the first reset, _digest at the end; and, so that coverage can be read from the file itself,
+    _body_max and _n_fruits (longest body and fruit count per step and env, as the reference had them)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from golden_util import feed_step
+    import scripted_play as sp
+    out, lines = {}, []
+    for name, cfg in sp.FIXTURE_RUNS.items():
+        rules, E, ns, T = cfg["rules"], cfg["num_envs"], cfg["n_snakes"], cfg["steps"]
+        vec = VecHarness(rules, cfg["dim"], ns, cfg["n_fruits"], cfg["seed"], E, env_id_base=cfg["env_id_base"])
+        h = hashlib.blake2b(digest_size=32)
+        reset_tag = feed_step(h, vec.reset(), [canon_state(e) for e in vec.envs], rules)
+        states = [canon_state(e) for e in vec.envs]
+        rs = sp.policy_rng(cfg)
+        r = dict(actions=np.zeros((T, E, ns), np.int8), reward=np.zeros((T, E), np.float32), done=np.zeros((T, E), np.uint8),
+                 num_snakes=np.zeros((T, E), np.int8), ep_return=np.zeros((T, E), np.float32), ep_len=np.zeros((T, E), np.int16),
+                 tag=np.zeros(T, np.uint32), body_max=np.zeros((T, E), np.int16), n_fruits=np.zeros((T, E), np.int16))
+        for t in range(T):
+            a = sp.choose_actions(cfg, states, rs)
+            ob, rew, d, n_, er, el = vec.step(a)
+            states = [canon_state(e) for e in vec.envs]
+            r["actions"][t] = a
+            for key, v in zip(("reward", "done", "num_snakes", "ep_return", "ep_len"), (rew, d, n_, er, el)):
+                r[key][t] = v
+            r["tag"][t] = feed_step(h, ob, states, rules)
+            r["body_max"][t] = [max(len(b) for b in st["snakes"]) for st in states]
+            r["n_fruits"][t] = [len(st["fruits"]) for st in states]
+        r["reset_tag"] = np.array([reset_tag], np.uint32)
+        r["digest"] = np.frombuffer(h.digest(), np.uint8)
+        cov = sp.coverage(cfg, r["body_max"], r["n_fruits"], r["done"], r["ep_len"])
+        sp.check_coverage(cfg, cov)
+        out.update({f"{name}_{k}": v for k, v in r.items()})
+        lines.append(f"  {name}: {E} envs x {T} steps, {cov}")
+    out["meta"] = np.array(json.dumps(dict(runs=sp.FIXTURE_RUNS)))
+    path = os.path.join(OUT, "long_play.npz")
+    np.savez_compressed(path, **out)
+    print(f"long_play.npz: {len(sp.FIXTURE_RUNS)} runs, {os.path.getsize(path) / 1024:.0f} KiB")
+    print("\n".join(lines))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if sys.argv[1:] == ["long_play"]:
+        return gen_long_play()
     gen_philox_kat()
     gen_edges()
     S, N, A = RULES_SNAKE_ENV, RULES_NEW_WORLD, RULES_ADVERSARIAL
@@ -768,6 +817,7 @@ def main():
     gen_tape("tape_A_6x6_3", A, 6, 3, 3, seed=13, num_envs=12, steps=96)
     gen_tape("tape_A_19x19_1", A, 19, 1, 1, seed=14, num_envs=8, steps=64)
     gen_random_configs()
+    gen_long_play()
 
 
 if __name__ == "__main__":
