@@ -29,6 +29,9 @@
  *                      counterpart (env state is never checkpointed there); used by
  *                      the parity tests to install hand-built states and by callers to checkpoint.
  *   msnake_state_blob_info: no reference counterpart either; validates such a checkpoint on the host.
+ *   msnake_scripted_actions: no reference counterpart (its opponents are always networks: evaluate_snake.py,
+ *                      ppo_multi_agent.py:28-50 MultiModel.multi_step); a fixed, deterministic opponent and the
+ *                      safe-move mask, computed on the device from the state the handle already owns.
  *   msnake_get_stats <- the epinfobuf aggregation in ppo_multi_agent.py:288,331,366-390
  *
  * RNG contract (shared with oracle/ and tests/golden): draw i of global env g is word (i & 3) of
@@ -212,6 +215,33 @@ int msnake_state_blob_info(const void* buf, size_t bytes, msnake_blob_info* out)
 
 /* Render the current state of every env without stepping (asynchronous). */
 int msnake_render(msnake_handle h, uint8_t* obs_dev, void* stream);
+
+/* Scripted opponents and safe-move masks, computed on the device from the current state of every env (the state
+ * the canonical words above describe).  Serves the callers that today can only put a network or the constant
+ * action 1 into an opponent's column (evaluate_snake.py, ppo_multi_agent.py:28-50).  Terms: `used` = the cells of
+ * every body in the env, heads, tails, new_world bodies kept after a self-hit and stacked duplicates included;
+ * move a in 1..4 goes from the head by (+1,0), (0,+1), (-1,0), (0,-1) on (c0,c1); a move is open iff its target
+ * lies in [0,dim)^2 and not in `used`.
+ *   MSNAKE_POLICY_SAFE_GREEDY: the first open move, in the order 1, 2, 3, 4, whose target has the strictly
+ *     smallest L1 distance to any fruit of the state's fruit list (adversarial: the complete list; distance 0
+ *     when the list is empty); 0 when no move is open or the body is empty.  The velocity plays no part.
+ *   MSNAKE_POLICY_HAMILTONIAN: the head's successor on a fixed Hamiltonian cycle of an even board (column 0 is
+ *     the return lane, the rows run back and forth over columns 1..dim-1): at (x,y), x == 0 -> (y > 0 ? 4 : 1);
+ *     y even -> (x < dim-1 ? 1 : 2); y == dim-1 -> 3; else (x > 1 ? 3 : 2).  0 for an empty body or a head
+ *     outside the grid.  Odd dim is MSNAKE_E_ARG.
+ * actions_dev: int32 [num_envs][action_stride], the buffer the step takes; entry s of every row is written for
+ * each s with bit s of snake_mask set, all other entries are left untouched.  safe_dev (may be NULL): uint8
+ * [num_envs][n_snakes], written for every snake whatever snake_mask is: bit a (1..4) is set iff move a is open,
+ * bits 0 and 5..7 are zero, an empty body gives 0.  MSNAKE_POLICY_NONE writes safe_dev only.
+ * The call only reads the handle's state (no random numbers are drawn, the Philox counter stays), allocates
+ * nothing and does not synchronise: it can be captured into a HIP graph in front of the step.  Asynchronous on
+ * `stream`; adds nothing to env_steps.  MSNAKE_E_ARG, before any device work: unknown policy; a snake_mask bit
+ * >= n_snakes; action_stride < n_snakes or actions_dev NULL when actions are to be written; nothing to write. */
+#define MSNAKE_POLICY_NONE 0         /* write no actions (safe_dev only) */
+#define MSNAKE_POLICY_SAFE_GREEDY 1
+#define MSNAKE_POLICY_HAMILTONIAN 2
+int msnake_scripted_actions(msnake_handle h, int32_t policy, uint32_t snake_mask, int32_t* actions_dev,
+                            int32_t action_stride, uint8_t* safe_dev, void* stream);
 
 /* Copy the aggregate statistics to the host.  Blocking: waits for the device (every step issued so
  * far, on any stream) before it sums the per-env totals.  episodes / ep_len_sum / ep_return_sum /

@@ -394,6 +394,30 @@ int msnake_rollout_tape(msnake_handle h, const int32_t* actions_dev, int32_t act
     return MSNAKE_OK;
 }
 
+int msnake_scripted_actions(msnake_handle h, int32_t policy, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride,
+                            uint8_t* safe_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    const int ns = h->p.n_snakes;
+    if (policy != MSNAKE_POLICY_NONE && policy != MSNAKE_POLICY_SAFE_GREEDY && policy != MSNAKE_POLICY_HAMILTONIAN)
+        return fail(MSNAKE_E_ARG, "msnake_scripted_actions: policy %d is not one of MSNAKE_POLICY_*", policy);
+    if (snake_mask >> ns) return fail(MSNAKE_E_ARG, "msnake_scripted_actions: snake_mask 0x%x has a bit >= n_snakes=%d", snake_mask, ns);
+    if (policy == MSNAKE_POLICY_HAMILTONIAN && (h->p.dim & 1))
+        return fail(MSNAKE_E_ARG, "msnake_scripted_actions: policy HAMILTONIAN needs an even dim (the cycle), got dim %d", h->p.dim);
+    const bool writes_actions = policy != MSNAKE_POLICY_NONE && snake_mask != 0;
+    if (!writes_actions && !safe_dev)
+        return fail(MSNAKE_E_ARG, "msnake_scripted_actions: nothing to write (policy NONE or snake_mask 0, and safe_dev is NULL)");
+    if (writes_actions && !actions_dev) return fail(MSNAKE_E_ARG, "msnake_scripted_actions: actions_dev is NULL");
+    if (writes_actions && action_stride < ns)
+        return fail(MSNAKE_E_ARG, "msnake_scripted_actions: action_stride %d must be >= n_snakes=%d", action_stride, ns);
+    if (writes_actions && ((uintptr_t)actions_dev & 3)) return fail(MSNAKE_E_ALIGN, "actions_dev must be 4-byte aligned");
+    DeviceGuard guard(h->cfg.device);
+    // without actions to write the kernel only fills safe_dev: POLICY_NONE
+    hipError_t e = msnake::launch_scripted(h->p, h->cfg.rules, writes_actions ? policy : MSNAKE_POLICY_NONE, snake_mask, actions_dev,
+                                           action_stride, safe_dev, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return MSNAKE_OK;
+}
+
 // ---- canonical state import / export.  The device packs / unpacks (msnake_state_*_kernel); the host
 //      only sizes buffers and copies.  Blocking: every call starts with a device synchronise. ----
 namespace {

@@ -125,6 +125,9 @@ hipError_t launch_state_pack(const StepParams& p, int rules, int env0, int count
                              hipStream_t stream);
 hipError_t launch_state_unpack(const StepParams& p, int rules, int env0, int count, const uint64_t* offsets,
                                const int32_t* words, uint32_t* status, hipStream_t stream);
+// scripted opponents / safe-move masks from the state in HBM (msnake_scripted.inc); reads the handle's state only
+hipError_t launch_scripted(const StepParams& p, int rules, int policy, uint32_t snake_mask, int32_t* actions, int32_t action_stride,
+                           uint8_t* safe, hipStream_t stream);
 void step_kernel_name(int rules, int n_snakes, int obs_scale, char* out, size_t n);
 
 }  // namespace msnake

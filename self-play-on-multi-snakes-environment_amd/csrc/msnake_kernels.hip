@@ -1957,3 +1957,5 @@ void step_kernel_name(int rules, int n_snakes, int obs_scale, char* out, size_t 
 }
 
 }  // namespace msnake
+
+#include "msnake_scripted.inc"  // msnake_scripted_actions: scripted opponents and safe-move masks (off the step path)

@@ -319,6 +319,75 @@ class MonitorCSV:
         self.f.close()
 
 
+# ----------------------------------------------------------------------------- scripted opponents
+class ScriptedColumns:
+    """The scripted action columns of a team of ScriptedOpponents of one env, in a buffer of its own: refresh() fills the
+    columns of every member with ONE env call per policy, each member's step() then reads its own.  Whoever drives the
+    env calls refresh() once per env step, before the members' step() (Runner.multi_step does)."""
+
+    def __init__(self, env):
+        self.env, self.members, self.filled = env, [], False
+        self.buf = torch.zeros((env.num_envs, env.n_snakes), dtype=torch.int32, device=env.device)
+
+    def add(self, member):
+        if any(m.snake == member.snake for m in self.members):
+            raise ValueError(f"snake {member.snake} already has a scripted opponent in this team")
+        self.members.append(member)
+        self.filled = False
+
+    def refresh(self):
+        by_policy = {}
+        for m in self.members:
+            by_policy.setdefault(m.policy, []).append(m.snake)
+        for policy, snakes in by_policy.items():
+            self.env.scripted_actions_device(policy, snakes=sorted(snakes), out=self.buf)
+        self.filled = True
+
+    def column(self, snake):
+        if not self.filled:
+            raise RuntimeError("ScriptedColumns.refresh() has not been called since the team was put together")
+        return self.buf[:, snake].to(torch.int64)  # (a copy: the next refresh() overwrites the buffer)
+
+
+class ScriptedOpponent:
+    """A fixed, deterministic opponent in the place of a CnnPolicy: snake `snake` plays the env's on-device scripted
+    `policy` ("safe_greedy" or "hamiltonian", MultiSnakeVecEnv.scripted_actions_device).  step(obs) has the shape
+    Runner.multi_step calls; the observation is ignored, the env's state is asked.  eps > 0: with probability eps
+    the action is replaced by randint(0, 5), drawn with torch on the env's device from `generator` (the env's own
+    random numbers are never used).  On its own (columns=None) every step() is one env call.  Several opponents of one
+    env given the same ScriptedColumns form a team: one env call per policy and env step for all of them, made by
+    columns.refresh(), which the driver calls before the members' step()."""
+
+    def __init__(self, env, policy, snake, eps=0.0, generator=None, columns=None):
+        if policy not in ("safe_greedy", "hamiltonian"):
+            raise ValueError(f"policy must be 'safe_greedy' or 'hamiltonian', got {policy!r}")
+        if not 0 <= int(snake) < env.n_snakes:
+            raise ValueError(f"snake must lie in [0, {env.n_snakes}), got {snake!r}")
+        self.env, self.policy, self.snake, self.eps, self.generator = env, policy, int(snake), float(eps), generator
+        self.own = columns is None
+        self.columns = ScriptedColumns(env) if columns is None else columns
+        if self.columns.env is not env:
+            raise ValueError("columns belongs to another env")
+        self.columns.add(self)
+
+    def step(self, obs=None):
+        if self.own:
+            self.columns.refresh()
+        a = self.columns.column(self.snake)
+        if self.eps > 0.0:
+            swap = torch.rand(a.shape, device=a.device, generator=self.generator) < self.eps
+            rnd = torch.randint(0, 5, a.shape, device=a.device, generator=self.generator)
+            a = torch.where(swap, rnd, a)
+        return a, None, None
+
+
+def refresh_scripted(opponents):
+    """One refresh() per team among `opponents` (lone ScriptedOpponents ask the env in their own step())."""
+    teams = {id(o.columns): o.columns for o in opponents if isinstance(o, ScriptedOpponent) and not o.own}
+    for columns in teams.values():
+        columns.refresh()
+
+
 # ----------------------------------------------------------------------------- rollouts
 class Runner:
     """ppo_multi_agent.py:145-216 with everything on the device."""
@@ -333,6 +402,7 @@ class Runner:
     def multi_step(self):
         a, v, nlp = self.model.step(self.obs[..., 0:3])
         acts = [a]
+        refresh_scripted(self.opponents)
         for i, opp in enumerate(self.opponents):
             if opp is None:
                 acts.append(torch.ones_like(a))  # ppo_multi_agent.py:32,37
@@ -372,7 +442,7 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
           max_grad_norm=0.5, gamma=0.99, lam=0.95, log_interval=1, nminibatches=8, noptepochs=4,
           cliprange=lambda f: f * 0.1, opponent_save_interval=50, max_saved_opponents=1000, csv_path=None,
           monitor_path=None, seed=0, log_fn=print, amp_dtype=None, json_path=None, tb_dir=None,
-          save_dir=None, save_interval=0, load_path=None, resume=False):
+          save_dir=None, save_interval=0, load_path=None, resume=False, scripted_opponents=None):
     """ppo_multi_agent.py:231-404 (hyper-parameters of test/ppo1_single_test.py:42-47 as defaults).
 
     Checkpoints (ppo_multi_agent.py:112-133, 296-306, 349-364, 392-404), weights only, under `save_dir`
@@ -382,19 +452,27 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
     snake only, :398-401), snake_model_num<N>.pt at the end.  `load_path` initialises the learner and
     its opponents from a weights file (the reference's `baseline_file`, :264-275).  `resume=True`
     continues a run from save_dir/trainer_state.pt (weights, Adam moments, update counter, pool
-    positions -- the reference cannot do this; schedules continue where they stopped)."""
+    positions -- the reference cannot do this; schedules continue where they stopped).
+    `scripted_opponents`, e.g. {1: "safe_greedy"}: those snakes are played by a ScriptedOpponent (a fixed yardstick
+    from update 1 on) instead of a past self; no pool is kept, saved or loaded for them."""
     torch.manual_seed(seed); random.seed(seed)
     dev = env.device
     n_snakes = env.n_snakes
     H, W, _ = env.obs_shape
     model = CnnPolicy((H, W, 3), amp_dtype=amp_dtype).to(dev)
-    opponents = [CnnPolicy((H, W, 3), amp_dtype=amp_dtype).to(dev) for _ in range(n_snakes - 1)]
+    scripted = dict(scripted_opponents or {})
+    if any(not 1 <= int(k) < n_snakes for k in scripted):
+        raise ValueError(f"scripted_opponents: snake indices must lie in [1, {n_snakes}), got {sorted(scripted)}")
+    team = ScriptedColumns(env) if scripted else None   # this run's own: nothing is left behind on the env
+    opponents = [ScriptedOpponent(env, scripted[i + 1], i + 1, columns=team) if i + 1 in scripted else
+                 CnnPolicy((H, W, 3), amp_dtype=amp_dtype).to(dev) for i in range(n_snakes - 1)]
+    learned = [i for i in range(n_snakes - 1) if i + 1 not in scripted]  # opponent slots played by past selves
     if save_dir:
         os.makedirs(save_dir, exist_ok=True)
     if load_path:
-        for m in [model] + opponents:
+        for m in [model] + [opponents[i] for i in learned]:
             load_weights(m, load_path)
-    pools = [OpponentPool(max_saved_opponents, save_dir, i + 1) for i in range(len(opponents))]
+    pools = [OpponentPool(max_saved_opponents, save_dir, i + 1) for i in learned]
     opt = torch.optim.Adam(model.parameters(), lr=lr(1.0), eps=1e-5)
     first_update, model_idx, next_highscore = 1, 0, 5
     state_file = os.path.join(save_dir, "trainer_state.pt") if save_dir else None
@@ -409,6 +487,12 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
         model.load_state_dict(ts["model"])
         opt.load_state_dict(ts["optimizer"])
         first_update, model_idx, next_highscore = ts["update"] + 1, ts["model_idx"], ts["next_highscore"]
+        # pools belong to the opponent slots that past selves play; a state file written with another set of scripted
+        # opponents (files from before the argument existed: every slot) cannot be continued with this one
+        saved_slots = list(ts.get("learned_slots", range(len(ts["pools"]))))
+        if saved_slots != learned:
+            raise RuntimeError(f"resume=True: {state_file} was written with opponent pools for slots {saved_slots}, this run "
+                               f"keeps pools for slots {learned} (scripted_opponents differs)")
         for pool, (idx, num) in zip(pools, ts["pools"]):
             pool.restore(dev, idx, num)
 
@@ -416,7 +500,7 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
         tmp = state_file + ".tmp"
         torch.save({"model": model.state_dict(), "optimizer": opt.state_dict(), "update": update,
                     "model_idx": model_idx, "next_highscore": next_highscore,
-                    "pools": [(p.idx, p.num) for p in pools]}, tmp)
+                    "pools": [(p.idx, p.num) for p in pools], "learned_slots": learned}, tmp)
         os.replace(tmp, state_file)
 
     if fresh:
@@ -438,8 +522,8 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
     mon = MonitorCSV(monitor_path, "msnake") if monitor_path else None
     history, tfirst = [], time.time()
     for update in range(first_update, nupdates + 1):
-        for opp, pool in zip(opponents, pools):
-            pool.load_random(opp)
+        for i, pool in zip(learned, pools):
+            pool.load_random(opponents[i])
         tstart = time.time()
         frac = 1.0 - (update - 1.0) / nupdates
         lrnow, clipnow = lr(frac), cliprange(frac)
@@ -478,7 +562,7 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
                    "fps": int(nbatch / (tnow - tstart)), "explained_variance": explained_variance(values, returns),
                    "eprewmean 100": eprew, "eplenmean": safemean([e["l"] for e in epinfobuf]),
                    "time_elapsed": tnow - tfirst, "ep_rew_mean": eprew}
-            if n_snakes > 1:
+            if pools:
                 kvs["num_opponents"] = pools[0].num
             kvs.update(dict(zip(("policy_loss", "value_loss", "policy_entropy", "approxkl", "clipfrac"), lossvals)))
             history.append(kvs)

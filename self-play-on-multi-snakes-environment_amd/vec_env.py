@@ -193,6 +193,8 @@ class MultiSnakeVecEnv:
         if self.terminal_obs:
             self._p_final, self._p_trunc = self.final_obs.data_ptr(), self.truncated.data_ptr()
         self._cur_stream = torch.cuda.current_stream
+        self._scripted_fn = self._L.msnake_scripted_actions
+        self._scripted_out = None  # scripted_actions_device(out=None): allocated on first use
 
     # ------------------------------------------------------------------ device-side API
     def _stream(self):
@@ -272,6 +274,59 @@ class MultiSnakeVecEnv:
             if rc < 0:
                 _capi.check(rc, "msnake_reset_envs")
         return obs, self._rew, self._done, self._info
+
+    def _safe_out(self, out):
+        torch = self._torch
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device or
+                tuple(out.shape) != (self.num_envs, self.n_snakes) or not out.is_contiguous()):
+            raise ValueError(f"safe_out must be a contiguous uint8 tensor of shape ({self.num_envs}, {self.n_snakes}) on "
+                             f"{self.device}")
+        return out
+
+    def scripted_actions_device(self, policy, snakes=None, out=None, safe_out=None):
+        """Actions of a scripted policy ("safe_greedy", "hamiltonian", or None for the mask alone) for the snakes in
+        `snakes` (indices; default every snake), computed on the device from the env's current state.  They go to
+        columns `snakes` of `out`, an int32 [num_envs, >= n_snakes] device tensor as step_device() takes it; its other
+        columns are left as they are (out=None: a cached, zero-initialised [num_envs, n_snakes] tensor of the env).
+        `safe_out`, a uint8 [num_envs, n_snakes] device tensor, gets every snake's safe-move mask (bit a = move a leads
+        to an on-board cell that no body occupies).  Returns `out`, or (out, safe_out) when a mask was asked for;
+        nothing is synchronised.  Draws no random numbers and changes no env state."""
+        torch = self._torch
+        if policy not in _capi.SCRIPTED_POLICY:
+            raise ValueError(f"policy must be 'safe_greedy', 'hamiltonian' or None, got {policy!r}")
+        if snakes is None:
+            bits = (1 << self.n_snakes) - 1
+        else:
+            bits = 0
+            for s in snakes:
+                if int(s) != s or not 0 <= int(s) < self.n_snakes:
+                    raise ValueError(f"snake indices must lie in [0, {self.n_snakes}), got {s!r}")
+                bits |= 1 << int(s)
+        if out is None:
+            if self._scripted_out is None:
+                with torch.cuda.device(self.device):
+                    self._scripted_out = torch.zeros((self.num_envs, self.n_snakes), dtype=torch.int32, device=self.device)
+            out = self._scripted_out
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.device != self.device or out.dim() != 2 or
+              out.shape[0] != self.num_envs or out.shape[1] < self.n_snakes or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous int32 tensor of shape ({self.num_envs}, >= {self.n_snakes}) on {self.device}")
+        p_safe = self._safe_out(safe_out).data_ptr() if safe_out is not None else None
+        rc = self._scripted_fn(self._h, _capi.SCRIPTED_POLICY[policy], bits, out.data_ptr(), int(out.shape[1]), p_safe,
+                               self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_scripted_actions")
+        return out if safe_out is None else (out, safe_out)
+
+    def safe_moves_device(self, out=None):
+        """uint8 [num_envs, n_snakes]: bit a (1..4) is set iff move a of that snake leads to an on-board cell that no
+        body occupies (the action mask of masked PPO); 0 for an empty body.  Nothing is synchronised."""
+        if out is None:
+            with self._torch.cuda.device(self.device):
+                out = self._torch.empty((self.num_envs, self.n_snakes), dtype=self._torch.uint8, device=self.device)
+        rc = self._scripted_fn(self._h, 0, 0, None, 0, self._safe_out(out).data_ptr(), self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_scripted_actions")
+        return out
 
     def rollout_device(self, tape, persistent=True, keep_obs=True):
         """T lockstep steps from an action tape int32 cuda [T, num_envs, >= n_snakes] in ONE call.

@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""Cost of msnake_scripted_actions next to msnake_step on the same handle.  19x19x3 snake_env at 4 096 and 32 768 envs,
+on a freshly reset batch and 500 steps into safe_greedy play (longer bodies).  The Hamiltonian cycle needs an even
+board: its legs run on a 20x20 handle of the same batch, in the same kind of state.
+
+Two figures per leg, both from HIP events after a warm-up, legs alternating in one process:
+  graph_us: CALLS back-to-back calls captured into one HIP graph (a linear chain) and replayed: the kernel's cadence,
+            free of the host's submission cost;
+  call_us:  CALLS back-to-back calls through the Python wrapper (validation + ctypes + the stream lookup): what a
+            Python caller pays when nothing else is queued; mostly the host's submission rate.
+The step leg plays the constant action 1 (with auto reset), so over its CALLS calls the batch leaves the state the run
+is labelled with; the scripted legs read the restored state every time.  The state is restored before every leg.
+    python tools/scripted_cost.py > profiles/scripted_cost.json"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--envs", type=int, nargs="+", default=[4096, 32768])
+    ap.add_argument("--play-steps", type=int, default=500)
+    args = ap.parse_args()
+    import torch
+    import msnake
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1000.0 / args.calls
+
+    res = {"device": torch.cuda.get_device_name(0), "config": "snake_env 19x19, 3 snakes", "calls_per_leg": args.calls,
+           "rounds": args.rounds, "unit": "us per call: median (min, max) over the rounds",
+           "graph_us": "calls captured into one HIP graph and replayed (kernel cadence)",
+           "call_us": "calls through the Python wrapper (includes the host's submission cost)",
+           "hamiltonian": "on a 20x20 handle of the same batch (the cycle needs an even board)",
+           "msnake_step": "plays the constant action 1 with auto reset: the batch drifts from the labelled state",
+           "batches": {}}
+    for n in args.envs:
+        env = msnake.MultiSnakeVecEnv(n, dim=19, n_snakes=3, rules="snake_env", seed=0)
+        env20 = msnake.MultiSnakeVecEnv(n, dim=20, n_snakes=3, rules="snake_env", seed=0)
+        acts = torch.ones((n, 3), dtype=torch.int32, device=env.device)
+        ones = torch.ones((n, 3), dtype=torch.int32, device=env.device)
+        safe = torch.zeros((n, 3), dtype=torch.uint8, device=env.device)
+        legs = {
+            "safe_greedy": lambda: env.scripted_actions_device("safe_greedy", out=acts),
+            "safe_greedy+mask": lambda: env.scripted_actions_device("safe_greedy", out=acts, safe_out=safe),
+            "hamiltonian_20x20": lambda: env20.scripted_actions_device("hamiltonian", out=acts),
+            "hamiltonian_20x20+mask": lambda: env20.scripted_actions_device("hamiltonian", out=acts, safe_out=safe),
+            "mask_only": lambda: env.safe_moves_device(out=safe),
+            "msnake_step": lambda: env.step_device(ones),
+        }
+        out = {}
+        for state in ("fresh_reset", f"after_{args.play_steps}_greedy_steps"):
+            for e in (env, env20):
+                e.reset_device()
+                if state != "fresh_reset":
+                    for _ in range(args.play_steps):
+                        e.step_device(e.scripted_actions_device("safe_greedy", out=acts))
+            blob = env.get_state_all()
+            graphs = {}
+            side = torch.cuda.Stream()
+            for name, fn in legs.items():
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture wants
+                    fn(), fn()
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    for _ in range(args.calls):
+                        fn()
+                graphs[name] = g
+            times = {k: {"graph_us": [], "call_us": []} for k in legs}
+            for _ in range(args.rounds):
+                for name, fn in legs.items():
+                    env.set_state_all(blob)
+                    times[name]["graph_us"].append(timed(graphs[name].replay))
+                    env.set_state_all(blob)
+                    times[name]["call_us"].append(timed(lambda: [fn() for _ in range(args.calls)]))
+            med = lambda v: [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)]
+            out[state] = {k: {kind: med(v) for kind, v in t.items()} for k, t in times.items()}
+        res["batches"][str(n)] = out
+        env.close(), env20.close()
+    print(json.dumps(res, indent=1))
+
+
+if __name__ == "__main__":
+    main()

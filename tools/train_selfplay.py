@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--save-interval", type=int, default=0, help="also save snake_model_num<N>_<k>.pt every this many updates")
     ap.add_argument("--load", default=None, metavar="FILE", help="initialise learner and opponents from a weights file")
     ap.add_argument("--resume", action="store_true", help="continue from <--save DIR>/trainer_state.pt")
+    ap.add_argument("--opponent", choices=("pool", "safe_greedy", "hamiltonian"), default="pool",
+                    help="who plays the other snakes: past selves from the pool, or a fixed on-device scripted policy")
     args = ap.parse_args()
     import torch
     import msnake
@@ -37,7 +39,8 @@ def main():
     selfplay.learn(env, nsteps=args.nsteps, total_timesteps=args.timesteps, csv_path=args.csv,
                    monitor_path=args.monitor, json_path=args.json, tb_dir=args.tensorboard,
                    amp_dtype=torch.bfloat16 if args.bf16 else None, save_dir=args.save, save_interval=args.save_interval,
-                   load_path=args.load, resume=args.resume)
+                   load_path=args.load, resume=args.resume,
+                   scripted_opponents=None if args.opponent == "pool" else {s: args.opponent for s in range(1, args.snakes)})
     print(env.stats())
     env.close()
 
