@@ -1,0 +1,962 @@
+"""Model-based differential test of every entry point on ONE handle: a seeded random sequence of operations goes to a
+handle and to the CPU oracle side by side, and after every operation everything the operation returns is compared and
+everything it must leave alone is checked.  Integer and byte arithmetic throughout: every comparison is bit-exact.
+
+What this is for: the state one kernel leaves in HBM for a DIFFERENT kernel to pick up (parked Philox draws, the
+finished bit, the overflow ring's head, chunk 0 of the adversarial fruit list, the persistent kernel's 16-step batches,
+the device-side episode totals), and a state made on one record policy and continued on the other.
+
+  gen_ops(cfg, seed, n_ops)  pure host: a list of plain-dict operations, every random choice made (bulk data such as
+                             action tensors is named by a seed in the op and derived from it alone)
+  run(adapter, cfg, ops)     drives an adapter and an Oracle; ops[:k] replays a failure up to the op where it appeared
+  HipAdapter                 the library (msnake.MultiSnakeVecEnv and, for NULL outputs / strides, its C entry points)
+  OracleAdapter              the same interface over a second Oracle (no GPU needed); fault= injects one silent defect
+
+A plain helper module (like scripted_play), imported by tests/test_op_fuzz_host.py and tests/test_op_fuzz_gpu.py.
+
+Every output buffer an adapter hands back is the WHOLE buffer: GUARD bytes of SENT, the payload, GUARD bytes of SENT,
+pre-filled with SENT before the call.  The driver builds the same bytes from the oracle (rows an op must not write keep
+SENT) and compares all of them, so outputs, untouched rows, surplus action columns and guard bands are one comparison.
+"""
+import ctypes
+import struct
+
+import numpy as np
+
+import scripted_play as sp
+
+GUARD, SENT = 64, 0xA5
+ROLLOUT_STEPS = (1, 2, 15, 16, 17, 31, 32, 33, 48)
+INVALID_ACTIONS = (-1, 5, 7)      # as tools/gen_golden.py random_configs mixes them in
+OBS_CAP = 400 << 20               # no single observation buffer above this many bytes
+KINDS = ("step", "step_tape", "rollout", "reset_all", "reset_mask", "render", "scripted", "checkpoint_self", "set_words",
+         "migrate", "stats")
+PAIR_CLASS = {"step": "S", "step_tape": "S", "rollout": "R", "reset_mask": "K", "checkpoint_self": "C", "set_words": "C",
+              "migrate": "M"}
+PAIR_CLASSES = "SRKCM"
+RULE_NAMES = {0: "snake_env", 1: "new_world", 2: "adversarial"}
+
+
+# ----------------------------------------------------------------------------------------------- configurations
+def _cfg(name, rules, dim, ns, n, max_steps, auto_reset, scale=1, nf=None, seed=1, base=0, rec="full", epb=0,
+         store="auto", n_ops=60, seeds=(1, 2, 3)):
+    return dict(name=name, rules=sp.RULES[rules], dim=dim, n_snakes=ns, n_fruits=ns if nf is None else nf, num_envs=n,
+                max_steps=max_steps, auto_reset=bool(auto_reset), obs_scale=scale, seed=seed, env_id_base=base,
+                tuning=dict(record_policy=rec, envs_per_block=epb, obs_store_policy=store), n_ops=n_ops, seeds=tuple(seeds))
+
+
+# Between them (not as a cross product): the three rule sets; 1..3 snakes and 4 for new_world; boards 3x3 .. 19x19;
+# max_steps 5..12; auto reset on and off; obs_scale 1 and 4; a start on the full and on the short record; batches of
+# 1, 130, 257, 333, 777 envs; non-zero env_id_base and seeds with a non-zero high word; one batch above 8 192 envs with
+# the launch shape the library picks itself (short record, 4 envs per workgroup) and a short sequence.
+CONFIGS = [
+    _cfg("S3x2_n1", "snake_env", 3, 2, 1, 5, 1, seed=7, rec="full", epb=1),
+    _cfg("S3x2", "snake_env", 3, 2, 130, 6, 0, seed=11, base=5, rec="short", epb=8),
+    _cfg("S19x3_x4", "snake_env", 19, 3, 130, 12, 1, scale=4, seed=(3 << 32) | 17, base=1 << 33, rec="short", epb=4),
+    _cfg("S12x3", "snake_env", 12, 3, 200, 9, 0, seed=23, base=77, rec="full", epb=2),
+    _cfg("S10x1", "snake_env", 10, 1, 777, 8, 1, seed=5, rec="full", epb=8, store="stream"),
+    _cfg("A6x3", "adversarial", 6, 3, 333, 7, 0, seed=29, base=4096, rec="full", epb=4),
+    _cfg("A10x2", "adversarial", 10, 2, 130, 10, 1, seed=(9 << 32) | 2, rec="short", epb=1),
+    _cfg("A19x2_x4", "adversarial", 19, 2, 65, 12, 0, scale=4, seed=31, base=3, rec="short", epb=8, store="plain"),
+    _cfg("N6x4", "new_world", 6, 4, 130, 8, 1, nf=9, seed=37, rec="auto", epb=0),
+    _cfg("N10x2_x4", "new_world", 10, 2, 100, 10, 0, scale=4, nf=4, seed=(1 << 40) | 41, base=9, rec="auto", epb=2),
+    _cfg("N19x3", "new_world", 19, 3, 257, 12, 1, nf=3, seed=43, base=(1 << 32) + 6, rec="auto", epb=8),
+    _cfg("S19x3_big", "snake_env", 19, 3, 8201, 10, 1, seed=47, base=12, rec="auto", epb=0, n_ops=48, seeds=(1,)),
+]
+BY_NAME = {c["name"]: c for c in CONFIGS}
+
+
+def cases():
+    """(cfg, seed) of every run of the GPU file (and so of the host file)."""
+    return [(c, s) for c in CONFIGS for s in c["seeds"]]
+
+
+def effective_record(cfg, tuning):
+    """The record a handle of this tuning runs on (msnake_capi.hip: new_world always full; auto = short above 8 192)."""
+    if cfg["rules"] == 1:
+        return "full"
+    if tuning["record_policy"] == "auto":
+        return "short" if cfg["num_envs"] > 8192 else "full"
+    return tuning["record_policy"]
+
+
+def long_body_allowed(cfg):
+    return cfg["dim"] >= 10       # 100 cells: a body of 66..72 and room for the other snakes and the fruits
+
+
+def row_bytes(cfg):
+    views = cfg["n_snakes"] if cfg["rules"] == 1 else 3
+    return ((cfg["dim"] + 2) * cfg["obs_scale"]) ** 2 * 3 * views
+
+
+# ----------------------------------------------------------------------------------------------- the generator
+def _euler(rng):
+    """A closed walk over the five classes of state-changing ops that takes every ordered pair (A, B), A == B included,
+    exactly once: 26 nodes (Hierholzer on the complete digraph with loops, edge order shuffled)."""
+    out_edges = {a: [PAIR_CLASSES[j] for j in rng.permutation(5)] for a in PAIR_CLASSES}
+    stack, walk = [PAIR_CLASSES[int(rng.integers(0, 5))]], []
+    while stack:
+        v = stack[-1]
+        if out_edges[v]:
+            stack.append(out_edges[v].pop())
+        else:
+            walk.append(stack.pop())
+    walk.reverse()
+    assert len(walk) == 26
+    return walk
+
+
+class _Gen:
+    def __init__(self, cfg, rng):
+        self.cfg, self.rng = cfg, rng
+        self.tuning = dict(cfg["tuning"])
+        self.n_c = 0
+
+    def seed(self):
+        return int(self.rng.integers(0, 1 << 31))
+
+    def pick(self, seq, p=None):
+        return seq[int(self.rng.choice(len(seq), p=p))]
+
+    def stride(self):
+        ns = self.cfg["n_snakes"]
+        return ns if self.rng.random() < 0.5 else int(self.rng.integers(ns, 8))
+
+    def step(self):
+        return dict(kind="step", stride=self.stride(), obs=bool(self.rng.random() < 0.7), seed=self.seed())
+
+    def _obs_fits(self, T):
+        return T * self.cfg["num_envs"] * row_bytes(self.cfg) <= OBS_CAP
+
+    def step_tape(self):
+        T = int(self.rng.integers(1, 21))
+        obs = "all" if self._obs_fits(T) and self.rng.random() < 0.7 else "none"
+        return dict(kind="step_tape", n_steps=T, stride=self.stride(), obs=obs, seed=self.seed())
+
+    def rollout(self):
+        T = int(self.pick(ROLLOUT_STEPS))
+        inplace = bool(self.rng.random() < 0.3)
+        modes = ["last", "none"] if inplace or not self._obs_fits(T) else ["all", "all", "last", "none"]
+        return dict(kind="rollout", n_steps=T, stride=self.stride(), inplace=inplace, obs=self.pick(modes), seed=self.seed())
+
+    def reset_all(self):
+        return dict(kind="reset_all")
+
+    def reset_mask(self):
+        r = self.rng
+        return dict(kind="reset_mask", p_done=float(self.pick([0.0, 0.5, 1.0, 1.0])), p_mid=float(self.pick([0.0, 0.05, 0.3])),
+                    p_fin=float(self.pick([0.0, 0.5, 1.0, 1.0])), obs=bool(r.random() < 0.6), final=bool(r.random() < 0.6),
+                    trunc=bool(r.random() < 0.6), seed=self.seed())
+
+    def render(self):
+        return dict(kind="render")
+
+    def scripted(self):
+        ns, r = self.cfg["n_snakes"], self.rng
+        pols = ["safe_greedy", "safe_greedy", None] + (["hamiltonian", "hamiltonian"] if self.cfg["dim"] % 2 == 0 else [])
+        pol = self.pick(pols)
+        bits = 0 if pol is None else int(r.integers(1, 1 << ns))
+        return dict(kind="scripted", policy=pol, snakes=bits, stride=self.stride(),
+                    safe=bool(pol is None or r.random() < 0.6), seed=self.seed())
+
+    def checkpoint_self(self):
+        return dict(kind="checkpoint_self")
+
+    def set_words(self, edit=None):
+        if edit is None:
+            edit = self.pick(["ctr", "ctr", "none"])
+        return dict(kind="set_words", count=int(self.rng.integers(1, 9)), edit=edit, k=int(self.rng.integers(1, 13)),
+                    seed=self.seed())
+
+    def migrate(self):
+        cfg, old = self.cfg, self.tuning
+        new = dict(old)
+        if cfg["rules"] != 1:      # [N] has no short record: it migrates over envs_per_block (and the store policy) only
+            new["record_policy"] = "full" if effective_record(cfg, old) == "short" else "short"
+        new["envs_per_block"] = int(self.pick([e for e in (1, 2, 4, 8) if e != old["envs_per_block"]]))
+        new["obs_store_policy"] = self.pick(["auto", "plain", "stream"])
+        op = dict(kind="migrate", tuning=new, keep=bool(self.rng.random() < 0.3),
+                  direction=effective_record(cfg, old) + ">" + effective_record(cfg, new))
+        self.tuning = new
+        return op
+
+    def stats(self):
+        return dict(kind="stats", reset=bool(self.rng.random() < 0.4))
+
+    def of_class(self, c, n_step):
+        if c == "S":
+            return self.step() if n_step[0] < 3 or self.rng.random() < 0.5 else self.step_tape()
+        if c == "C":
+            self.n_c += 1
+            return self.checkpoint_self() if self.n_c % 2 else self.set_words()
+        return {"R": self.rollout, "K": self.reset_mask, "M": self.migrate}[c]()
+
+
+def gen_ops(cfg, seed, n_ops):
+    """The op list of (cfg, seed).  Built so that the coverage conditions of tests/test_op_fuzz_host.py hold by
+    construction where they can: a spine that takes every ordered pair of state-changing op classes (cut into segments
+    that re-enter on the node they left, so no pair is lost), a block `set_words(long body) -> migrate ->
+    checkpoint_self -> step` where the board allows a body over 64 cells, at least three ops of every kind, migrations
+    that flip the record policy every time -- and random ops (weights below) for the rest, in the gaps."""
+    rng = np.random.default_rng([0x6F70, int(seed), cfg["rules"], cfg["dim"], cfg["n_snakes"], cfg["num_envs"]])
+    g = _Gen(cfg, rng)
+    walk = _euler(rng)
+    cuts = sorted(int(x) for x in rng.choice(np.arange(3, 23), 2, replace=False))
+    segments = [walk[:cuts[0] + 1], walk[cuts[0]:cuts[1] + 1], walk[cuts[1]:]]
+    n_fixed = 1 + sum(len(s) for s in segments) + (4 if long_body_allowed(cfg) else 0)
+    quota = ["render"] * 3 + ["scripted"] * 3 + ["stats"] * 3 + ["reset_all"] * 2 + ["step_tape"] * 3 + ["set_words"]
+    weights = dict(step=5, step_tape=2, rollout=4, reset_all=1, reset_mask=3, render=1, scripted=3, checkpoint_self=2,
+                   set_words=2, migrate=2, stats=1)
+    if not cfg["auto_reset"]:     # finished envs step no further: reset them more often
+        weights["reset_mask"] = 7
+    names = list(weights)
+    p = np.array([weights[k] for k in names], float)
+    extra = quota + [names[int(i)] for i in rng.choice(len(names), max(0, n_ops - n_fixed - len(quota)), p=p / p.sum())]
+    extra = [extra[int(i)] for i in rng.permutation(len(extra))]
+    quiet = [k for k in extra if k in ("render", "scripted", "stats")]       # change no state: go anywhere
+    loud = [k for k in extra if k not in ("render", "scripted", "stats")]    # go into the gaps between segments
+    gaps = [[], [], []]
+    for k in loud:
+        gaps[int(rng.integers(0, 3))].append(k)
+    # the order the ops are MADE in is the order they run in (migrate tracks the tuning it leaves)
+    plan = []
+    for seg, gap in zip(segments, gaps):
+        plan += [("class", c) for c in seg] + [("kind", k) for k in gap]
+        if seg is segments[0] and long_body_allowed(cfg):
+            plan += [("long", None)]
+    for k in quiet:
+        plan.insert(int(rng.integers(0, len(plan) + 1)), ("kind", k))
+    ops, n_step = [dict(kind="reset_all", gen_seed=int(seed), cfg=cfg["name"])], [0]
+    for what, arg in plan:
+        if what == "class":
+            op = g.of_class(arg, n_step)
+            n_step[0] += op["kind"] == "step"
+            ops.append(op)
+        elif what == "long":
+            ops += [g.set_words(edit="long"), g.migrate(), g.checkpoint_self(), g.step()]
+        else:
+            ops.append(getattr(g, arg)())
+    return ops
+
+
+# ----------------------------------------------------------------------------------------------- shared pieces
+def up(frames, k):
+    """The fused WarpFrame: integer pixel replication of oracle frames [..., H, W, C] (always a copy)."""
+    return frames.copy() if k == 1 else np.repeat(np.repeat(frames, k, axis=-3), k, axis=-2)
+
+
+def guarded(payload):
+    """payload (any dtype / shape) -> the whole buffer as bytes: GUARD x SENT, payload, GUARD x SENT."""
+    g = np.full(GUARD, SENT, np.uint8)
+    return np.concatenate([g, np.ascontiguousarray(payload).reshape(-1).view(np.uint8), g])
+
+
+def make_actions(cfg, seed, shape):
+    """Seeded uniform actions 0..4 with ~2 % invalid codes, int32 of `shape` (.., num_envs, stride)."""
+    rs = np.random.default_rng([0xAC7, int(seed)])
+    a = rs.integers(0, 5, shape).astype(np.int32)
+    bad = rs.random(shape) < 0.02
+    a[bad] = np.array(INVALID_ACTIONS, np.int32)[rs.integers(0, 3, int(bad.sum()))]
+    return a
+
+
+def pack_blob(cfg, words):
+    """include/msnake.h's state blob (version 2) from one int32 word array per env."""
+    off = np.zeros(len(words) + 1, np.uint64)
+    off[1:] = np.cumsum([len(w) for w in words])
+    head = struct.pack("<IIiiiiiiQ", 0x5453534D, 2, len(words), cfg["dim"], cfg["n_snakes"], cfg["n_fruits"], cfg["rules"], 0,
+                       int(off[-1]))
+    return np.frombuffer(head + off.tobytes() + np.concatenate(words).astype(np.int32).tobytes(), np.uint8).copy()
+
+
+def unpack_blob(blob):
+    b = np.ascontiguousarray(blob, np.uint8).tobytes()
+    magic, version, n = struct.unpack_from("<IIi", b, 0)
+    assert magic == 0x5453534D and version == 2, (hex(magic), version)
+    total, = struct.unpack_from("<Q", b, 32)
+    off = np.frombuffer(b, np.uint64, n + 1, 40).astype(np.int64)
+    words = np.frombuffer(b, np.int32, int(total), 40 + 8 * (n + 1))
+    assert off[0] == 0 and off[-1] == total and len(b) == 40 + 8 * (n + 1) + 4 * total
+    return [words[off[e]:off[e + 1]] for e in range(n)]
+
+
+def make_oracle(cfg):
+    from oracle.snake_oracle import Oracle
+    return Oracle(cfg["num_envs"], dim=cfg["dim"], n_snakes=cfg["n_snakes"], n_fruits=cfg["n_fruits"], rules=cfg["rules"],
+                  seed=cfg["seed"], env_id_base=cfg["env_id_base"], max_steps=cfg["max_steps"], auto_reset=cfg["auto_reset"])
+
+
+class Totals:
+    """msnake_get_stats as a model: an episode counts on the step it ends and, while its env stays finished, only once."""
+
+    def __init__(self):
+        self.episodes = self.ep_len_sum = self.ep_return_sum = self.env_steps = 0
+
+    def count(self, done, fin, er, el):
+        new = (done != 0) & ~fin
+        self.episodes += int(new.sum())
+        self.ep_len_sum += int(el[new].astype(np.int64).sum())
+        self.ep_return_sum += int(er[new].astype(np.int64).sum())
+
+    def dict(self):
+        return {"episodes": self.episodes, "ep_len_sum": self.ep_len_sum, "ep_return_sum": self.ep_return_sum,
+                "env_steps": self.env_steps, "errors": 0}
+
+
+class Model:
+    """An Oracle behind the op interface: payloads as the library must write them (SENT where it must not write), the
+    finished bits and the episode totals -- all from the oracle's outputs alone."""
+
+    def __init__(self, cfg, hook=None):
+        self.cfg, self.n, self.ns = cfg, cfg["num_envs"], cfg["n_snakes"]
+        self.ora = make_oracle(cfg)
+        self.fin = np.zeros(self.n, bool)
+        self.totals = Totals()
+        self.threads = 8 if self.n >= 2000 else 1
+        self.hook = hook                      # called after every single step with (done,) -- coverage counting
+        self._buf = np.zeros(256, np.int32)
+        self.last_done = np.zeros(self.n, np.uint8)
+
+    def words(self, e):
+        L, h = self.ora.L, self.ora.h
+        k = L.orc_export_state(h, e, self._buf.ctypes.data, len(self._buf))
+        if k > len(self._buf):
+            self._buf = np.zeros(2 * k, np.int32)
+            k = L.orc_export_state(h, e, self._buf.ctypes.data, len(self._buf))
+        w = self._buf[:k].copy()
+        if L.orc_finished(h, e):
+            w[7] |= 0x100
+        return w
+
+    def install(self, e, words):
+        w = np.ascontiguousarray(words, np.int32)
+        rc = self.ora.L.orc_import_state(self.ora.h, e, w.ctypes.data, len(w))
+        assert rc == 0, rc
+        self.fin[e] = bool(w[7] & 0x100)
+
+    def state(self, e):
+        from oracle.snake_oracle import flat_to_state
+        return flat_to_state(self.words(e))
+
+    def reset_all(self):
+        obs = self.ora.reset()
+        self.fin[:] = False
+        return {"obs": up(obs, self.cfg["obs_scale"])}
+
+    def render(self):
+        return {"obs": up(self.ora.render(), self.cfg["obs_scale"])}
+
+    def step(self, act, want_obs=True):
+        obs, rew, done, ns, er, el = self.ora.step(act, threads=self.threads, want_obs=want_obs)
+        self.totals.count(done, self.fin, er, el)
+        self.totals.env_steps += self.n
+        if self.cfg["auto_reset"]:
+            self.fin[done != 0] = False
+        else:
+            self.fin[done != 0] = True
+        info = np.stack([er.view(np.int32), el, ns, done.astype(np.int32)], axis=1).astype(np.int32)
+        out = {"rew": rew.copy(), "done": done.copy(), "info": info}
+        if want_obs:
+            out["obs"] = up(obs, self.cfg["obs_scale"])
+        self.last_done = done.copy()
+        if self.hook:
+            self.hook(done)
+        return out
+
+    def tape(self, tape, obs_mode, inplace):
+        T = len(tape)
+        steps = [self.step(tape[t], obs_mode == "all" or (obs_mode == "last" and t == T - 1)) for t in range(T)]
+        out = {k: steps[-1][k] if inplace else np.stack([s[k] for s in steps]) for k in ("rew", "done", "info")}
+        if obs_mode == "all":
+            out["obs"] = np.stack([s["obs"] for s in steps])
+        elif obs_mode == "last":
+            out["obs"] = steps[-1]["obs"]
+        return out
+
+    def reset_mask(self, mask, want_obs, want_final, want_trunc):
+        shape = (self.n,) + self.ora.obs_shape
+        obs = np.full(shape, SENT, np.uint8) if want_obs else None
+        final = np.full(shape, SENT, np.uint8) if want_final else None
+        trunc = np.full(self.n, SENT, np.uint8) if want_trunc else None
+        self.ora.reset_envs(mask, obs=obs, final_obs=final, truncated=trunc)
+        self.fin[np.asarray(mask) != 0] = False
+        out = {}
+        if want_obs:
+            out["obs"] = up(obs, self.cfg["obs_scale"])
+        if want_final:
+            out["final"] = up(final, self.cfg["obs_scale"])
+        if want_trunc:
+            out["trunc"] = trunc
+        return out
+
+    def scripted(self, policy, bits, act, want_safe):
+        """scripted_play's policies (eps = 0) and the NumPy safe mask on the oracle's canonical states."""
+        dim, ns = self.cfg["dim"], self.ns
+        states = [self.state(e) for e in range(self.n)]
+        out = {}
+        if policy is not None:
+            pol = sp.POLICIES[policy]
+            want = np.array([pol(st, dim, ns, None, 0.0) for st in states], np.int32).reshape(self.n, ns)
+            act = act.copy()
+            for s in range(ns):
+                if bits >> s & 1:
+                    act[:, s] = want[:, s]
+            out["act"] = act
+        if want_safe:
+            out["safe"] = np.array([sp.np_safe_mask(st, dim, ns) for st in states], np.uint8).reshape(self.n, ns)
+        return out
+
+
+# ----------------------------------------------------------------------------------------------- adapters
+class OracleAdapter:
+    """The adapter interface over a second Oracle.  fault=(kind, min_op): one silent defect, applied to ONE env once, at
+    the first suitable op with index >= min_op (self.fault_at then holds that index):
+      "ctr_lag"      after a rollout, an env's draw counter is re-installed one lower
+      "fruit_moved"  after a migrate, a fruit of one env lies on another free cell
+      "fin_dropped"  a checkpoint_self drops the finished bit of one finished env
+      "double_count" one finished episode is counted twice in the totals"""
+
+    def __init__(self, fault=None):
+        self.fault, self.fault_at, self.op_index = fault, None, -1
+
+    def open(self, cfg):
+        self.cfg = cfg
+        self.m = Model(cfg)
+        self.kept = []
+
+    def _due(self, kind):
+        return self.fault and self.fault_at is None and self.fault[0] == kind and self.op_index >= self.fault[1]
+
+    def _wrap(self, out):
+        return {k: guarded(v) for k, v in out.items()}
+
+    def reset_all(self):
+        return self._wrap(self.m.reset_all())
+
+    def render(self):
+        return self._wrap(self.m.render())
+
+    def _after_steps(self, before):
+        if self._due("double_count") and self.m.totals.episodes > before:
+            self.m.totals.episodes += 1
+            self.fault_at = self.op_index
+
+    def step(self, act, want_obs):
+        before = self.m.totals.episodes
+        out = self._wrap(self.m.step(act, want_obs))
+        self._after_steps(before)
+        return out
+
+    def tape(self, tape, persistent, obs_mode, inplace):
+        before = self.m.totals.episodes
+        out = self._wrap(self.m.tape(tape, obs_mode, inplace))
+        self._after_steps(before)
+        if persistent and self._due("ctr_lag"):
+            e = self.cfg["num_envs"] // 2
+            w = self.m.words(e)
+            ctr = ((int(w[1]) & 0xFFFFFFFF) | (int(w[2]) & 0xFFFFFFFF) << 32) - 1
+            w[1], w[2] = np.array([ctr & 0xFFFFFFFF, ctr >> 32], np.uint32).view(np.int32)
+            self.m.install(e, w)
+            self.fault_at = self.op_index
+        return out
+
+    def reset_mask(self, mask, want_obs, want_final, want_trunc):
+        return self._wrap(self.m.reset_mask(mask, want_obs, want_final, want_trunc))
+
+    def scripted(self, policy, bits, act, want_safe):
+        return self._wrap(self.m.scripted(policy, bits, act, want_safe))
+
+    def get_words(self, e):
+        return self.m.words(e)
+
+    def set_words(self, e, words):
+        self.m.install(e, words)
+
+    def get_blob(self):
+        return pack_blob(self.cfg, [self.m.words(e) for e in range(self.cfg["num_envs"])])
+
+    def set_blob(self, blob, _migrating=False):
+        words = [w.copy() for w in unpack_blob(blob)]
+        if not _migrating and self._due("fin_dropped"):
+            fin = [e for e, w in enumerate(words) if w[7] & 0x100]
+            if fin:
+                words[fin[len(fin) // 2]][7] &= 0xFF
+                self.fault_at = self.op_index
+        for e, w in enumerate(words):
+            self.m.install(e, w)
+
+    def migrate(self, tuning, keep, blob):
+        if keep:
+            self.kept.append(self.m.totals.dict())
+        self.m = Model(self.cfg)
+        self.m.reset_all()
+        self.set_blob(blob, _migrating=True)
+        if self._due("fruit_moved"):
+            from oracle.snake_oracle import flat_to_state, state_to_flat
+            dim = self.cfg["dim"]
+            for e in range(self.cfg["num_envs"]):
+                w = self.m.words(e)
+                st = flat_to_state(w)
+                used = {tuple(c) for b in st["snakes"] for c in b} | {tuple(f) for f in st["fruits"]}
+                free = [(x, y) for x in range(dim) for y in range(dim) if (x, y) not in used]
+                if st["fruits"] and free:
+                    st["fruits"][0] = list(free[len(free) // 2])
+                    st["finished"] = bool(w[7] & 0x100)
+                    self.m.install(e, state_to_flat(st, self.cfg["n_snakes"]))
+                    self.fault_at = self.op_index
+                    break
+
+    def stats(self, reset):
+        out = self.m.totals.dict()
+        if reset:
+            self.m.totals = Totals()
+        return out
+
+    def kept_stats(self):
+        return list(self.kept)
+
+    def close(self):
+        self.m = None
+
+
+class HipAdapter:
+    """The library.  Handles come from msnake.MultiSnakeVecEnv; every stream-ordered call goes to the C entry point
+    directly (NULL outputs, strides and guarded raw buffers have no face on the Python class), on one stream of the
+    adapter's own that is current for everything it does."""
+
+    def __init__(self):
+        self.op_index = -1
+
+    def open(self, cfg):
+        import torch
+        self.torch, self.cfg = torch, cfg
+        self.stream = torch.cuda.Stream()
+        self.kept = []
+        self.env = self._make(cfg["tuning"])
+
+    def _make(self, tuning):
+        import msnake
+        c = self.cfg
+        with self.torch.cuda.stream(self.stream):
+            return msnake.MultiSnakeVecEnv(c["num_envs"], dim=c["dim"], n_snakes=c["n_snakes"], n_fruits=c["n_fruits"],
+                                           rules=c["rules"], seed=c["seed"], env_id_base=c["env_id_base"],
+                                           max_steps=c["max_steps"], auto_reset=c["auto_reset"], obs_scale=c["obs_scale"],
+                                           **tuning)
+
+    def _s(self):
+        return ctypes.c_void_p(self.stream.cuda_stream)
+
+    def _new(self, nbytes):
+        """A SENT-filled device buffer of nbytes + two guard bands; (tensor, pointer to the payload)."""
+        t = self.torch.full((int(nbytes) + 2 * GUARD,), SENT, dtype=self.torch.uint8, device=self.env.device)
+        return t, t.data_ptr() + GUARD
+
+    def _put(self, arr):
+        t = self.torch.from_numpy(guarded(arr)).to(self.env.device)
+        return t, t.data_ptr() + GUARD
+
+    def _call(self, name, *args):
+        from msnake import _capi
+        _capi.check(getattr(self.env._L, name)(self.env._h, *args), name)
+
+    def _back(self, bufs):
+        return {k: t.cpu().numpy() for k, (t, _) in bufs.items()}
+
+    def _obs_call(self, name):
+        with self.torch.cuda.stream(self.stream):
+            bufs = {"obs": self._new(self.cfg["num_envs"] * row_bytes(self.cfg))}
+            self._call(name, bufs["obs"][1], self._s())
+            return self._back(bufs)
+
+    def reset_all(self):
+        return self._obs_call("msnake_reset")
+
+    def render(self):
+        return self._obs_call("msnake_render")
+
+    def step(self, act, want_obs):
+        n = self.cfg["num_envs"]
+        with self.torch.cuda.stream(self.stream):
+            a = self._put(act)
+            bufs = {"rew": self._new(4 * n), "done": self._new(n), "info": self._new(16 * n)}
+            if want_obs:
+                bufs["obs"] = self._new(n * row_bytes(self.cfg))
+            self._call("msnake_step", a[1], int(act.shape[1]), bufs["obs"][1] if want_obs else None, bufs["rew"][1],
+                       bufs["done"][1], bufs["info"][1], self._s())
+            return self._back(bufs)
+
+    def tape(self, tape, persistent, obs_mode, inplace):
+        n, T = self.cfg["num_envs"], int(tape.shape[0])
+        rows = n * row_bytes(self.cfg)
+        k = 1 if inplace else T
+        with self.torch.cuda.stream(self.stream):
+            a = self._put(tape)
+            bufs = {"rew": self._new(4 * n * k), "done": self._new(n * k), "info": self._new(16 * n * k)}
+            if obs_mode != "none":
+                bufs["obs"] = self._new(rows * (T if obs_mode == "all" else 1))
+            self._call("msnake_rollout_tape" if persistent else "msnake_step_tape", a[1], int(tape.shape[2]), T,
+                       bufs["obs"][1] if obs_mode != "none" else None, rows if obs_mode == "all" else 0, bufs["rew"][1],
+                       bufs["done"][1], bufs["info"][1], 0 if inplace else n, self._s())
+            return self._back(bufs)
+
+    def reset_mask(self, mask, want_obs, want_final, want_trunc):
+        n = self.cfg["num_envs"]
+        with self.torch.cuda.stream(self.stream):
+            m = self._put(np.ascontiguousarray(mask, np.uint8))
+            bufs = {}
+            if want_obs:
+                bufs["obs"] = self._new(n * row_bytes(self.cfg))
+            if want_final:
+                bufs["final"] = self._new(n * row_bytes(self.cfg))
+            if want_trunc:
+                bufs["trunc"] = self._new(n)
+            ptr = lambda k: bufs[k][1] if k in bufs else None  # noqa: E731
+            self._call("msnake_reset_envs", m[1], ptr("obs"), ptr("final"), ptr("trunc"), self._s())
+            return self._back(bufs)
+
+    def scripted(self, policy, bits, act, want_safe):
+        from msnake import _capi
+        n, ns = self.cfg["num_envs"], self.cfg["n_snakes"]
+        with self.torch.cuda.stream(self.stream):
+            bufs = {}
+            if policy is not None:
+                bufs["act"] = self._put(act)
+            if want_safe:
+                bufs["safe"] = self._new(n * ns)
+            self._call("msnake_scripted_actions", _capi.SCRIPTED_POLICY[policy], bits,
+                       bufs["act"][1] if policy is not None else None, int(act.shape[1]) if policy is not None else 0,
+                       bufs["safe"][1] if want_safe else None, self._s())
+            return self._back(bufs)
+
+    def get_words(self, e):
+        return self.env.get_state_words(e)
+
+    def set_words(self, e, words):
+        self.env.set_state_words(e, words)
+
+    def get_blob(self):
+        return self.env.get_state_all()
+
+    def set_blob(self, blob):
+        self.env.set_state_all(blob)
+
+    def migrate(self, tuning, keep, blob):
+        if keep:
+            self.kept.append(self.env)
+        else:
+            self.env.close()
+        self.env = self._make(tuning)
+        with self.torch.cuda.stream(self.stream):
+            self.env.reset_device()        # a fresh handle is reset, then takes the blob (as a checkpoint restore does)
+        self.env.set_state_all(blob)
+
+    def stats(self, reset):
+        return self.env.stats(reset=reset)
+
+    def kept_stats(self):
+        return [e.stats() for e in self.kept]
+
+    def close(self):
+        self.stream.synchronize()
+        for e in self.kept + [self.env]:
+            e.close()
+        self.kept = []
+
+
+# ----------------------------------------------------------------------------------------------- the driver
+class Mismatch(AssertionError):
+    pass
+
+
+def new_cov():
+    return dict(kinds={k: 0 for k in KINDS}, migrate_dirs={}, pairs=set(), stepping=0, with_end=0, with_respawn=0,
+                rollout_cross16_end=0, wraps=0, long_migrate=0, long_checkpoint=0, fin_across=0, resets_of_finished=0,
+                episodes=0, env_steps=0)
+
+
+class _Driver:
+    def __init__(self, adapter, cfg, count):
+        self.a, self.cfg, self.count = adapter, cfg, count
+        self.n, self.ns = cfg["num_envs"], cfg["n_snakes"]
+        self.m = Model(cfg, hook=self._on_step if count else None)
+        self.cov = new_cov()
+        self.touched = []                 # envs set_words installed into (most recent last): always in the sample
+        self.pending = None               # actions a scripted op filled, for the next step
+        self.kept = []
+        self.gen_seed = None
+        self.prev_class = None
+        self.watch = list(range(min(self.n, 128)))   # envs whose draw counter / fruit count is read around every step (coverage)
+        self.seen_r = np.zeros(self.n, bool)
+        self.seen_c = np.zeros(self.n, bool)
+        self.ctr_of = {}
+
+    # ---- failure message
+    def fail(self, i, op, what, env=None, detail=""):
+        c = {k: v for k, v in self.cfg.items() if k not in ("n_ops", "seeds")}
+        raise Mismatch(f"op_fuzz: {what} differs at op {i} {op!r}; first differing env {env}; cfg {c}; seed {self.gen_seed}; "
+                       f"replay with run(adapter, cfg, gen_ops(cfg, seed, n_ops)[:{i + 1}]) {detail}")
+
+    def eq(self, i, op, got, want, per_env):
+        """got: name -> whole buffer (bytes) from the adapter; want: name -> payload from the model; per_env: name ->
+        bytes per env row (the first differing env is derived from it)."""
+        if set(got) != set(want):
+            self.fail(i, op, f"the set of outputs {sorted(got)} vs {sorted(want)}")
+        for k in sorted(want):
+            w = guarded(want[k])
+            g = np.asarray(got[k]).reshape(-1)
+            if g.shape != w.shape:
+                self.fail(i, op, f"size of {k} ({g.shape} vs {w.shape})")
+            if not np.array_equal(g, w):
+                at = int(np.flatnonzero(g != w)[0])
+                if at < GUARD or at >= len(w) - GUARD:
+                    self.fail(i, op, f"guard band of {k} (byte {at - GUARD} of the payload)")
+                row = (at - GUARD) // per_env[k]
+                self.fail(i, op, k, env=row % self.n, detail=f"(row {row}, byte {(at - GUARD) % per_env[k]}: got {int(g[at])}, "
+                          f"want {int(w[at])}; 0x{SENT:X} = untouched)")
+
+    def _sizes(self, stride=0):
+        rb = row_bytes(self.cfg)
+        return {"obs": rb, "final": rb, "trunc": 1, "rew": 4, "done": 1, "info": 16, "act": 4 * max(stride, 1), "safe": self.ns}
+
+    # ---- coverage hooks (count=True only; numbers of the oracle alone)
+    def _ctr(self, e):
+        w = self.m.words(e)
+        return (int(w[1]) & 0xFFFFFFFF) | (int(w[2]) & 0xFFFFFFFF) << 32
+
+    def _ctr_nf(self, e):
+        w = self.m.words(e)
+        return (int(w[1]), int(w[2]), int(w[6]))
+
+    def _on_step(self, done):
+        ctr = [self._ctr_nf(e) for e in self.watch]
+        if any(c != p and not done[e] for e, c, p in zip(self.watch, ctr, self._watch_ctr)):
+            self._respawn = True
+        self._watch_ctr = ctr
+        if done.any():
+            self._ended = True
+
+    def _begin_stepping(self):
+        self._respawn = self._ended = False
+        if self.count:
+            self._watch_ctr = [self._ctr_nf(e) for e in self.watch]
+
+    def _end_stepping(self, op):
+        cov = self.cov
+        cov["stepping"] += 1
+        cov["with_end"] += self._ended
+        cov["with_respawn"] += self._respawn
+        if op["kind"] == "rollout" and op["n_steps"] > 16 and self._ended:
+            cov["rollout_cross16_end"] += 1
+
+    # ---- ops
+    def op_reset_all(self, i, op):
+        self.eq(i, op, self.a.reset_all(), self.m.reset_all(), self._sizes())
+
+    def op_render(self, i, op):
+        self.eq(i, op, self.a.render(), self.m.render(), self._sizes())
+
+    def op_step(self, i, op):
+        if self.pending is not None:
+            act, self.pending = self.pending, None
+        else:
+            act = make_actions(self.cfg, op["seed"], (self.n, op["stride"]))
+        self._begin_stepping()
+        want = self.m.step(act, op["obs"])
+        self.eq(i, op, self.a.step(act, op["obs"]), want, self._sizes())
+        self._end_stepping(op)
+
+    def _tape(self, i, op, persistent):
+        tape = make_actions(self.cfg, op["seed"], (op["n_steps"], self.n, op["stride"]))
+        inplace = op.get("inplace", False)
+        fin_before = self.m.fin.copy()
+        self._begin_stepping()
+        want = self.m.tape(tape, op["obs"], inplace)
+        self.eq(i, op, self.a.tape(tape, persistent, op["obs"], inplace), want, self._sizes())
+        self._end_stepping(op)
+        if persistent:
+            self.seen_r |= fin_before & self.m.fin
+
+    def op_step_tape(self, i, op):
+        self._tape(i, op, False)
+
+    def op_rollout(self, i, op):
+        self._tape(i, op, True)
+
+    def op_reset_mask(self, i, op):
+        rs = np.random.default_rng([0x3A5C, op["seed"]])
+        fin = self.m.fin
+        mask = ((self.m.last_done != 0) & (rs.random(self.n) < op["p_done"])) | (~fin & (rs.random(self.n) < op["p_mid"])) | \
+               (fin & (rs.random(self.n) < op["p_fin"]))
+        mask = np.where(mask, np.array([1, 2, 0x80, 0xFF], np.uint8)[np.arange(self.n) % 4], 0).astype(np.uint8)
+        self.cov["resets_of_finished"] += int((fin & (mask != 0)).sum())
+        want = self.m.reset_mask(mask, op["obs"], op["final"], op["trunc"])
+        self.eq(i, op, self.a.reset_mask(mask, op["obs"], op["final"], op["trunc"]), want, self._sizes())
+
+    def op_scripted(self, i, op):
+        act = make_actions(self.cfg, op["seed"], (self.n, op["stride"]))
+        want = self.m.scripted(op["policy"], op["snakes"], act, op["safe"])
+        self.eq(i, op, self.a.scripted(op["policy"], op["snakes"], act, op["safe"]), want, self._sizes(op["stride"]))
+        if op["policy"] is not None:
+            self.pending = want["act"]
+
+    def _check_blob(self, i, op, blob):
+        words = unpack_blob(blob)
+        if len(words) != self.n:
+            self.fail(i, op, f"num_envs of the blob ({len(words)})")
+        for e in range(self.n):
+            if not np.array_equal(words[e], self.m.words(e)):
+                self._state_fail(i, op, e, words[e], "state blob")
+
+    def op_checkpoint_self(self, i, op):
+        blob = self.a.get_blob()
+        self._check_blob(i, op, blob)
+        self.a.set_blob(blob)
+        self._check_blob(i, op, self.a.get_blob())     # every env, finished bits included, as the restore left them
+        self.seen_c |= self.m.fin
+        self.cov["long_checkpoint"] += self._long_touched()
+
+    def op_migrate(self, i, op):
+        got = self.a.stats(False)
+        if got != self.m.totals.dict():
+            self.fail(i, op, f"stats() before the migration ({got} vs {self.m.totals.dict()})")
+        blob = self.a.get_blob()
+        self._check_blob(i, op, blob)
+        if op["keep"]:
+            self.kept.append(self.m.totals.dict())
+        self.a.migrate(op["tuning"], op["keep"], blob)
+        self._check_blob(i, op, self.a.get_blob())
+        self.m.totals = Totals()
+        d = op["direction"]
+        self.cov["migrate_dirs"][d] = self.cov["migrate_dirs"].get(d, 0) + 1
+        self.cov["long_migrate"] += self._long_touched()
+
+    def op_stats(self, i, op):
+        got, want = self.a.stats(op["reset"]), self.m.totals.dict()
+        if got != want:
+            self.fail(i, op, f"stats() ({got} vs the model {want})")
+        if op["reset"]:
+            self.cov["episodes"] += want["episodes"]
+            self.cov["env_steps"] += want["env_steps"]
+            self.m.totals = Totals()
+
+    def _long_touched(self):
+        return int(any(max(len(b) for b in self.m.state(e)["snakes"]) > 64 for e in self.touched[-16:]))
+
+    def _long_state(self, e, st, rs):
+        """The env's state with snake 0 laid along a boustrophedon path as a body of 66..72 cells, head last on the path."""
+        dim, ns = self.cfg["dim"], self.ns
+        L = int(rs.integers(66, 73))
+        path = []
+        for y in range(dim):
+            path += [(x, y) for x in (range(dim) if y % 2 == 0 else range(dim - 1, -1, -1))]
+        body = [list(c) for c in reversed(path[:L])]
+        free = path[L + 2:]
+        n_fr = min(len(st["fruits"]), len(free) - (ns - 1))
+        pick = [free[int(j)] for j in rs.choice(len(free), (ns - 1) + n_fr, replace=False)]
+        st = dict(st)
+        st["snakes"] = [body] + [[list(pick[s])] for s in range(ns - 1)]
+        st["vels"] = [[body[0][0] - body[1][0], body[0][1] - body[1][1]]] + [[1, 0]] * (ns - 1)
+        st["grow_to"] = [L + int(rs.integers(0, 3))] + [1] * (ns - 1)
+        st["alive"], st["in_dead"] = [True] * ns, [False] * ns
+        st["fruits"] = [list(pick[ns - 1 + f]) for f in range(n_fr)]
+        st["t"], st["ep_len"], st["ep_return"] = 1, 1, 0.0
+        return st
+
+    def op_set_words(self, i, op):
+        from oracle.snake_oracle import state_to_flat
+        rs = np.random.default_rng([0x5E7, op["seed"]])
+        envs = sorted(int(e) for e in rs.choice(self.n, min(self.n, op["count"]), replace=False))
+        for j, e in enumerate(envs):
+            got, want = self.a.get_words(e), self.m.words(e)
+            if not np.array_equal(got, want):
+                self._state_fail(i, op, e, got, "get_state before set_words")
+            edit = op["edit"] if j % 2 == 0 else "none"    # every other env: its own words go back in unchanged
+            if edit != "none":
+                st = self.m.state(e)
+                if edit == "ctr":
+                    st["ctr"] = (1 << 32) - (op["k"] + j)    # the wrap comes a few draws later
+                else:
+                    st = self._long_state(e, st, rs)
+                st["finished"] = bool(want[7] & 0x100) and edit == "ctr"
+                want = state_to_flat(st, self.ns)
+            self.m.install(e, want)
+            self.a.set_words(e, want)
+            self.ctr_of[e] = self._ctr(e)
+            if e in self.touched:
+                self.touched.remove(e)
+            self.touched.append(e)
+
+    # ---- state checks
+    def _state_fail(self, i, op, e, got, what):
+        from oracle.snake_oracle import flat_finished, flat_to_state
+        try:
+            g = (flat_to_state(got), flat_finished(got))
+        except Exception:  # noqa: BLE001
+            g = list(got)
+        self.fail(i, op, what, env=e, detail=f"got {g} want {(self.m.state(e), bool(self.m.fin[e]))}")
+
+    def check_states(self, i, op, every=False):
+        if every:
+            envs = range(self.n)
+        else:
+            rs = np.random.default_rng([0x57A7E, i])
+            envs = sorted(set(int(e) for e in rs.choice(self.n, min(self.n, 8), replace=False)) | set(self.touched[-16:]))
+        for e in envs:
+            want = self.m.words(e)
+            if bool(want[7] & 0x100) != bool(self.m.fin[e]):
+                self.fail(i, op, "the model's own finished bit (driver error)", env=e)
+            got = self.a.get_words(e)
+            if not np.array_equal(got, want):
+                self._state_fail(i, op, e, got, "canonical state / finished bit")
+        for e in list(self.ctr_of):        # 2^32 wraps of the counters set_words moved close to it
+            now = self._ctr(e)
+            if self.ctr_of[e] < (1 << 32) <= now:
+                self.cov["wraps"] += 1
+            self.ctr_of[e] = now
+
+    def play(self, ops):
+        self.gen_seed = ops[0].get("gen_seed") if ops else None
+        self.a.open(self.cfg)
+        i, op = -1, None
+        for i, op in enumerate(ops):
+            self.a.op_index = i
+            kind = op["kind"]
+            getattr(self, "op_" + kind)(i, op)
+            self.cov["kinds"][kind] += 1
+            cls = PAIR_CLASS.get(kind)
+            if cls:
+                if self.prev_class:
+                    self.cov["pairs"].add(self.prev_class + cls)
+                self.prev_class = cls
+            elif kind == "reset_all":
+                self.prev_class = None
+            self.seen_r &= self.m.fin
+            self.seen_c &= self.m.fin
+            self.cov["fin_across"] = max(self.cov["fin_across"], int((self.seen_r & self.seen_c).sum()))
+            self.check_states(i, op)
+        end = dict(kind="end of sequence")
+        self.a.op_index = len(ops)
+        self.check_states(len(ops), end, every=True)
+        got, want = self.a.stats(False), self.m.totals.dict()
+        if got != want:
+            self.fail(len(ops), end, f"stats() ({got} vs the model {want})")
+        self.cov["episodes"] += want["episodes"]
+        self.cov["env_steps"] += want["env_steps"]
+        got = self.a.kept_stats()
+        if got != self.kept:
+            self.fail(len(ops), end, f"stats() of the handles kept open after a migration ({got} vs {self.kept})")
+
+
+def run(adapter, cfg, ops, count=True):
+    """Drive `adapter` and an Oracle through `ops` side by side (ops[:k] of a generated list is as good as the list).
+    Raises Mismatch (an AssertionError) at the first difference; returns the coverage counters (count=False skips the
+    ones that cost per-step reads of the oracle)."""
+    d = _Driver(adapter, cfg, count)
+    try:
+        d.play(ops)
+    finally:
+        try:
+            adapter.close()
+        except Exception:  # noqa: BLE001  (a failed open leaves nothing to close)
+            pass
+    return d.cov

@@ -91,6 +91,25 @@ def safe_greedy(st, dim, n_snakes, rs, eps=0.0):
 POLICIES = {"hamiltonian": hamiltonian, "safe_greedy": safe_greedy}
 
 
+def np_safe_mask(st, dim, n_snakes):
+    """Bit a (1..4) of entry s: the target of move a of snake s lies on the board and in no body; 0 for an empty body."""
+    occ = np.zeros((dim, dim), bool)
+    for body in st["snakes"]:
+        for c0, c1 in body:
+            if 0 <= c0 < dim and 0 <= c1 < dim:
+                occ[c0, c1] = True
+    out = np.zeros(n_snakes, np.uint8)
+    for s in range(n_snakes):
+        body = st["snakes"][s] if s < len(st["snakes"]) else []
+        if not body:
+            continue
+        for a, (d0, d1) in DIRS.items():
+            x, y = body[0][0] + d0, body[0][1] + d1
+            if 0 <= x < dim and 0 <= y < dim and not occ[x, y]:
+                out[s] |= 1 << a
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- scenarios
 def scenario(rules, dim, n_snakes, policy, steps, num_envs, seed, n_fruits=None, eps=0.0, max_steps=2000,
              env_id_base=0, expect=()):

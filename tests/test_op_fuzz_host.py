@@ -1,0 +1,138 @@
+"""tests/op_fuzz.py on the CPU: the driver, its stats model and its guards against a second Oracle (the null test), the
+coverage the generated sequences reach (counted on the oracle alone, for every (configuration, seed) the GPU file runs),
+the four injected silent defects (each must be caught), and the generator's determinism."""
+import hashlib
+import re
+
+import pytest
+
+import op_fuzz as of
+
+CASES = of.cases()
+IDS = [f"{c['name']}-s{s}" for c, s in CASES]
+_COV = {}
+
+
+def _null(cfg, seed):
+    """run(OracleAdapter()) of one case, once per process; passing at all is the null test."""
+    key = (cfg["name"], seed)
+    if key not in _COV:
+        ops = of.gen_ops(cfg, seed, cfg["n_ops"])
+        _COV[key] = (of.run(of.OracleAdapter(), cfg, ops), ops)
+    return _COV[key]
+
+
+def _applicable(cfg):
+    return set(of.KINDS)     # every kind applies everywhere ([N] migrates over envs_per_block; odd boards script safe_greedy)
+
+
+@pytest.mark.parametrize("cfg,seed", CASES, ids=IDS)
+def test_null_run_and_coverage_of_every_case(cfg, seed):
+    cov, ops = _null(cfg, seed)
+    print(cfg["name"], seed, {k: (sorted(v) if isinstance(v, set) else v) for k, v in cov.items()})
+    assert len(ops) == cfg["n_ops"]
+    # 1. every op kind at least 3 times
+    assert all(cov["kinds"][k] >= 3 for k in _applicable(cfg)), cov["kinds"]
+    # 2. at least 2 migrations in each direction ([N] has no short record: envs_per_block only)
+    if cfg["rules"] != 1:
+        assert cov["migrate_dirs"].get("full>short", 0) >= 2 and cov["migrate_dirs"].get("short>full", 0) >= 2, cov["migrate_dirs"]
+    else:
+        assert cov["migrate_dirs"].get("full>full", 0) >= 3, cov["migrate_dirs"]
+    # 3. every ordered pair of state-changing op classes, consecutively (here: for every seed, not only over the seeds)
+    assert cov["pairs"] == {a + b for a in of.PAIR_CLASSES for b in of.PAIR_CLASSES}, sorted(cov["pairs"])
+    # 4. episode ends and respawns inside the stepping ops
+    assert cov["with_end"] >= 0.2 * cov["stepping"] and cov["with_respawn"] >= 0.2 * cov["stepping"], cov
+    # 5. a rollout across a 16-step boundary with an episode end inside
+    assert cov["rollout_cross16_end"] >= 1, cov
+
+
+@pytest.mark.parametrize("cfg", of.CONFIGS, ids=[c["name"] for c in of.CONFIGS])
+def test_coverage_over_the_seeds_of_a_configuration(cfg):
+    covs = [_null(cfg, s)[0] for s in cfg["seeds"]]
+    total = {k: sum(c[k] for c in covs) for k in ("wraps", "long_migrate", "long_checkpoint", "fin_across", "resets_of_finished")}
+    print(cfg["name"], total)
+    # 6. a 2^32 wrap of the draw counter (asked for per rule set; held per configuration)
+    assert total["wraps"] >= 1, total
+    # 7. a body over 64 cells survives a migration and a checkpoint_self, where the board has room for one
+    if of.long_body_allowed(cfg):
+        assert total["long_migrate"] >= 1 and total["long_checkpoint"] >= 1, total
+    # 8. without auto reset: an env stays finished across a rollout and a checkpoint_self before it is reset
+    if not cfg["auto_reset"]:
+        assert total["fin_across"] >= 1 and total["resets_of_finished"] >= 1, total
+
+
+def test_the_table_covers_what_it_is_there_for():
+    C = of.CONFIGS
+    assert {c["rules"] for c in C} == {0, 1, 2} and 10 <= len(C) <= 14
+    assert {c["n_snakes"] for c in C if c["rules"] != 1} == {1, 2, 3} and any(c["n_snakes"] == 4 for c in C if c["rules"] == 1)
+    assert min(c["dim"] for c in C) == 3 and max(c["dim"] for c in C) == 19
+    assert all(5 <= c["max_steps"] <= 12 for c in C) and {c["max_steps"] for c in C} >= {5, 12}
+    assert {c["obs_scale"] for c in C} == {1, 4}
+    for r in (0, 1, 2):
+        assert {c["auto_reset"] for c in C if c["rules"] == r} == {True, False}
+    for r in (0, 2):
+        assert {of.effective_record(c, c["tuning"]) for c in C if c["rules"] == r} == {"full", "short"}
+    big = [c for c in C if c["num_envs"] > 8192]
+    assert len(big) == 1 and big[0]["tuning"] == dict(record_policy="auto", envs_per_block=0, obs_store_policy="auto")
+    assert len(big[0]["seeds"]) == 1 and big[0]["n_ops"] < min(c["n_ops"] for c in C if c is not big[0])
+    assert {1, 130, 777} <= {c["num_envs"] for c in C} and any(c["num_envs"] % 4 for c in C)
+    assert any(c["env_id_base"] >> 32 for c in C) and any(c["seed"] >> 32 for c in C) and any(c["env_id_base"] == 0 for c in C)
+
+
+# ---------------------------------------------------------------------------------------------- sensitivity
+FAULTS = [("ctr_lag", "S12x3", 1, 15), ("fruit_moved", "A10x2", 2, 15), ("fin_dropped", "A6x3", 1, 15), ("double_count", "N6x4", 3, 15)]
+
+
+@pytest.mark.parametrize("kind,name,seed,after", FAULTS, ids=[f[0] for f in FAULTS])
+def test_an_injected_silent_defect_is_caught(kind, name, seed, after):
+    cfg = of.BY_NAME[name]
+    ops = of.gen_ops(cfg, seed, cfg["n_ops"])
+    bad = of.OracleAdapter(fault=(kind, after))
+    with pytest.raises(of.Mismatch) as err:
+        of.run(bad, cfg, ops)
+    msg = str(err.value)
+    assert bad.fault_at is not None and bad.fault_at >= after, "the defect was never injected"
+    at = int(re.search(r"differs at op (\d+)", msg).group(1))
+    assert bad.fault_at <= at <= len(ops), (bad.fault_at, at, msg)
+    assert cfg["name"] in msg and f"seed {seed}" in msg and "first differing env" in msg
+    # the replay the message names reproduces it; one op less does not reach it
+    if at < len(ops):
+        with pytest.raises(of.Mismatch):
+            of.run(of.OracleAdapter(fault=(kind, after)), cfg, ops[:at + 1])
+
+
+def test_a_guard_band_and_an_unselected_row_are_watched():
+    """The whole-buffer comparison itself: a byte in a guard band, and a row of an env a masked reset did not select."""
+    cfg = of.BY_NAME["S3x2"]
+    ops = of.gen_ops(cfg, 1, cfg["n_ops"])
+
+    class Scribbler(of.OracleAdapter):
+        def __init__(self, where):
+            super().__init__()
+            self.where = where
+
+        def reset_mask(self, mask, want_obs, want_final, want_trunc):
+            out = super().reset_mask(mask, want_obs, want_final, want_trunc)
+            if want_obs and self.where == "guard":
+                out["obs"][-1] = 0
+            if want_obs and self.where == "row" and (mask == 0).any():
+                e = int((mask == 0).argmax())
+                out["obs"][of.GUARD + e * of.row_bytes(cfg)] = 0
+            return out
+
+    with pytest.raises(of.Mismatch, match="guard band of obs"):
+        of.run(Scribbler("guard"), cfg, ops)
+    with pytest.raises(of.Mismatch, match="untouched"):
+        of.run(Scribbler("row"), cfg, ops)
+
+
+# ---------------------------------------------------------------------------------------------- determinism
+def test_the_generator_is_deterministic_and_pinned():
+    cfg = of.BY_NAME["A10x2"]
+    a, b = of.gen_ops(cfg, 2, cfg["n_ops"]), of.gen_ops(cfg, 2, cfg["n_ops"])
+    assert a == b and repr(a) == repr(b)
+    assert a != of.gen_ops(cfg, 3, cfg["n_ops"])
+    assert hashlib.sha256(repr(a).encode()).hexdigest() == PINNED
+
+
+PINNED = "fae5313f975b794a1b96991c2b08e565f283633b8dd327631e50953f24477c09"

@@ -2,7 +2,7 @@
 
 Everything is bit-exact and nothing is left out of a comparison: every step, env and snake.  The expected actions are
 scripted_play.POLICIES[...] with eps = 0 on the canonical state of the CPU oracle (or on a hand-built state dict); the
-expected mask is the NumPy statement in this file.  Neither ever comes from the library under test.
+expected mask is the NumPy statement scripted_play.np_safe_mask.  Neither ever comes from the library under test.
 """
 
 import numpy as np
@@ -16,23 +16,7 @@ GUARD = 64  # guard elements on each side of an output buffer
 
 
 # ------------------------------------------------------------------------------------------ expectations
-def np_safe_mask(st, dim, n_snakes):
-    """Bit a (1..4) of entry s: the target of move a of snake s lies on the board and in no body; 0 for an empty body."""
-    occ = np.zeros((dim, dim), bool)
-    for body in st["snakes"]:
-        for c0, c1 in body:
-            if 0 <= c0 < dim and 0 <= c1 < dim:
-                occ[c0, c1] = True
-    out = np.zeros(n_snakes, np.uint8)
-    for s in range(n_snakes):
-        body = st["snakes"][s] if s < len(st["snakes"]) else []
-        if not body:
-            continue
-        for a, (d0, d1) in sp.DIRS.items():
-            x, y = body[0][0] + d0, body[0][1] + d1
-            if 0 <= x < dim and 0 <= y < dim and not occ[x, y]:
-                out[s] |= 1 << a
-    return out
+np_safe_mask = sp.np_safe_mask   # the NumPy statement of the mask (shared with tests/op_fuzz.py)
 
 
 def expected(policy, states, dim, ns):
