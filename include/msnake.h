@@ -32,6 +32,9 @@
  *   msnake_scripted_actions: no reference counterpart (its opponents are always networks: evaluate_snake.py,
  *                      ppo_multi_agent.py:28-50 MultiModel.multi_step); a fixed, deterministic opponent and the
  *                      safe-move mask, computed on the device from the state the handle already owns.
+ *   msnake_copy_envs <- no reference counterpart (a reference env can only be re-created and replayed); the analogue is
+ *                      ALE's cloneState / restoreState, batched and on the device: snapshot, fork and restore of envs
+ *                      between two handles without the host round trip of msnake_get_state / msnake_set_state.
  *   msnake_get_stats <- the epinfobuf aggregation in ppo_multi_agent.py:288,331,366-390
  *
  * RNG contract (shared with oracle/ and tests/golden): draw i of global env g is word (i & 3) of
@@ -242,6 +245,31 @@ int msnake_render(msnake_handle h, uint8_t* obs_dev, void* stream);
 #define MSNAKE_POLICY_HAMILTONIAN 2
 int msnake_scripted_actions(msnake_handle h, int32_t policy, uint32_t snake_mask, int32_t* actions_dev,
                             int32_t action_stride, uint8_t* safe_dev, void* stream);
+
+/* Copy env state from `src` into `dst` on the device: destination env e receives the state of source env
+ * src_index_dev[e] (int32 [dst.num_envs], a device pointer).  A negative entry leaves destination env e completely
+ * untouched: no byte of its record, rings or lists is written.  NULL means the identity and needs equal env counts.
+ * An entry >= src.num_envs leaves env e untouched and adds 1 to that env's `errors` total (msnake_get_stats); nothing
+ * out of range is read.  The same holds for a body that does not fit the destination (possible only between new_world
+ * handles of different max_steps, whose body capacity follows the episode cap).
+ * What moves is exactly the canonical state the words above describe -- t, the 64-bit draw counter, spare_fruits,
+ * ep_len, ep_return, the fruit list, every snake's fields and cells, the new_world alive / in_dead bits, `finished`:
+ * afterwards msnake_get_state(dst, e) returns word for word what msnake_get_state(src, src_index[e]) returned before.
+ * What stays, as with msnake_set_state: the destination env's logging totals and the destination's configuration
+ * (num_envs, record_policy, envs_per_block, obs_scale, auto_reset, max_steps, seed and env_id_base may all differ
+ * between the two handles).  A destination env whose episode was in progress is abandoned: it is not counted in
+ * msnake_get_stats, as with msnake_reset.
+ * Random numbers: the Philox subsequence of an env is its slot's global id (env_id_base + index, see the RNG contract
+ * above) and is not part of the state.  A copy into the SAME global slot (equal seed and env_id_base, src_index[e] ==
+ * e: snapshot / restore) therefore continues bit-identically to the source; a copy into another slot starts from the
+ * same position and draws from its own slot's stream at the copied counter.  Draws that a full-record source has
+ * parked for later steps belong to the source slot's stream: they are never copied.
+ * `src` is only read.  The call allocates nothing, does not synchronise, draws no random numbers and adds nothing to
+ * env_steps: it can be captured into a HIP graph in front of a step.  Asynchronous on `stream`; the caller orders it
+ * against work on both handles.  MSNAKE_E_ARG, before any device work: dst == src (stage an in-place permutation
+ * through a second handle); dim, n_snakes, n_fruits or rules differ; the devices differ; src_index_dev NULL with
+ * different env counts. */
+int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_index_dev, void* stream);
 
 /* Copy the aggregate statistics to the host.  Blocking: waits for the device (every step issued so
  * far, on any stream) before it sums the per-env totals.  episodes / ep_len_sum / ep_return_sum /

@@ -19,7 +19,7 @@ SYMBOLS = [
     "msnake_reset", "msnake_reset_envs", "msnake_step", "msnake_step_tape", "msnake_rollout_tape", "msnake_get_state", "msnake_set_state",
     "msnake_get_state_all", "msnake_set_state_all", "msnake_state_blob_info",
     "msnake_render", "msnake_get_stats", "msnake_kernel_name", "msnake_algorithmic_bytes_per_env_step",
-    "msnake_scripted_actions",
+    "msnake_scripted_actions", "msnake_copy_envs",
 ]
 
 
@@ -83,6 +83,7 @@ def load():
     L.msnake_reset_envs.argtypes = [vp, u8p, u8p, u8p, u8p, vp]
     L.msnake_step.argtypes = [vp, vp, i32, u8p, vp, vp, vp, vp]
     L.msnake_scripted_actions.argtypes = [vp, i32, ctypes.c_uint32, vp, i32, u8p, vp]
+    L.msnake_copy_envs.argtypes = [vp, vp, vp, vp]  # dst, src, src_index_dev (int32 [dst.num_envs] or NULL), stream
     L.msnake_step_tape.argtypes = [vp, vp, i32, i32, u8p, ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, vp]
     L.msnake_rollout_tape.argtypes = L.msnake_step_tape.argtypes
     L.msnake_get_state.argtypes = [vp, i32, vp, i32]
@@ -98,7 +99,7 @@ def load():
     L.msnake_algorithmic_bytes_per_env_step.restype = ctypes.c_int64
     for name in ("msnake_create", "msnake_destroy", "msnake_obs_shape", "msnake_reset", "msnake_reset_envs", "msnake_render",
                  "msnake_step", "msnake_step_tape", "msnake_rollout_tape", "msnake_get_state", "msnake_set_state", "msnake_set_state_all",
-                 "msnake_state_blob_info", "msnake_get_stats", "msnake_scripted_actions"):
+                 "msnake_state_blob_info", "msnake_get_stats", "msnake_scripted_actions", "msnake_copy_envs"):
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L

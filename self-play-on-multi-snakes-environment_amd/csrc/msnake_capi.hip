@@ -418,6 +418,31 @@ int msnake_scripted_actions(msnake_handle h, int32_t policy, uint32_t snake_mask
     return MSNAKE_OK;
 }
 
+int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_index_dev, void* stream) {
+    if (int rc = check(dst)) return rc;
+    if (int rc = check(src)) return rc;
+    if (dst == src)
+        return fail(MSNAKE_E_ARG, "msnake_copy_envs: src is the same handle as dst (copies within one handle are staged "
+                                  "through a second handle)");
+    const msnake_config &d = dst->cfg, &s = src->cfg;
+    if (s.dim != d.dim) return fail(MSNAKE_E_ARG, "msnake_copy_envs: src has dim %d, dst has dim %d", s.dim, d.dim);
+    if (s.n_snakes != d.n_snakes)
+        return fail(MSNAKE_E_ARG, "msnake_copy_envs: src has n_snakes %d, dst has n_snakes %d", s.n_snakes, d.n_snakes);
+    if (s.n_fruits != d.n_fruits)
+        return fail(MSNAKE_E_ARG, "msnake_copy_envs: src has n_fruits %d, dst has n_fruits %d", s.n_fruits, d.n_fruits);
+    if (s.rules != d.rules) return fail(MSNAKE_E_ARG, "msnake_copy_envs: src has rules %d, dst has rules %d", s.rules, d.rules);
+    if (s.device != d.device)
+        return fail(MSNAKE_E_ARG, "msnake_copy_envs: src lives on device %d, dst on device %d", s.device, d.device);
+    if (!src_index_dev && s.num_envs != d.num_envs)
+        return fail(MSNAKE_E_ARG, "msnake_copy_envs: src_index_dev is NULL (the identity) but src has num_envs %d and dst has "
+                                  "num_envs %d", s.num_envs, d.num_envs);
+    if ((uintptr_t)src_index_dev & 3) return fail(MSNAKE_E_ALIGN, "src_index_dev must be 4-byte aligned");
+    DeviceGuard guard(d.device);
+    hipError_t e = msnake::launch_copy_envs(dst->p, src->p, d.rules, src_index_dev, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return MSNAKE_OK;
+}
+
 // ---- canonical state import / export.  The device packs / unpacks (msnake_state_*_kernel); the host
 //      only sizes buffers and copies.  Blocking: every call starts with a device synchronise. ----
 namespace {

@@ -128,6 +128,8 @@ hipError_t launch_state_unpack(const StepParams& p, int rules, int env0, int cou
 // scripted opponents / safe-move masks from the state in HBM (msnake_scripted.inc); reads the handle's state only
 hipError_t launch_scripted(const StepParams& p, int rules, int policy, uint32_t snake_mask, int32_t* actions, int32_t action_stride,
                            uint8_t* safe, hipStream_t stream);
+// env state of `src` into `dst`, one wave per destination env (msnake_copy.inc); src_index NULL = the identity.  Reads `src` only
+hipError_t launch_copy_envs(const StepParams& dst, const StepParams& src, int rules, const int32_t* src_index, hipStream_t stream);
 void step_kernel_name(int rules, int n_snakes, int obs_scale, char* out, size_t n);
 
 }  // namespace msnake

@@ -1959,3 +1959,4 @@ void step_kernel_name(int rules, int n_snakes, int obs_scale, char* out, size_t 
 }  // namespace msnake
 
 #include "msnake_scripted.inc"  // msnake_scripted_actions: scripted opponents and safe-move masks (off the step path)
+#include "msnake_copy.inc"      // msnake_copy_envs: env state copied between two handles on the device (off the step path)

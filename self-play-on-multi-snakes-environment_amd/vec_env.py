@@ -67,6 +67,31 @@ def normalize_mask(mask, num_envs):
     return m
 
 
+def normalize_copy_index(index, num_envs):
+    """Source index of a device-side env copy -> contiguous int32 [num_envs] (entry e: the source env whose state
+    destination env e receives; negative = leave env e as it is).
+
+    Takes a sequence or an integer ndarray of shape [num_envs].  Entries past the int32 range become -1 / 2**31 - 1,
+    i.e. stay "untouched" / "out of range"; the range check against the source is the library's.  Device tensors are
+    handled by the env itself."""
+    idx = np.asarray(index)
+    if idx.ndim != 1 or idx.shape[0] != num_envs:
+        raise ValueError(f"index must have shape ({num_envs},), got {idx.shape}")
+    if not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError(f"index must be of an integer dtype, got {idx.dtype}")
+    lo, hi = idx < 0, idx > 2**31 - 1
+    out = np.empty(num_envs, np.int32)
+    out[lo], out[hi] = -1, 2**31 - 1
+    keep = ~(lo | hi)
+    out[keep] = idx[keep]
+    return out
+
+
+# constructor arguments that may differ between the two handles of a device-side copy (include/msnake.h,
+# msnake_copy_envs): what MultiSnakeVecEnv.clone() lets a caller override
+CLONE_OVERRIDES = ("record_policy", "envs_per_block", "obs_scale", "auto_reset", "max_steps", "seed", "env_id_base")
+
+
 class LazyInfos:
     """Sequence of per-env info dicts, materialised on access.
 
@@ -144,6 +169,12 @@ class MultiSnakeVecEnv:
             raise ValueError("terminal_obs=True needs auto_reset=True (it replaces the in-kernel auto reset)")
         if n_fruits is None:
             n_fruits = n_snakes
+        # what clone() needs to build the same env again
+        self._ctor = dict(dim=dim, n_snakes=n_snakes, n_fruits=n_fruits, rules=rules, seed=seed, env_id_base=env_id_base,
+                          device=self.device, max_steps=max_steps, auto_reset=auto_reset, obs_scale=obs_scale,
+                          declared_channels=declared_channels, host_views=host_views, envs_per_block=envs_per_block,
+                          record_policy=record_policy, obs_store_policy=obs_store_policy,
+                          tape_store_policy=tape_store_policy, terminal_obs=terminal_obs)
         self.cfg = _capi.MsnakeConfig(ctypes.sizeof(_capi.MsnakeConfig), self.device.index or 0, int(num_envs),
                                       int(dim), int(n_snakes), int(n_fruits), rules_id, int(max_steps),
                                       int(bool(auto_reset) and not self.terminal_obs), int(obs_scale), int(seed),
@@ -356,6 +387,51 @@ class MultiSnakeVecEnv:
                        rew.data_ptr(), done.data_ptr(), info.data_ptr(), n, self._stream()),
                     "msnake_rollout_tape" if persistent else "msnake_step_tape")
         return obs, rew, done, info
+
+    def copy_envs_device(self, src, index=None):
+        """Overwrite envs of this env with the state of envs of `src`, another MultiSnakeVecEnv with the same dim,
+        n_snakes, n_fruits and rules on the same device (msnake_copy_envs: one launch, no host round trip).  `index`:
+        entry e names the env of `src` that env e receives, negative = env e stays as it is; an int32 / int64 tensor
+        on this device, or a sequence / ndarray, which is uploaded; None = the identity (equal num_envs).  The envs'
+        logging totals stay.  An env copied into the same global slot (equal seed and env_id_base, index[e] == e)
+        continues bit-identically to its source; any other draws from its own slot's random stream at the copied
+        counter.  Nothing is synchronised: the caller orders the call against work on both envs."""
+        torch = self._torch
+        if not isinstance(src, MultiSnakeVecEnv):
+            raise TypeError(f"src must be a MultiSnakeVecEnv, got {type(src).__name__}")
+        if self._pending is not None or src._pending is not None:
+            raise RuntimeError("copy_envs_device() between step_async() and step_wait(): the pending step's results would "
+                               "no longer belong to the state")
+        if index is None:
+            p_idx = None
+        elif isinstance(index, torch.Tensor):
+            if index.dtype not in (torch.int32, torch.int64) or tuple(index.shape) != (self.num_envs,):
+                raise ValueError(f"an index tensor must be int32 or int64 of shape ({self.num_envs},), got {index.dtype} "
+                                 f"{tuple(index.shape)}")
+            if index.dtype == torch.int64:
+                index = index.clamp(-1, 2**31 - 1)
+            index = index.to(device=self.device, dtype=torch.int32).contiguous()
+            p_idx = index.data_ptr()
+        else:
+            index = torch.from_numpy(normalize_copy_index(index, self.num_envs)).to(self.device)
+            p_idx = index.data_ptr()
+        rc = self._L.msnake_copy_envs(self._h, src._h, p_idx, self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_copy_envs")
+
+    def clone(self, num_envs=None, **overrides):
+        """A new MultiSnakeVecEnv with this env's configuration; `overrides` may change what a device-side copy lets
+        differ (CLONE_OVERRIDES).  With the same number of envs (the default) it starts as a copy of this env's state
+        (copy_envs_device with the identity) -- a snapshot to roll back to when seed and env_id_base are kept;
+        with another num_envs its envs are unset until reset_device() or copy_envs_device(self, index)."""
+        bad = sorted(set(overrides) - set(CLONE_OVERRIDES))
+        if bad:
+            raise ValueError(f"clone() can override {', '.join(CLONE_OVERRIDES)}; got {', '.join(bad)}")
+        n = self.num_envs if num_envs is None else int(num_envs)
+        new = MultiSnakeVecEnv(n, **dict(self._ctor, **overrides))
+        if n == self.num_envs:
+            new.copy_envs_device(self)
+        return new
 
     def render_device(self, out=None):
         obs = self._out(out)
