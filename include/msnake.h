@@ -277,9 +277,24 @@ int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_in
  * of a captured HIP graph are not included in it. */
 int msnake_get_stats(msnake_handle h, msnake_stats* out, int32_t reset);
 
-/* Name of the step kernel (for profilers; the string is owned by the handle and lives until
- * msnake_destroy) and algorithmic HBM bytes per env-step. */
+/* Name of the step kernel that msnake_step launches of this handle run with action_stride == n_snakes (for
+ * profilers; the string is owned by the handle and lives until msnake_destroy) and algorithmic HBM bytes per
+ * env-step.  Handles of the shapes 19x19 with 2 or 3 snakes and 10x10 with one snake (snake_env rules,
+ * obs_scale 1, auto reset, the full record) run kernels compiled for that shape, named with a fifth template
+ * argument, the board size; a call whose action_stride differs runs the generic kernel for that call, with the same
+ * results. */
 const char* msnake_kernel_name(msnake_handle h);
+/* The same name for a configuration, decided on the host exactly as msnake_create decides it, without a handle and
+ * without touching a GPU (tests, tools).  Writes at most n bytes, NUL-terminated; MSNAKE_E_ARG for a configuration
+ * msnake_create would refuse. */
+int msnake_kernel_name_for_config(const msnake_config* cfg, char* out, size_t n);
+/* Process-wide switch for same-box A/B runs and tests: while it is on, msnake_create (and the call above) choose the
+ * generic kernels for every configuration; handles that exist keep what they were created with.  Returns the previous
+ * setting.  The library itself reads no environment variable: the Python binding turns the switch on for handles
+ * created while MSNAKE_GENERIC_KERNELS=1 is in the environment.  Not for concurrent use: the switch is one
+ * process-wide value, so a thread that flips it while another thread is inside msnake_create (or the call above)
+ * decides which kernels that handle gets; callers that create handles from several threads set it once, before. */
+int msnake_set_generic_kernels(int32_t on);
 int64_t msnake_algorithmic_bytes_per_env_step(msnake_handle h);
 
 #ifdef __cplusplus

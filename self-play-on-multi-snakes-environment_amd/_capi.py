@@ -19,7 +19,8 @@ SYMBOLS = [
     "msnake_reset", "msnake_reset_envs", "msnake_step", "msnake_step_tape", "msnake_rollout_tape", "msnake_get_state", "msnake_set_state",
     "msnake_get_state_all", "msnake_set_state_all", "msnake_state_blob_info",
     "msnake_render", "msnake_get_stats", "msnake_kernel_name", "msnake_algorithmic_bytes_per_env_step",
-    "msnake_scripted_actions", "msnake_copy_envs",
+    "msnake_scripted_actions", "msnake_copy_envs", "msnake_kernel_name_for_config",
+    "msnake_set_generic_kernels",
 ]
 
 
@@ -95,6 +96,10 @@ def load():
     L.msnake_get_stats.argtypes = [vp, ctypes.POINTER(MsnakeStats), i32]
     L.msnake_kernel_name.argtypes = [vp]
     L.msnake_kernel_name.restype = ctypes.c_char_p
+    L.msnake_kernel_name_for_config.argtypes = [ctypes.POINTER(MsnakeConfig), ctypes.c_char_p, ctypes.c_size_t]
+    L.msnake_kernel_name_for_config.restype = ctypes.c_int
+    L.msnake_set_generic_kernels.argtypes = [i32]
+    L.msnake_set_generic_kernels.restype = ctypes.c_int
     L.msnake_algorithmic_bytes_per_env_step.argtypes = [vp]
     L.msnake_algorithmic_bytes_per_env_step.restype = ctypes.c_int64
     for name in ("msnake_create", "msnake_destroy", "msnake_obs_shape", "msnake_reset", "msnake_reset_envs", "msnake_render",
@@ -103,6 +108,22 @@ def load():
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L
+
+
+def apply_kernel_switch():
+    """MSNAKE_GENERIC_KERNELS=1 in the environment (anything but empty or "0") at the time a handle is created keeps that
+    handle on the generic step kernels instead of the ones compiled for its shape: same-box A/B runs and tests.  Called
+    right before msnake_create / msnake_kernel_name_for_config; the library itself reads no environment variable."""
+    load().msnake_set_generic_kernels(int(os.environ.get("MSNAKE_GENERIC_KERNELS", "") not in ("", "0")))
+
+
+def kernel_name_for_config(cfg):
+    """The step kernel a handle created from `cfg` (a MsnakeConfig) right now would report, decided by the library's
+    host glue without a GPU."""
+    apply_kernel_switch()
+    buf = ctypes.create_string_buffer(64)
+    check(load().msnake_kernel_name_for_config(ctypes.byref(cfg), buf, len(buf)), "msnake_kernel_name_for_config")
+    return buf.value.decode()
 
 
 def check(rc, what="msnake call"):

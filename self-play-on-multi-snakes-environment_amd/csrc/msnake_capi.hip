@@ -5,6 +5,7 @@
 // MSNAKE_E_HIP.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -99,18 +100,18 @@ extern "C" {
 int msnake_abi_version(void) { return MSNAKE_ABI_VERSION; }
 const char* msnake_last_error(void) { return g_err; }
 
-int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
-    if (!cfg_in || !out) return fail(MSNAKE_E_ARG, "msnake_create: NULL argument");
-    *out = nullptr;
+namespace {
+
+// argument checks of msnake_create (no GPU involved); *cfg_full <- the configuration widened to the current struct
+int validate_config(const msnake_config* cfg_in, msnake_config* cfg_full) {
     // ABI 3 appended the launch-tuning fields; an ABI-2 caller passes the 56-byte prefix and gets "auto"
     if (cfg_in->struct_size != sizeof(msnake_config) && cfg_in->struct_size != MSNAKE_CONFIG_SIZE_V2)
         return fail(MSNAKE_E_ARG, "msnake_config.struct_size %u is neither %zu (ABI 3) nor %u (ABI 2)", cfg_in->struct_size,
                     sizeof(msnake_config), MSNAKE_CONFIG_SIZE_V2);
-    msnake_config cfg_full;
-    memset(&cfg_full, 0, sizeof(cfg_full));
-    memcpy(&cfg_full, cfg_in, cfg_in->struct_size);
-    cfg_full.struct_size = (uint32_t)sizeof(msnake_config);
-    const msnake_config* cfg = &cfg_full;
+    memset(cfg_full, 0, sizeof(*cfg_full));
+    memcpy(cfg_full, cfg_in, cfg_in->struct_size);
+    cfg_full->struct_size = (uint32_t)sizeof(msnake_config);
+    const msnake_config* cfg = cfg_full;
     if (cfg->num_envs < 1) return fail(MSNAKE_E_ARG, "num_envs must be >= 1 (got %d)", cfg->num_envs);
     if (cfg->dim < 2 || cfg->dim > MSNAKE_MAX_DIM)
         return fail(MSNAKE_E_ARG, "dim must be in [2, %d] (got %d)", MSNAKE_MAX_DIM, cfg->dim);
@@ -144,18 +145,12 @@ int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
     if (cfg->obs_store_policy < 0 || cfg->obs_store_policy > MSNAKE_STORE_STREAM || cfg->tape_store_policy < 0 ||
         cfg->tape_store_policy > MSNAKE_STORE_STREAM)
         return fail(MSNAKE_E_ARG, "obs_store_policy / tape_store_policy must be MSNAKE_AUTO, MSNAKE_STORE_PLAIN or MSNAKE_STORE_STREAM");
+    return MSNAKE_OK;
+}
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(MSNAKE_E_NOGPU, "no HIP device available (this library has no CPU path)");
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(MSNAKE_E_ARG, "device %d out of range (have %d)", cfg->device, ndev);
-    DeviceGuard guard(cfg->device);
-
-    msnake_env* h = static_cast<msnake_env*>(calloc(1, sizeof(msnake_env)));
-    if (!h) return fail(MSNAKE_E_ARG, "out of host memory");
-    h->cfg = *cfg;
-    msnake::StepParams& p = h->p;
+// Everything of StepParams that follows from the configuration alone: the shape of the observation, of the state and of
+// the LDS image, and the record policy.  No GPU involved (msnake_kernel_name_for_config runs it without one).
+int derive_shape(const msnake_config* cfg, msnake::StepParams& p) {
     const int dim = cfg->dim, W = dim + 2, n2 = dim * dim;
     p.nenv = cfg->num_envs;
     p.dim = dim;
@@ -173,24 +168,64 @@ int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
     if (cfg->rules == MSNAKE_RULES_NEW_WORLD && cfg->max_steps + 2 > need) need = cfg->max_steps + 2;
     p.rest.cap = (need + 63) / 64 * 64;
     const int K = cfg->obs_scale;
-    if (K > 1 && (W * K * p.C) % 4 != 0) {
-        free(h);
-        return fail(MSNAKE_E_ARG, "obs_scale %d: output rows must be whole dwords", K);
-    }
+    if (K > 1 && (W * K * p.C) % 4 != 0) return fail(MSNAKE_E_ARG, "obs_scale %d: output rows must be whole dwords", K);
     p.img_bytes = (p.S * K + (K == 1 ? 15 : 0) + 1023) / 1024 * 1024;  // K-fold wide image, whole 1 KiB wave-instructions
+    p.lds_per_wave = p.img_bytes + (n2 + 15) / 16 * 16;  // composed image + respawn occupancy
+    if ((size_t)p.lds_per_wave > 64 * 1024 - 16 || p.S > 0xFFFF)
+        return fail(MSNAKE_E_ARG, "observation image of %d bytes does not fit in LDS", p.S);
+    // record_policy: snake_env / adversarial steps can run on the first 128 bytes of the 256-byte
+    // record; the upper half only parks Philox draws for the waves that respawn or reset, which pays
+    // while a launch is latency bound (<= 8 192 envs) and is pure traffic above (see DESIGN.md)
+    p.short_rec = (cfg->rules != MSNAKE_RULES_NEW_WORLD && p.nenv > 8192) ? 1 : 0;
+    if (cfg->record_policy != MSNAKE_AUTO)  // (new_world keeps its fruits in the upper half: always the full record)
+        p.short_rec = (cfg->rules != MSNAKE_RULES_NEW_WORLD && cfg->record_policy == MSNAKE_RECORD_SHORT) ? 1 : 0;
+    return MSNAKE_OK;
+}
+
+// msnake_set_generic_kernels: handles created while it is on stay on the generic kernels (A/B runs, tests)
+std::atomic<int> g_generic_kernels{0};
+
+// The compile-time shape the handle's step / tape launches use (0 = the generic kernels): decided once, from the
+// derived configuration.
+int pick_spec_dim(const msnake::StepParams& p, int rules) {
+    if (g_generic_kernels.load(std::memory_order_relaxed)) return 0;
+    return msnake::spec_dim_of(p, rules);
+}
+
+}  // namespace
+
+int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
+    if (!cfg_in || !out) return fail(MSNAKE_E_ARG, "msnake_create: NULL argument");
+    *out = nullptr;
+    msnake_config cfg_full;
+    if (int rc = validate_config(cfg_in, &cfg_full)) return rc;
+    const msnake_config* cfg = &cfg_full;
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(MSNAKE_E_NOGPU, "no HIP device available (this library has no CPU path)");
+    if (cfg->device < 0 || cfg->device >= ndev)
+        return fail(MSNAKE_E_ARG, "device %d out of range (have %d)", cfg->device, ndev);
+    DeviceGuard guard(cfg->device);
+
+    msnake_env* h = static_cast<msnake_env*>(calloc(1, sizeof(msnake_env)));
+    if (!h) return fail(MSNAKE_E_ARG, "out of host memory");
+    h->cfg = *cfg;
+    msnake::StepParams& p = h->p;
+    if (int rc = derive_shape(cfg, p)) {
+        free(h);
+        return rc;
+    }
+    const int dim = cfg->dim, W = dim + 2, n2 = dim * dim;
+    const int K = cfg->obs_scale;
     p.rest.seed_lo = (uint32_t)cfg->seed;
     p.rest.seed_hi = (uint32_t)(cfg->seed >> 32);
     p.rest.env_id_base = cfg->env_id_base;
-    p.lds_per_wave = p.img_bytes + (n2 + 15) / 16 * 16;  // composed image + respawn occupancy
     // envs (= waves) per workgroup: 8 up to 8 192 envs (512 workgroups at 4 096 envs start 3 % sooner
     // than 1 024: 7.63 -> 7.40 us per launch), 4 above (an 8-wave workgroup needs 8 free wave slots on
     // one CU at once: 29.5 vs 30.9 us at 32 768 envs)
     h->epb = p.nenv <= 8192 ? MSNAKE_MAX_ENVS_PER_BLOCK : 4;
     while (h->epb > 1 && (size_t)h->epb * p.lds_per_wave > 64 * 1024) h->epb >>= 1;
-    if ((size_t)p.lds_per_wave > 64 * 1024 - 16 || p.S > 0xFFFF) {
-        free(h);
-        return fail(MSNAKE_E_ARG, "observation image of %d bytes does not fit in LDS", p.S);
-    }
 
     const size_t hdr_bytes = (size_t)p.nenv * MSNAKE_HDR_WORDS * 4;
     const size_t body0_bytes = (size_t)p.nenv * p.n_snakes * 64 * 2;
@@ -230,12 +265,6 @@ int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
         return fail(MSNAKE_E_HIP, "uploading the background image failed: %s", hipGetErrorString(e));
     }
     if (cfg->envs_per_block > 0 && cfg->envs_per_block < h->epb) h->epb = cfg->envs_per_block;  // (never above what LDS allows)
-    // record_policy: snake_env / adversarial steps can run on the first 128 bytes of the 256-byte
-    // record; the upper half only parks Philox draws for the waves that respawn or reset, which pays
-    // while a launch is latency bound (<= 8 192 envs) and is pure traffic above (see DESIGN.md)
-    p.short_rec = (cfg->rules != MSNAKE_RULES_NEW_WORLD && p.nenv > 8192) ? 1 : 0;
-    if (cfg->record_policy != MSNAKE_AUTO)  // (new_world keeps its fruits in the upper half: always the full record)
-        p.short_rec = (cfg->rules != MSNAKE_RULES_NEW_WORLD && cfg->record_policy == MSNAKE_RECORD_SHORT) ? 1 : 0;
     // obs_store_policy: should the observation stores carry the nt (streaming) hint?  Measured on
     // MI355X with the native 16-byte-per-lane copy-out (tools/kbench.py --store-policy plain/stream), per launch:
     //   <= 32 MiB of observations (<= 8 192 envs at 19x19x3; fits the 8 L2s): 2-3 % faster with nt
@@ -261,7 +290,8 @@ int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
         if (h->dbg_span_slots < 1) h->dbg_span_slots = 1;
     }
 #endif
-    msnake::step_kernel_name(cfg->rules, cfg->n_snakes, cfg->obs_scale, h->kname, sizeof(h->kname));
+    p.spec_dim = pick_spec_dim(p, cfg->rules);
+    msnake::step_kernel_name(cfg->rules, cfg->n_snakes, cfg->obs_scale, p.spec_dim, h->kname, sizeof(h->kname));
     h->magic = kMagic;
     *out = h;
     return MSNAKE_OK;
@@ -615,6 +645,19 @@ const char* msnake_kernel_name(msnake_handle h) {
     if (check(h)) return "";
     return h->kname;  // owned by the handle: valid until msnake_destroy
 }
+
+int msnake_kernel_name_for_config(const msnake_config* cfg_in, char* out, size_t n) {
+    if (!cfg_in || !out || n == 0) return fail(MSNAKE_E_ARG, "msnake_kernel_name_for_config: NULL argument");
+    msnake_config cfg;
+    if (int rc = validate_config(cfg_in, &cfg)) return rc;
+    msnake::StepParams p;
+    memset(&p, 0, sizeof(p));
+    if (int rc = derive_shape(&cfg, p)) return rc;
+    msnake::step_kernel_name(cfg.rules, cfg.n_snakes, cfg.obs_scale, pick_spec_dim(p, cfg.rules), out, n);
+    return MSNAKE_OK;
+}
+
+int msnake_set_generic_kernels(int32_t on) { return g_generic_kernels.exchange(on ? 1 : 0, std::memory_order_relaxed); }
 
 int64_t msnake_algorithmic_bytes_per_env_step(msnake_handle h) {
     if (check(h)) return -1;

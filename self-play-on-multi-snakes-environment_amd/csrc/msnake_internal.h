@@ -99,6 +99,8 @@ struct StepParams {
     int32_t obs_scale;     // fused WarpFrame replication factor (1, 4 or 7)
     int32_t short_rec;     // 1: the step moves only the first 128 bytes of each record
     int32_t stream_tape;   // 1: msnake_rollout_tape stores observations with the nt hint (set per call)
+    int32_t spec_dim;      // != 0: the handle's step / tape launches use the compile-time shape msnake_step_kernel<.., spec_dim>
+                           // (decided once by msnake_create: spec_dim_of; 0 = the generic kernels)
     // state (HBM, owned by the handle): ONE allocation
     //   [hdr: nenv x 256 B][body0: nenv x n_snakes x 128 B][tmpl: img_bytes][ovf: nenv x n_snakes x cap x 2 B]
     //   adversarial only: [fl0: nenv x 128 B][flist: nenv x fcap x 2 B] (fruit list chunk 0 / complete)
@@ -130,7 +132,10 @@ hipError_t launch_scripted(const StepParams& p, int rules, int policy, uint32_t 
                            uint8_t* safe, hipStream_t stream);
 // env state of `src` into `dst`, one wave per destination env (msnake_copy.inc); src_index NULL = the identity.  Reads `src` only
 hipError_t launch_copy_envs(const StepParams& dst, const StepParams& src, int rules, const int32_t* src_index, hipStream_t stream);
-void step_kernel_name(int rules, int n_snakes, int obs_scale, char* out, size_t n);
+// the DIM of the compile-time-shape instantiation that fits the configuration in `p` in every folded field, or 0 (host only)
+int spec_dim_of(const StepParams& p, int rules);
+// the instantiation that per-step launches run (spec_dim 0: the generic four-parameter one)
+void step_kernel_name(int rules, int n_snakes, int obs_scale, int spec_dim, char* out, size_t n);
 
 }  // namespace msnake
 

@@ -236,13 +236,21 @@ __device__ __forceinline__ void paint_pixel(uint8_t* p, bool head) {
 // The first 14 kernel-argument dwords (pointers + packed configuration) are preloaded into SGPRs
 // by the dispatcher (-mllvm -amdgpu-kernarg-preload-count), so a wave can issue its state loads
 // without waiting for a scalar-memory round trip; the rarely used rest comes by value behind them.
-template <int RULES, int NS, int MODE, int K>
+// DIM: 0 = the shape comes from pk0 / pk1 / pk2 at run time (every configuration).  DIM > 0 = a compile-time shape
+//      (snake_env, native size, step and tape kernels only): a DIM x DIM board, action_stride == NS, auto reset, the
+//      full record.  Everything that follows from those -- S, W, n2, cap, the LDS layout, the divisor -- is a constant
+//      instead of scalar arithmetic that every wave repeats (the scalar port is this kernel's bottleneck).  The launch
+//      glue picks such an instantiation only for a handle and a call that match it in every folded field (spec_dim_of).
+template <int RULES, int NS, int MODE, int K, int DIM = 0>
 __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     uint8_t* __restrict__ state, uint8_t* __restrict__ obs, const int32_t* __restrict__ actions,
     float* __restrict__ rew_out, uint8_t* __restrict__ done_out, const int32_t nenv, const uint32_t pk0,
     const uint32_t pk1, const uint32_t pk2, const StepRest p) {
     constexpr int VIEWS = RULES == MSNAKE_RULES_NEW_WORLD ? NS : 3;
     constexpr int C = 3 * VIEWS;
+    constexpr bool SPEC = DIM > 0;
+    static_assert(!SPEC || (RULES == MSNAKE_RULES_SNAKE_ENV && K == 1 && (MODE == 0 || MODE == 3) && DIM <= MSNAKE_MAX_DIM),
+                  "compile-time shapes: snake_env, native size, step / tape kernels");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     int lane = (int)(threadIdx.x & 63u);  // (not const: MODE 3 hides it from loop-invariant hoisting, see the step loop)
     const int wave = (int)uni(threadIdx.x >> 6);
@@ -293,6 +301,13 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     //  step stride is a multiple of 16 bytes -- the launch glue checks -- so that its LDS-resident background fits all steps)
     const bool align_now = CAN_ALIGN && (MODE != 3 || (pk2 & PK2_TAPE_ALIGNED));
     auto unpack = [&]() {
+        if constexpr (SPEC) {  // the shape is a constant (msnake_create derives S and cap the same way); only max_steps is data
+            dim = DIM; nf = NS; action_stride = NS; auto_reset = true; short_rec = false;
+            max_steps = pk0v >> 16;
+            S = (DIM + 2) * (DIM + 2) * C; cap = (DIM * DIM + 2 + 63) / 64 * 64;
+            W = DIM + 2; n2 = DIM * DIM;
+            return;
+        }
         dim = (int)(pk0v & 63u); nf = (int)((pk0v >> 6) & 63u); action_stride = (int)((pk0v >> 12) & 7u);
         auto_reset = (pk0v >> 15) & 1u;
         max_steps = pk0v >> 16;
@@ -359,7 +374,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     // The same for everything unpacked from the three configuration words (a dozen SGPRs): re-derived behind the fence
     // from copies the compiler cannot see through, so the values of the section before die there.  (The persistent
     // kernel does this once per step already.)
-#define CONFIG_FENCE() do { if (FENCED && MODE != 3) { asm volatile("" : "+s"(pk0v), "+s"(pk1v), "+s"(pk2v)); unpack(); lds_layout(); } } while (0)
+#define CONFIG_FENCE() do { if (FENCED && MODE != 3 && !SPEC) { asm volatile("" : "+s"(pk0v), "+s"(pk1v), "+s"(pk2v)); unpack(); lds_layout(); } } while (0)
 
     // ---- 0. every load whose address depends only on the env index.  One allocation holds
     //         [records | chunk-0 bodies | background image | rings]: one preloaded pointer ---------
@@ -633,10 +648,17 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
         }
         // x / dim and x % dim without a division: pk2 carries M = floor(2^k / dim) + 1 with k = 14 + bits(dim),
         // exact for every x < 2^14 (cell indices stay below 63^2); the launch glue computes M
-        uint32_t p2 = pk2v;
-        asm volatile("" : "+s"(p2));  // (slow path only: nothing of this belongs in the entry block)
-        const uint32_t sh = 14u + 32u - (uint32_t)__builtin_clz((uint32_t)dim);
-        const uint32_t q = ((uint32_t)x * (p2 >> PK2_DIVM_SHIFT)) >> sh;
+        uint32_t q;
+        if constexpr (SPEC) {  // (the same multiplier and shift as div_magic in the launch glue, as immediates)
+            constexpr uint32_t SH = 14u + 32u - (uint32_t)__builtin_clz((uint32_t)DIM);
+            constexpr uint32_t M = (1u << SH) / (uint32_t)DIM + 1u;
+            q = ((uint32_t)x * M) >> SH;
+        } else {
+            uint32_t p2 = pk2v;
+            asm volatile("" : "+s"(p2));  // (slow path only: nothing of this belongs in the entry block)
+            const uint32_t sh = 14u + 32u - (uint32_t)__builtin_clz((uint32_t)dim);
+            q = ((uint32_t)x * (p2 >> PK2_DIVM_SHIFT)) >> sh;
+        }
         const uint32_t r = (uint32_t)x - q * (uint32_t)dim;
         return ((r + 1u) << 8) | (q + 1u);
     };
@@ -736,7 +758,8 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     // computed ahead of the loop and stay live across it (or be spilled).  Redefining `lane` per
     // iteration keeps them local to the step.
     if (MODE == 3) {
-        asm volatile("" : "+v"(lane), "+s"(pk0v), "+s"(pk1v), "+s"(pk2v));
+        if (SPEC) asm volatile("" : "+v"(lane), "+s"(pk0v));  // (a compile-time shape: only max_steps is unpacked)
+        else asm volatile("" : "+v"(lane), "+s"(pk0v), "+s"(pk1v), "+s"(pk2v));
         unpack();
         lds_layout();
         __builtin_amdgcn_s_setprio(0);  // (a slow path of the previous step raised it)
@@ -789,6 +812,21 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
         // write, one address pair (the instruction offset moves both sides), plain tests in between.  (The
         // builtin re-writes M0 per load, and an if / else-if over nk becomes a flag-driven state machine.)
         const uint32_t lds0 = (uint32_t)(uintptr_t)MSNAKE_LP(0);
+        // (a compile-time shape knows its number of KiB: no tests in between)
+        constexpr int NK_SPEC = SPEC ? ((DIM + 2) * (DIM + 2) * C + 15 + 1023) >> 10 : 0;
+        if constexpr (NK_SPEC == 4)
+            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\t"
+                         "global_load_lds_dwordx4 %0, off\n\t"
+                         "global_load_lds_dwordx4 %0, off offset:1024\n\t"
+                         "global_load_lds_dwordx4 %0, off offset:2048\n\t"
+                         "global_load_lds_dwordx4 %0, off offset:3072"
+                         :: "v"(tsrc), "s"(uni(lds0)) : "m0", "memory");
+        else if constexpr (NK_SPEC == 2)
+            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\t"
+                         "global_load_lds_dwordx4 %0, off\n\t"
+                         "global_load_lds_dwordx4 %0, off offset:1024"
+                         :: "v"(tsrc), "s"(uni(lds0)) : "m0", "memory");
+        else
         asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\t"
                      "global_load_lds_dwordx4 %0, off\n\t"
                      "s_cmp_lt_u32 %2, 2\n\ts_cbranch_scc1 1f\n\t"
@@ -1467,9 +1505,18 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
                         const u32x4 v = *reinterpret_cast<const u32x4*>(lsrc + 1024 * i);
                         if constexpr (decltype(NT)::value) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(gdst + 1024 * i));
                         else *reinterpret_cast<u32x4*>(gdst + 1024 * i) = v;
+                        // (a compile-time shape has nothing behind the fourth store, and the two copies of it -- the same
+                        //  instruction but for the hint -- were merged into ONE plain store at the join; an empty asm that
+                        //  differs between the copies keeps them apart: tests/test_isa_guards.py counts both kinds)
+                        if constexpr (SPEC) {
+                            if constexpr (decltype(NT)::value) asm volatile("; streaming copy-out" ::: "memory");
+                            else asm volatile("; plain copy-out" ::: "memory");
+                        }
                     }
                 }
-                if (nk + (uint32_t)(kmin + lead) > 256u)                     // (images beyond 4 KiB)
+                // (images beyond 4 KiB; a compile-time shape whose last chunk, at the largest shift and lead, stays within the
+                //  four unrolled instructions has no such loop)
+                if ((!SPEC || ((S + 15) >> 4) + 7 > 256) && nk + (uint32_t)(kmin + lead) > 256u)
                     for (uint32_t r = rel + 256u; r < nk; r += 64u) {
                         const u32x4 v = *reinterpret_cast<const u32x4*>(lsrc + 16 * (r - rel));
                         if constexpr (decltype(NT)::value) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(gdst + 16 * (size_t)(r - rel)));
@@ -1880,6 +1927,27 @@ static uint32_t div_magic(uint32_t dim) {
     return (uint32_t)((1ull << (14u + bits)) / dim) + 1u;
 }
 
+// The compile-time shapes (msnake_step_kernel<.., DIM>): snake_env at native size, 19x19 with 2 or 3 snakes and 10x10 with
+// one, each as the per-step and the persistent tape kernel.  spec_dim_of: the DIM of the instantiation that fits a
+// configuration in EVERY field the kernel folds (msnake_create asks once per handle), or 0.
+static constexpr bool has_spec(int rules, int ns, int k, int dim) {
+    return rules == MSNAKE_RULES_SNAKE_ENV && k == 1 && ((dim == 19 && (ns == 2 || ns == 3)) || (dim == 10 && ns == 1));
+}
+int spec_dim_of(const StepParams& p, int rules) {
+    if (!has_spec(rules, p.n_snakes, p.obs_scale, p.dim)) return 0;
+    const int W = p.dim + 2, n2 = p.dim * p.dim, S = W * W * 9;
+    if (p.n_fruits != p.n_snakes || !p.auto_reset || p.short_rec || p.views != 3 || p.C != 9) return 0;
+    if (p.S != S || p.rest.cap != (n2 + 2 + 63) / 64 * 64 || p.img_bytes != ((S + 15 + 1023) & ~1023) ||
+        p.lds_per_wave != p.img_bytes + ((n2 + 15) & ~15))
+        return 0;
+    return p.dim;
+}
+// what one launch really runs: the handle's compile-time shape, unless a per-call field that the shape folds differs
+// (an action_stride other than n_snakes) or the mode has no such instantiation (reset, render)
+static int spec_dim_now(const StepParams& p, int mode) {
+    return (p.spec_dim != 0 && (mode == 0 || mode == 3) && p.action_stride == p.n_snakes) ? p.spec_dim : 0;
+}
+
 template <int RULES, int NS, int K>
 static hipError_t launch_k(const StepParams& p, int mode, int epb, hipStream_t stream) {
     const uint32_t pk0 = (uint32_t)p.dim | ((uint32_t)p.n_fruits << 6) | ((uint32_t)p.action_stride << 12) |
@@ -1906,9 +1974,18 @@ static hipError_t launch_k(const StepParams& p, int mode, int epb, hipStream_t s
                          (div_magic((uint32_t)p.dim) << PK2_DIVM_SHIFT);
     const dim3 grid((unsigned)((((p.nenv + epb - 1) / epb) + 63) & ~63));  // whole groups of 64: see the kernel's XCD swap
     const dim3 block(64u * (unsigned)epb);
-#define MSNAKE_LAUNCH(M)                                                                                       \
-    hipLaunchKernelGGL((msnake_step_kernel<RULES, NS, M, K>), grid, block, lds, stream, p.state, p.obs, p.actions, \
+#define MSNAKE_LAUNCH_D(M, D)                                                                                     \
+    hipLaunchKernelGGL((msnake_step_kernel<RULES, NS, M, K, D>), grid, block, lds, stream, p.state, p.obs, p.actions, \
                        p.rest.rew, p.rest.done, p.nenv, pk0, pk1, pk2, p.rest)
+#define MSNAKE_LAUNCH(M) MSNAKE_LAUNCH_D(M, 0)
+    constexpr int SPEC_DIM = has_spec(RULES, NS, K, 19) ? 19 : has_spec(RULES, NS, K, 10) ? 10 : 0;
+    if constexpr (SPEC_DIM != 0) {
+        if (spec_dim_now(p, mode) == SPEC_DIM) {
+            if (mode == 0) MSNAKE_LAUNCH_D(0, SPEC_DIM);
+            else MSNAKE_LAUNCH_D(3, SPEC_DIM);
+            return hipGetLastError();
+        }
+    }
     switch (mode) {
         case 0: MSNAKE_LAUNCH(0); break;
         case 1: MSNAKE_LAUNCH(1); break;
@@ -1916,6 +1993,7 @@ static hipError_t launch_k(const StepParams& p, int mode, int epb, hipStream_t s
         default: MSNAKE_LAUNCH(2); break;
     }
 #undef MSNAKE_LAUNCH
+#undef MSNAKE_LAUNCH_D
     return hipGetLastError();
 }
 
@@ -1952,8 +2030,9 @@ hipError_t launch_step(const StepParams& p, int rules, int mode, int epb, hipStr
     }
 }
 
-void step_kernel_name(int rules, int n_snakes, int obs_scale, char* out, size_t n) {
-    snprintf(out, n, "msnake_step_kernel<%d, %d, 0, %d>", rules, n_snakes, obs_scale);
+void step_kernel_name(int rules, int n_snakes, int obs_scale, int spec_dim, char* out, size_t n) {
+    if (spec_dim != 0) snprintf(out, n, "msnake_step_kernel<%d, %d, 0, %d, %d>", rules, n_snakes, obs_scale, spec_dim);
+    else snprintf(out, n, "msnake_step_kernel<%d, %d, 0, %d>", rules, n_snakes, obs_scale);
 }
 
 }  // namespace msnake

@@ -183,6 +183,7 @@ class MultiSnakeVecEnv:
                                       int(envs_per_block), _capi.RECORD_POLICY[record_policy],
                                       _capi.STORE_POLICY[obs_store_policy], _capi.STORE_POLICY[tape_store_policy])
         self._h = ctypes.c_void_p()
+        _capi.apply_kernel_switch()  # (MSNAKE_GENERIC_KERNELS, read when the handle is created)
         _capi.check(self._L.msnake_create(ctypes.byref(self.cfg), ctypes.byref(self._h)), "msnake_create")
         H, W, C = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
         _capi.check(self._L.msnake_obs_shape(self._h, ctypes.byref(H), ctypes.byref(W), ctypes.byref(C)))

@@ -4,6 +4,7 @@ lines and the rocprofv3 kernel stats of the same box).   usage: compose_span_gap
 import csv
 import json
 import os
+import re
 import sys
 
 tag = sys.argv[1]
@@ -28,7 +29,7 @@ k20 = bench_line(os.path.join(out, "bench_k20.json"))["roofline"]["launch_us"]
 prof = bench_line(os.path.join(root, "gpurun_out", f"prof_{tag}_4096", "bench_plain.json"))["roofline"]["launch_us"]
 rp = None
 for r in csv.DictReader(open(os.path.join(root, "profiles", f"{tag}_4096_kernel_stats.csv"))):
-    if "msnake_step_kernel<0, 3, 0, 1>" in r["Name"]:
+    if re.search(r"msnake_step_kernel<0, 3, 0, 1(, \d+)?>", r["Name"]):  # (generic or compile-time shape)
         rp = (float(r["AverageNs"]) / 1e3, int(r["Calls"]))
 gap = round((dbg["gap_us"] + light["gap_us"]) / 2, 3)
 alg = 4411 * 4096

@@ -11,7 +11,7 @@ for st in 7 2 3 4 5 6 0; do
   timeout -k 10 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_BRANCH SQ_WAVES --output-format csv -d $OUT/st$st -- python3 $R/tools/pmc_stage.py $st > $OUT/st$st.log 2>&1 || echo "stage $st failed"
 done
 python3 - <<PY
-import csv, glob, collections, statistics
+import csv, glob, collections, re, statistics
 names = {7: "prologue + loads + wait", 2: "+ moves", 3: "+ collision matrix", 4: "+ aliveness", 5: "+ stats, outputs, reset", 6: "+ paint", 0: "+ copy-out, write-back (whole kernel)"}
 prev = None
 for st in (7, 2, 3, 4, 5, 6, 0):
@@ -20,7 +20,7 @@ for st in (7, 2, 3, 4, 5, 6, 0):
         print(st, "no data"); continue
     acc = collections.defaultdict(list)
     for r in csv.DictReader(open(f[0])):
-        if "msnake_step_kernel<0, 3, 0, 1>" in r["Kernel_Name"]:
+        if re.search(r"msnake_step_kernel<0, 3, 0, 1(, \\d+)?>", r["Kernel_Name"]):  # (generic or compile-time shape)
             acc[r["Counter_Name"]].append(float(r["Counter_Value"]))
     k = 32  # the staged launches are the last 32
     w = statistics.median(acc["SQ_WAVES"][-k:])
