@@ -246,6 +246,27 @@ int msnake_render(msnake_handle h, uint8_t* obs_dev, void* stream);
 int msnake_scripted_actions(msnake_handle h, int32_t policy, uint32_t snake_mask, int32_t* actions_dev,
                             int32_t action_stride, uint8_t* safe_dev, void* stream);
 
+/* Reachable-space counts and the flood-fill opponent space_greedy, in the terms of msnake_scripted_actions (`used`,
+ * moves 1..4, open); a cell is free iff it lies in the grid and not in `used`.
+ * space_dev (may be NULL): uint16 [num_envs][n_snakes][4], written for every snake whatever snake_mask is: entry m
+ * is the number of free cells 4-connected to the target of move m + 1 through free cells, the target included; 0
+ * when move m + 1 is not open, and all four are 0 for an empty body.  At most 62^2 - 1.  2-byte aligned
+ * (MSNAKE_E_ALIGN otherwise).
+ * safe_dev (may be NULL): exactly what msnake_scripted_actions writes there.
+ * actions_dev: int32 [num_envs][action_stride]; entry s of every row is written for each s with bit s of
+ * snake_mask set, all other entries are left untouched.  The policy space_greedy: with len = the snake's body
+ * length as the canonical state gives it (duplicates counted), the action is 0 if the body is empty or no move is
+ * open; otherwise need = min(len, max over the open moves of space), the eligible moves are the open moves with
+ * space >= need, and the action is the first eligible move, in the order 1, 2, 3, 4, whose target has the strictly
+ * smallest L1 distance to any fruit of the state's fruit list (adversarial: the complete list; distance 0 when the
+ * list is empty).  The velocity plays no part; odd boards are fine.
+ * Like its sibling the call only reads the handle's state, draws no random numbers, allocates nothing, does not
+ * synchronise and adds nothing to env_steps; asynchronous on `stream`, and it can be captured into a HIP graph in
+ * front of the step.  MSNAKE_E_ARG, before any device work: a snake_mask bit >= n_snakes; actions_dev NULL or
+ * action_stride < n_snakes when snake_mask != 0; nothing to write (snake_mask 0, safe_dev and space_dev NULL). */
+int msnake_space_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride,
+                         uint8_t* safe_dev, uint16_t* space_dev, void* stream);
+
 /* Copy env state from `src` into `dst` on the device: destination env e receives the state of source env
  * src_index_dev[e] (int32 [dst.num_envs], a device pointer).  A negative entry leaves destination env e completely
  * untouched: no byte of its record, rings or lists is written.  NULL means the identity and needs equal env counts.

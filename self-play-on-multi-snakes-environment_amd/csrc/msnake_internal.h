@@ -130,6 +130,9 @@ hipError_t launch_state_unpack(const StepParams& p, int rules, int env0, int cou
 // scripted opponents / safe-move masks from the state in HBM (msnake_scripted.inc); reads the handle's state only
 hipError_t launch_scripted(const StepParams& p, int rules, int policy, uint32_t snake_mask, int32_t* actions, int32_t action_stride,
                            uint8_t* safe, hipStream_t stream);
+// reachable-space counts and the space_greedy opponent (msnake_space.inc); reads the handle's state only
+hipError_t launch_space(const StepParams& p, int rules, uint32_t snake_mask, int32_t* actions, int32_t action_stride, uint8_t* safe,
+                        uint16_t* space, hipStream_t stream);
 // env state of `src` into `dst`, one wave per destination env (msnake_copy.inc); src_index NULL = the identity.  Reads `src` only
 hipError_t launch_copy_envs(const StepParams& dst, const StepParams& src, int rules, const int32_t* src_index, hipStream_t stream);
 // the DIM of the compile-time-shape instantiation that fits the configuration in `p` in every folded field, or 0 (host only)

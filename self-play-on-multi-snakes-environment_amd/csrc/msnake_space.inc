@@ -1,0 +1,246 @@
+// msnake_space.inc -- reachable-space counts and the flood-fill opponent space_greedy (msnake_space_actions).
+// Included behind msnake_scripted.inc at the end of msnake_kernels.hip: it uses that file's wave helpers and
+// wave_reduce, and must stay in its translation unit.  Off the step path.
+//
+// One wavefront per env; the wave only READS the handle's state (record by lane, 64-slot rings, overflow rings
+// strided in whole waves, the adversarial `flist`), exactly as msnake_scripted_kernel does.
+//   * Occupancy: lane y owns row y of the board as ONE 64-bit mask, bit x <-> cell (x, y) = (c0, c1).  The body
+//     cells arrive lane-distributed (lane <-> ring slot), so they are scattered through a wave-private 512-byte
+//     slice of static LDS: one ds_or per cell, then every lane reads its own row once.  DS operations of one wave
+//     execute in program order, so wave_sync() (a compiler fence) is all the ordering this needs: no workgroup
+//     barrier -- the waves of the batch tail have returned by then.  `vacant` = ~used inside the grid; rows >= dim
+//     and bits >= dim are 0, i.e. blocked.
+//   * The 16 candidates (4 snakes x 4 moves) live in lanes 0..15, lane 4 s + m <-> move m + 1 of snake s: target
+//     coordinates, open bit, and in the end the count.  Whether a target is free is one ds_bpermute gather of the
+//     target row's mask.
+//   * A fill is one seed bit, then sweeps r |= ((r << 1) | (r >> 1) | row_above | row_below) & vacant; the
+//     neighbour rows come by DPP wave_shr:1 / wave_shl:1 with bound_ctrl (lane 0 / lane 63 receive 0; rows >= dim
+//     hold 0 anyway).  No LDS traffic in the loop.  Four sweeps per convergence test (one ballot); growth is
+//     monotone and a region has at most dim^2 cells, so the loop is cut after dim^2 sweeps whatever the record says.
+//   * Count = popcount per lane + one DPP sum over the wave.  After a fill, every still-pending candidate whose
+//     target bit lies in the finished region takes the same count (one more gather): a board with one big free
+//     region costs ONE fill per env, however many snakes and moves.  The result does not depend on that reuse: the
+//     regions of two targets are either equal or disjoint.
+//   * space_greedy: need = min(len, max over the open moves of space) by two quad-permute DPP steps, eligible =
+//     open && space >= need, then safe_greedy's choice among the eligible moves (min over (fruit, move) pairs of
+//     distance << 3 | move, fruits lane-distributed).
+//   * lane s stores snake s's action word and mask byte, lane 4 s + m the count of move m + 1.
+// No random numbers, no global atomics, no workgroup barrier, no scratch.
+namespace msnake {
+
+struct SpaceArgs {
+    const uint32_t* hdr; const uint16_t* body0; const uint16_t* ovf; const uint16_t* flist;
+    int32_t* actions; uint8_t* safe; uint16_t* space;
+    int32_t nenv, dim, ns, nf, cap, fcap, rules, stride;
+    uint32_t mask;
+};
+
+constexpr int SPACE_WAVES = 4;  // waves (envs) per workgroup
+
+// row y - 1 / row y + 1 of a row-per-lane mask; the lane without a neighbour receives 0
+__device__ __forceinline__ uint64_t row_above(uint64_t r) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)r, 0x138, 0xF, 0xF, true);          // wave_shr:1
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(r >> 32), 0x138, 0xF, 0xF, true);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t row_below(uint64_t r) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)r, 0x130, 0xF, 0xF, true);          // wave_shl:1
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(r >> 32), 0x130, 0xF, 0xF, true);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// sum over the wave: an inclusive scan inside the rows of 16 (row_shr 1, 2, 4, 8; a lane without a source adds 0),
+// then row_bcast:15 into rows 1, 3 and row_bcast:31 into rows 2, 3.  The total is in lane 63.
+__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, true);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, true);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, true);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);
+    return rdlane(x, 63);
+}
+
+// lane l receives v of lane src(l) & 63
+__device__ __forceinline__ uint64_t gather_row(uint64_t v, int src) {
+    const int addr = (src & 63) << 2;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)(uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// ACT: the space_greedy actions are written (snake_mask != 0); SAFE / SPACE: safe_dev / space_dev are written
+template <bool ACT, bool SAFE, bool SPACE>
+__global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArgs a) {
+    __shared__ uint32_t occ[SPACE_WAVES][128];  // per wave: row y = words 2 y (bits 0..31) and 2 y + 1 (bits 32..63)
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = (int)uni(threadIdx.x >> 6);
+    const int e = (int)uni(blockIdx.x * SPACE_WAVES + (threadIdx.x >> 6));
+    if (e >= a.nenv) return;  // (no workgroup barrier below)
+    const int ns = a.ns, dim = a.dim;
+    const uint32_t hv = a.hdr[(size_t)e * MSNAKE_HDR_WORDS + lane];
+    uint32_t ring[MSNAKE_MAX_SNAKES];
+#pragma unroll
+    for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s)
+        ring[s] = s < ns ? (uint32_t)a.body0[((size_t)e * ns + s) * 64 + lane] : 0u;
+    uint32_t* my = occ[wave];
+    my[lane] = 0u;
+    my[64 + lane] = 0u;
+    wave_sync();
+
+    // ---- occupancy: every body cell inside the grid sets its bit
+    auto mark = [&](uint32_t c, bool valid) {
+        const int x = (int)(c >> 8) - 1, y = (int)(c & 255u) - 1;
+        if (valid && x >= 0 && x < dim && y >= 0 && y < dim)
+            __hip_atomic_fetch_or(&my[2 * y + (x >> 5)], 1u << (x & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    int len[MSNAKE_MAX_SNAKES], hx[MSNAKE_MAX_SNAKES], hy[MSNAKE_MAX_SNAKES];
+#pragma unroll
+    for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
+        len[s] = 0; hx[s] = hy[s] = -2;
+        if (s >= ns) continue;
+        len[s] = (int)(rdlane(hv, SN_A(s)) >> 16);
+        const int hp0 = (int)((rdlane(hv, SN_C(s)) >> SN_C_HP0_SHIFT) & 63u);
+        if (len[s] > 0) {
+            const uint32_t head = rdlane(ring[s], hp0);  // piece 0 sits in ring slot hp0
+            hx[s] = (int)(head >> 8) - 1; hy[s] = (int)(head & 255u) - 1;
+        }
+        const int n0 = len[s] < 64 ? len[s] : 64;
+        mark(ring[s], ((lane - hp0) & 63) < n0);
+        if (len[s] > 64) {  // pieces >= 64: the overflow ring, piece i at (ohp + i - 64) % cap
+            const int ohp = (int)(rdlane(hv, SN_A(s)) & 0xFFFFu);
+            const int n = len[s] < 64 + a.cap ? len[s] : 64 + a.cap;
+            for (int base = 64; base < n; base += 64) {
+                const int i = base + lane;
+                int idx = ohp + i - 64;
+                idx = idx >= a.cap ? idx - a.cap : idx;
+                idx = idx >= a.cap ? a.cap - 1 : idx;  // (a well-formed record never gets here)
+                idx = idx < 0 ? 0 : idx;
+                mark((uint32_t)a.ovf[((size_t)e * ns + s) * a.cap + idx], i < n);
+            }
+        }
+    }
+    wave_sync();
+    const uint64_t used = (uint64_t)my[2 * lane] | ((uint64_t)my[2 * lane + 1] << 32);
+    const uint64_t vacant = lane < dim ? ~used & ((1ull << dim) - 1ull) : 0ull;
+
+    // ---- the candidates: lane 4 s + m <-> move m + 1 of snake s
+    const int cs = lane >> 2, cm = lane & 3;
+    const int my_len = cs == 0 ? len[0] : cs == 1 ? len[1] : cs == 2 ? len[2] : cs == 3 ? len[3] : 0;
+    const int my_hx = cs == 0 ? hx[0] : cs == 1 ? hx[1] : cs == 2 ? hx[2] : hx[3];
+    const int my_hy = cs == 0 ? hy[0] : cs == 1 ? hy[1] : cs == 2 ? hy[2] : hy[3];
+    const int tx = my_hx + (cm == 0 ? 1 : cm == 2 ? -1 : 0), ty = my_hy + (cm == 1 ? 1 : cm == 3 ? -1 : 0);
+    const bool onb = lane < 4 * ns && my_len > 0 && tx >= 0 && tx < dim && ty >= 0 && ty < dim;
+    const int gx = onb ? tx : 0, gy = onb ? ty : 0;  // what the gathers index with: always inside the wave
+    const uint64_t target_row = gather_row(vacant, gy);  // (every lane takes part: the source lanes must be active)
+    const bool is_open = onb && ((target_row >> gx) & 1ull);
+    const uint32_t open_all = (uint32_t)__ballot(is_open);  // bit 4 s + m: move m + 1 of snake s is open
+
+    // ---- fills: one per distinct region that holds an open target
+    uint32_t space = 0u;
+    uint32_t pending = open_all;
+    const int max_sweeps = dim * dim;
+    for (int guard = 0; pending != 0u && guard < 16; ++guard) {
+        const int k = __builtin_ctz(pending);
+        const int sx = (int)rdlane((uint32_t)gx, k), sy = (int)rdlane((uint32_t)gy, k);
+        uint64_t r = lane == sy ? 1ull << sx : 0ull;
+        for (int sweeps = 0; sweeps < max_sweeps; sweeps += 4) {
+            const uint64_t before = r;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) r |= ((r << 1) | (r >> 1) | row_above(r) | row_below(r)) & vacant;
+            if (__ballot(r != before) == 0ull) break;
+        }
+        const uint32_t cells = wave_sum((uint32_t)__popcll(r));
+        const uint64_t filled_row = gather_row(r, gy);
+        const bool inside = lane < 16 && ((pending >> lane) & 1u) && ((filled_row >> gx) & 1ull);
+        const uint32_t got = (uint32_t)__ballot(inside) | (1u << k);
+        if (lane < 16 && ((got >> lane) & 1u)) space = cells;
+        pending &= ~got;
+    }
+
+    // ---- space_greedy: the eligible moves, then safe_greedy's choice among them
+    uint32_t act[MSNAKE_MAX_SNAKES];
+#pragma unroll
+    for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) act[s] = 0u;
+    if (ACT) {
+        uint32_t mx = space;  // (0 where the move is not open)
+        uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mx, 0xB1, 0xF, 0xF, true);  // quad_perm:[1,0,3,2]
+        mx = mx > o ? mx : o;
+        o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mx, 0x4E, 0xF, 0xF, true);           // quad_perm:[2,3,0,1]
+        mx = mx > o ? mx : o;
+        const uint32_t need = (uint32_t)my_len < mx ? (uint32_t)my_len : mx;
+        const uint32_t elig_all = (uint32_t)__ballot(lane < 16 && ((open_all >> lane) & 1u) && space >= need);
+        uint32_t elig[MSNAKE_MAX_SNAKES];
+#pragma unroll
+        for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) elig[s] = (elig_all >> (4 * s)) & 15u;
+
+        const bool adv = a.rules == MSNAKE_RULES_ADVERSARIAL;
+        const int fr0 = a.rules == MSNAKE_RULES_NEW_WORLD ? HDR_FRUIT0_N : HDR_FRUIT0_S;
+        int nfr = adv ? (int)rdlane(hv, HDR_NLIST) : a.nf;
+        if (adv && nfr > a.fcap) nfr = a.fcap;
+        uint32_t key[MSNAKE_MAX_SNAKES];  // min over this lane's fruits and the eligible moves of distance << 3 | move
+#pragma unroll
+        for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) key[s] = 0xFFFFFFFFu;
+        auto fruit = [&](uint32_t c, bool valid) {
+            const int fx = (int)(c >> 8) - 1, fy = (int)(c & 255u) - 1;
+#pragma unroll
+            for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s)
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    const int qx = hx[s] + (m == 0 ? 1 : m == 2 ? -1 : 0), qy = hy[s] + (m == 1 ? 1 : m == 3 ? -1 : 0);
+                    const int dx = fx - qx, dy = fy - qy;
+                    const uint32_t kk = ((uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy)) << 3) | (uint32_t)(m + 1);
+                    if (valid && ((elig[s] >> m) & 1u) && kk < key[s]) key[s] = kk;
+                }
+        };
+        if (adv) {
+            for (int base = 0; base < nfr; base += 64) {
+                const int f = base + lane;
+                const int fi = f < nfr ? f : 0;
+                fruit((uint32_t)a.flist[(size_t)e * a.fcap + fi], f < nfr);
+            }
+        } else {
+            fruit(hv & 0xFFFFu, lane >= fr0 && lane < fr0 + nfr);
+        }
+#pragma unroll
+        for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
+            if (s >= ns || elig[s] == 0u) continue;
+            if (nfr <= 0) {  // every distance is 0: the first eligible move
+                act[s] = (uint32_t)__builtin_ctz(elig[s]) + 1u;
+            } else {
+                act[s] = wave_reduce(key[s], [](uint32_t x, uint32_t y) { return x < y ? x : y; }) & 7u;
+            }
+        }
+    }
+
+    // lane s owns snake s's action word and mask byte, lane 4 s + m the count of move m + 1
+    if (lane < ns) {
+        const uint32_t my_act = lane == 0 ? act[0] : lane == 1 ? act[1] : lane == 2 ? act[2] : act[3];
+        if (ACT && ((a.mask >> lane) & 1u)) a.actions[(size_t)e * a.stride + lane] = (int32_t)my_act;
+        if (SAFE) a.safe[(size_t)e * ns + lane] = (uint8_t)(((open_all >> (4 * lane)) & 15u) << 1);
+    }
+    if (SPACE && lane < 4 * ns) a.space[(size_t)e * ns * 4 + lane] = (uint16_t)space;
+}
+
+hipError_t launch_space(const StepParams& p, int rules, uint32_t snake_mask, int32_t* actions, int32_t action_stride, uint8_t* safe,
+                        uint16_t* space, hipStream_t stream) {
+    const SpaceArgs a{p.hdr, p.body0, p.ring, p.flist, actions, safe, space, p.nenv, p.dim, p.n_snakes, p.n_fruits, p.rest.cap,
+                      p.fcap, rules, action_stride, snake_mask};
+    const dim3 grid((unsigned)((p.nenv + SPACE_WAVES - 1) / SPACE_WAVES)), block(SPACE_WAVES * 64);
+    const int which = (snake_mask != 0u ? 4 : 0) | (safe ? 2 : 0) | (space ? 1 : 0);
+#define MSNAKE_SPACE(A, S, C) hipLaunchKernelGGL((msnake_space_kernel<A, S, C>), grid, block, 0, stream, a)
+    switch (which) {
+        case 1: MSNAKE_SPACE(false, false, true); break;
+        case 2: MSNAKE_SPACE(false, true, false); break;
+        case 3: MSNAKE_SPACE(false, true, true); break;
+        case 4: MSNAKE_SPACE(true, false, false); break;
+        case 5: MSNAKE_SPACE(true, false, true); break;
+        case 6: MSNAKE_SPACE(true, true, false); break;
+        case 7: MSNAKE_SPACE(true, true, true); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef MSNAKE_SPACE
+    return hipGetLastError();
+}
+
+}  // namespace msnake

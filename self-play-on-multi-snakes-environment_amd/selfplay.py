@@ -320,6 +320,9 @@ class MonitorCSV:
 
 
 # ----------------------------------------------------------------------------- scripted opponents
+SCRIPTED_POLICIES = ("safe_greedy", "hamiltonian", "space_greedy")
+
+
 class ScriptedColumns:
     """The scripted action columns of a team of ScriptedOpponents of one env, in a buffer of its own: refresh() fills the
     columns of every member with ONE env call per policy, each member's step() then reads its own.  Whoever drives the
@@ -351,7 +354,7 @@ class ScriptedColumns:
 
 class ScriptedOpponent:
     """A fixed, deterministic opponent in the place of a CnnPolicy: snake `snake` plays the env's on-device scripted
-    `policy` ("safe_greedy" or "hamiltonian", MultiSnakeVecEnv.scripted_actions_device).  step(obs) has the shape
+    `policy` ("safe_greedy", "hamiltonian" or "space_greedy", MultiSnakeVecEnv.scripted_actions_device).  step(obs) has the shape
     Runner.multi_step calls; the observation is ignored, the env's state is asked.  eps > 0: with probability eps
     the action is replaced by randint(0, 5), drawn with torch on the env's device from `generator` (the env's own
     random numbers are never used).  On its own (columns=None) every step() is one env call.  Several opponents of one
@@ -359,8 +362,8 @@ class ScriptedOpponent:
     columns.refresh(), which the driver calls before the members' step()."""
 
     def __init__(self, env, policy, snake, eps=0.0, generator=None, columns=None):
-        if policy not in ("safe_greedy", "hamiltonian"):
-            raise ValueError(f"policy must be 'safe_greedy' or 'hamiltonian', got {policy!r}")
+        if policy not in SCRIPTED_POLICIES:
+            raise ValueError(f"policy must be one of {', '.join(map(repr, SCRIPTED_POLICIES))}, got {policy!r}")
         if not 0 <= int(snake) < env.n_snakes:
             raise ValueError(f"snake must lie in [0, {env.n_snakes}), got {snake!r}")
         self.env, self.policy, self.snake, self.eps, self.generator = env, policy, int(snake), float(eps), generator

@@ -227,6 +227,7 @@ class MultiSnakeVecEnv:
         self._cur_stream = torch.cuda.current_stream
         self._scripted_fn = self._L.msnake_scripted_actions
         self._scripted_out = None  # scripted_actions_device(out=None): allocated on first use
+        self._space_fn = self._L.msnake_space_actions
 
     # ------------------------------------------------------------------ device-side API
     def _stream(self):
@@ -315,16 +316,30 @@ class MultiSnakeVecEnv:
                              f"{self.device}")
         return out
 
-    def scripted_actions_device(self, policy, snakes=None, out=None, safe_out=None):
-        """Actions of a scripted policy ("safe_greedy", "hamiltonian", or None for the mask alone) for the snakes in
-        `snakes` (indices; default every snake), computed on the device from the env's current state.  They go to
+    def _space_out(self, out):
+        torch = self._torch
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint16 or out.device != self.device or
+                tuple(out.shape) != (self.num_envs, self.n_snakes, 4) or not out.is_contiguous()):
+            raise ValueError(f"space_out must be a contiguous uint16 tensor of shape ({self.num_envs}, {self.n_snakes}, 4) on "
+                             f"{self.device}")
+        return out
+
+    def scripted_actions_device(self, policy, snakes=None, out=None, safe_out=None, space_out=None):
+        """Actions of a scripted policy ("safe_greedy", "hamiltonian", "space_greedy", or None for the mask alone) for the
+        snakes in `snakes` (indices; default every snake), computed on the device from the env's current state.  They go to
         columns `snakes` of `out`, an int32 [num_envs, >= n_snakes] device tensor as step_device() takes it; its other
         columns are left as they are (out=None: a cached, zero-initialised [num_envs, n_snakes] tensor of the env).
         `safe_out`, a uint8 [num_envs, n_snakes] device tensor, gets every snake's safe-move mask (bit a = move a leads
         to an on-board cell that no body occupies).  Returns `out`, or (out, safe_out) when a mask was asked for;
-        nothing is synchronised.  Draws no random numbers and changes no env state."""
+        nothing is synchronised.  Draws no random numbers and changes no env state.
+        "space_greedy" (msnake_space_actions) flood-fills from every open move's target and refuses moves into a region
+        smaller than the body; only with it, `space_out`, a uint16 [num_envs, n_snakes, 4] device tensor, gets the
+        reachable-space counts (see reachable_space_device) and is returned behind the others that were asked for."""
         torch = self._torch
-        if policy not in _capi.SCRIPTED_POLICY:
+        space = policy == _capi.SPACE_POLICY
+        if space_out is not None and not space:
+            raise ValueError(f"space_out is written by policy 'space_greedy' only, got policy {policy!r}")
+        if not space and policy not in _capi.SCRIPTED_POLICY:
             raise ValueError(f"policy must be 'safe_greedy', 'hamiltonian' or None, got {policy!r}")
         if snakes is None:
             bits = (1 << self.n_snakes) - 1
@@ -343,6 +358,14 @@ class MultiSnakeVecEnv:
               out.shape[0] != self.num_envs or out.shape[1] < self.n_snakes or not out.is_contiguous()):
             raise ValueError(f"out must be a contiguous int32 tensor of shape ({self.num_envs}, >= {self.n_snakes}) on {self.device}")
         p_safe = self._safe_out(safe_out).data_ptr() if safe_out is not None else None
+        if space:
+            p_space = self._space_out(space_out).data_ptr() if space_out is not None else None
+            rc = self._space_fn(self._h, bits, out.data_ptr(), int(out.shape[1]), p_safe, p_space,
+                                self._cur_stream(self.device).cuda_stream)
+            if rc < 0:
+                _capi.check(rc, "msnake_space_actions")
+            res = (out,) + tuple(t for t in (safe_out, space_out) if t is not None)
+            return res[0] if len(res) == 1 else res
         rc = self._scripted_fn(self._h, _capi.SCRIPTED_POLICY[policy], bits, out.data_ptr(), int(out.shape[1]), p_safe,
                                self._cur_stream(self.device).cuda_stream)
         if rc < 0:
@@ -358,6 +381,18 @@ class MultiSnakeVecEnv:
         rc = self._scripted_fn(self._h, 0, 0, None, 0, self._safe_out(out).data_ptr(), self._cur_stream(self.device).cuda_stream)
         if rc < 0:
             _capi.check(rc, "msnake_scripted_actions")
+        return out
+
+    def reachable_space_device(self, out=None):
+        """uint16 [num_envs, n_snakes, 4]: entry m of a snake is the number of free cells 4-connected to the target of
+        its move m + 1 through free cells, the target included; 0 when that move is not open (off the board or into a
+        body) or the body is empty.  One flood fill per distinct region, on the device; nothing is synchronised."""
+        if out is None:
+            with self._torch.cuda.device(self.device):
+                out = self._torch.empty((self.num_envs, self.n_snakes, 4), dtype=self._torch.uint16, device=self.device)
+        rc = self._space_fn(self._h, 0, None, 0, None, self._space_out(out).data_ptr(), self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_space_actions")
         return out
 
     def rollout_device(self, tape, persistent=True, keep_obs=True):

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
-"""Cost of msnake_scripted_actions next to msnake_step on the same handle.  19x19x3 snake_env at 4 096 and 32 768 envs,
-on a freshly reset batch and 500 steps into safe_greedy play (longer bodies).  The Hamiltonian cycle needs an even
-board: its legs run on a 20x20 handle of the same batch, in the same kind of state.
+"""Cost of msnake_scripted_actions and msnake_space_actions next to msnake_step on the same handle.  19x19x3 snake_env at
+4 096 and 32 768 envs, on a freshly reset batch and 500 steps into safe_greedy play (longer bodies).  The Hamiltonian
+cycle needs an even board: its legs run on a 20x20 handle of the same batch, in the same kind of state.  The "->step"
+legs are one scripted call and one step per call (the self-play loop on the device).  `worst_case_62x62`: the flood
+fill's longest runs, serpentine mazes of a 62x62 board (one corridor of 1 953 cells, along the rows and along the
+columns, nine head positions each), copied over the whole batch.
 
 Two figures per leg, both from HIP events after a warm-up, legs alternating in one process:
   graph_us: CALLS back-to-back calls captured into one HIP graph (a linear chain) and replayed: the kernel's cadence,
@@ -17,6 +20,26 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def serpentine_states(dim, transposed):
+    """Canonical states of a two-snake snake_env: snake 1 is a serpentine wall (the odd rows, each with one gap at
+    alternating ends), snake 0 a single cell at nine places of the corridor."""
+    walls, path, right = [], [], True
+    for y in range(dim):
+        if y % 2 == 0:
+            path += [(x, y) for x in (range(dim) if right else range(dim - 1, -1, -1))]
+        else:
+            gap = dim - 1 if right else 0
+            walls += [(x, y) for x in range(dim) if x != gap]
+            path.append((gap, y))
+            right = not right
+    if transposed:
+        walls, path = [(y, x) for x, y in walls], [(y, x) for x, y in path]
+    L = len(path)
+    return [{"t": 0, "ctr": 0, "spare_fruits": 0, "ep_len": 0, "ep_return": 0.0, "fruits": [[0, 0], [0, 0]],
+             "snakes": [[list(path[i])], [list(c) for c in walls]], "vels": [[1, 0]] * 2, "grow_to": [1, len(walls)],
+             "alive": [True] * 2, "in_dead": [False] * 2} for i in (0, 1, L // 8, L // 4, L // 3, L // 2, 2 * L // 3, L - 2, L - 1)]
 
 
 def main():
@@ -51,13 +74,19 @@ def main():
         acts = torch.ones((n, 3), dtype=torch.int32, device=env.device)
         ones = torch.ones((n, 3), dtype=torch.int32, device=env.device)
         safe = torch.zeros((n, 3), dtype=torch.uint8, device=env.device)
+        space = torch.zeros((n, 3, 4), dtype=torch.uint16, device=env.device)
         legs = {
             "safe_greedy": lambda: env.scripted_actions_device("safe_greedy", out=acts),
             "safe_greedy+mask": lambda: env.scripted_actions_device("safe_greedy", out=acts, safe_out=safe),
             "hamiltonian_20x20": lambda: env20.scripted_actions_device("hamiltonian", out=acts),
             "hamiltonian_20x20+mask": lambda: env20.scripted_actions_device("hamiltonian", out=acts, safe_out=safe),
             "mask_only": lambda: env.safe_moves_device(out=safe),
+            "space_greedy": lambda: env.scripted_actions_device("space_greedy", out=acts),
+            "space_greedy+mask+space": lambda: env.scripted_actions_device("space_greedy", out=acts, safe_out=safe, space_out=space),
+            "space_only": lambda: env.reachable_space_device(out=space),
             "msnake_step": lambda: env.step_device(ones),
+            "safe_greedy->step": lambda: env.step_device(env.scripted_actions_device("safe_greedy", out=acts)),
+            "space_greedy->step": lambda: env.step_device(env.scripted_actions_device("space_greedy", out=acts)),
         }
         out = {}
         for state in ("fresh_reset", f"after_{args.play_steps}_greedy_steps"):
@@ -91,6 +120,36 @@ def main():
             out[state] = {k: {kind: med(v) for kind, v in t.items()} for k, t in times.items()}
         res["batches"][str(n)] = out
         env.close(), env20.close()
+    from oracle.snake_oracle import state_to_flat
+    res["worst_case_62x62"] = {}
+    for n in args.envs:
+        out = {}
+        for name, transposed in (("walls_on_rows", False), ("walls_on_columns", True)):
+            states = serpentine_states(62, transposed)
+            src = msnake.MultiSnakeVecEnv(len(states), dim=62, n_snakes=2, rules="snake_env", seed=0)
+            env = msnake.MultiSnakeVecEnv(n, dim=62, n_snakes=2, rules="snake_env", seed=0)
+            src.reset_device(), env.reset_device()
+            for e, st in enumerate(states):
+                src.set_state_words(e, state_to_flat(st, 2))
+            env.copy_envs_device(src, torch.arange(n, dtype=torch.int32, device=env.device) % len(states))
+            acts = torch.ones((n, 2), dtype=torch.int32, device=env.device)
+            space = torch.zeros((n, 2, 4), dtype=torch.uint16, device=env.device)
+            fn = lambda: env.scripted_actions_device("space_greedy", out=acts, space_out=space)
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                fn(), fn()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for _ in range(args.calls):
+                    fn()
+            v = [timed(g.replay) for _ in range(args.rounds)]
+            out[name] = {"graph_us": [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)],
+                         "largest_count": int(space.view(torch.int16).max())}
+            env.close(), src.close()
+        res["worst_case_62x62"][str(n)] = out
     print(json.dumps(res, indent=1))
 
 
