@@ -35,6 +35,8 @@
  *   msnake_copy_envs <- no reference counterpart (a reference env can only be re-created and replayed); the analogue is
  *                      ALE's cloneState / restoreState, batched and on the device: snapshot, fork and restore of envs
  *                      between two handles without the host round trip of msnake_get_state / msnake_set_state.
+ *   msnake_render_cells <- get_ob_for_snake / get_multi_snake_ob (snake_multiple_test.py:35-58,93-95) without its last
+ *                      step, the colour table: which of six things each cell shows, per view, plus the per-snake facts.
  *   msnake_get_stats <- the epinfobuf aggregation in ppo_multi_agent.py:288,331,366-390
  *
  * RNG contract (shared with oracle/ and tests/golden): draw i of global env g is word (i & 3) of
@@ -291,6 +293,36 @@ int msnake_space_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_
  * through a second handle); dim, n_snakes, n_fruits or rules differ; the devices differ; src_index_dev NULL with
  * different env counts. */
 int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_index_dev, void* stream);
+
+/* The observation as cell codes, computed on the device from the current state of every env: what the reference's
+ * frame (get_ob_for_snake / get_multi_snake_ob, snake_multiple_test.py:35-58,93-95) shows before its colour table is
+ * applied.  The yardstick is the reference's frame, not msnake_render: the two frames agree on every state that play
+ * reaches, but msnake_render paints a snake's body and head in one pass, so on a hand-installed state whose body has a
+ * duplicate stacked on its own head cell it can show the body colour where the reference shows the head.
+ * `views` is what the RGB frame has (C / 3 of msnake_obs_shape): 3 for snake_env and adversarial whatever n_snakes is,
+ * n_snakes for new_world.
+ * cells_dev: uint8 [num_envs][V][dim][dim], V = popcount(view_mask), the planes of the selected views in ascending view
+ * order.  Plane entry [c0][c1] is cell (c0, c1), the cell that frame pixel [c0 + 1][c1 + 1] shows; there is no wall
+ * border.  No alignment is required (a 19 x 19 plane is 361 bytes, so blocks start at odd addresses).  The codes in the
+ * plane of view v:
+ *   0 empty   1 fruit   2 body of snake v   3 head of snake v   4 body of another snake   5 head of another snake
+ * Paint order, the frame's; a later paint wins: every entry of the state's fruit list first (adversarial: the complete
+ * list); then, for snake i = 0, 1, ... in turn, all of its body cells (duplicates included), then its piece 0 as the
+ * head.  A snake with an empty body paints nothing; under new_world a snake whose alive bit is 0 paints nothing; a
+ * coordinate outside [0, dim)^2 (heads and adversarial fruits can sit at -1 or dim) paints nothing; in a view v >=
+ * n_snakes every snake is "other".
+ * Equivalence to the frame: decoding the obs_scale-1 RGB frame through the six-colour table (black 0; 255,0,0 fruit;
+ * 0,204,0 / 191,242,191 own body / head; 0,51,204 / 128,154,230 another's body / head) and cutting off the wall border
+ * gives these planes byte for byte.  The handle's obs_scale plays no part.
+ * snakes_dev (may be NULL): int32 [num_envs][n_snakes][8], 4-byte aligned (MSNAKE_E_ALIGN otherwise); row s holds
+ *   len, head c0, head c1, v0, v1, grow_to, alive, in_dead
+ * of snake s, the values msnake_get_state returns in those words with piece 0 as the head; the head is (-2, -2) for an
+ * empty body.  The rows are not rotated per view.
+ * Like msnake_scripted_actions the call only reads the handle's state (no random numbers are drawn, the Philox counter
+ * stays), allocates nothing, does not synchronise and adds nothing to env_steps; asynchronous on `stream`, and it can be
+ * captured into a HIP graph behind a step.  MSNAKE_E_ARG, before any device work: a view_mask bit >= views; view_mask
+ * != 0 with cells_dev NULL; view_mask == 0 with cells_dev non-NULL; nothing to write (view_mask 0 and snakes_dev NULL). */
+int msnake_render_cells(msnake_handle h, uint32_t view_mask, uint8_t* cells_dev, int32_t* snakes_dev, void* stream);
 
 /* Copy the aggregate statistics to the host.  Blocking: waits for the device (every step issued so
  * far, on any stream) before it sums the per-env totals.  episodes / ep_len_sum / ep_return_sum /

@@ -492,6 +492,21 @@ int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_in
     return MSNAKE_OK;
 }
 
+int msnake_render_cells(msnake_handle h, uint32_t view_mask, uint8_t* cells_dev, int32_t* snakes_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    const int views = h->p.views;
+    if (view_mask >> views) return fail(MSNAKE_E_ARG, "msnake_render_cells: view_mask 0x%x has a bit >= views=%d", view_mask, views);
+    if (view_mask && !cells_dev) return fail(MSNAKE_E_ARG, "msnake_render_cells: cells_dev is NULL but view_mask is 0x%x", view_mask);
+    if (!view_mask && cells_dev) return fail(MSNAKE_E_ARG, "msnake_render_cells: cells_dev is given but view_mask is 0");
+    if (!view_mask && !snakes_dev)
+        return fail(MSNAKE_E_ARG, "msnake_render_cells: nothing to write (view_mask 0 and snakes_dev is NULL)");
+    if ((uintptr_t)snakes_dev & 3) return fail(MSNAKE_E_ALIGN, "snakes_dev must be 4-byte aligned");
+    DeviceGuard guard(h->cfg.device);
+    hipError_t e = msnake::launch_cells(h->p, h->cfg.rules, view_mask, cells_dev, snakes_dev, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return MSNAKE_OK;
+}
+
 // ---- canonical state import / export.  The device packs / unpacks (msnake_state_*_kernel); the host
 //      only sizes buffers and copies.  Blocking: every call starts with a device synchronise. ----
 namespace {

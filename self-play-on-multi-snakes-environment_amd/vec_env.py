@@ -87,6 +87,29 @@ def normalize_copy_index(index, num_envs):
     return out
 
 
+def normalize_views(views, n_views):
+    """Selection of observation views for render_cells_device -> (view_mask, list of the selected views).
+
+    None = every view; an int = that view alone; otherwise a sequence of strictly ascending view indices (the planes
+    come out in ascending view order, so any other order would mislabel them); the empty sequence selects no plane."""
+    if views is None:
+        sel = list(range(n_views))
+    elif isinstance(views, (int, np.integer)) and not isinstance(views, (bool, np.bool_)):
+        sel = [int(views)]
+    else:
+        sel = list(views)
+        for v in sel:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"views must be None, an int or a sequence of ints, got {views!r}")
+        sel = [int(v) for v in sel]
+    for v in sel:
+        if not 0 <= v < n_views:
+            raise ValueError(f"view indices must lie in [0, {n_views}), got {v}")
+    if any(b <= a for a, b in zip(sel, sel[1:])):
+        raise ValueError(f"views must be strictly ascending (the planes are written in ascending view order), got {sel}")
+    return sum(1 << v for v in sel), sel
+
+
 # constructor arguments that may differ between the two handles of a device-side copy (include/msnake.h,
 # msnake_copy_envs): what MultiSnakeVecEnv.clone() lets a caller override
 CLONE_OVERRIDES = ("record_policy", "envs_per_block", "obs_scale", "auto_reset", "max_steps", "seed", "env_id_base")
@@ -139,7 +162,7 @@ class LazyInfos:
 class MultiSnakeVecEnv:
     """num_envs independent multi-snake games stepped in lockstep by one HIP kernel launch."""
 
-    metadata = {"render.modes": ["rgb_array"]}
+    metadata = {"render.modes": ["rgb_array", "cells"]}
 
     def __init__(self, num_envs, dim=19, n_snakes=3, n_fruits=None, rules="snake_env", seed=0,
                  env_id_base=0, device=None, max_steps=2000, auto_reset=True, obs_scale=1,
@@ -228,6 +251,7 @@ class MultiSnakeVecEnv:
         self._scripted_fn = self._L.msnake_scripted_actions
         self._scripted_out = None  # scripted_actions_device(out=None): allocated on first use
         self._space_fn = self._L.msnake_space_actions
+        self._cells_fn = self._L.msnake_render_cells
 
     # ------------------------------------------------------------------ device-side API
     def _stream(self):
@@ -395,6 +419,52 @@ class MultiSnakeVecEnv:
             _capi.check(rc, "msnake_space_actions")
         return out
 
+    @property
+    def cells_shape(self):
+        """(views, dim, dim): one env's planes of render_cells_device() with every view selected."""
+        return (self.obs_shape[2] // 3, int(self.cfg.dim), int(self.cfg.dim))
+
+    def render_cells_device(self, views=None, out=None, snakes_out=None, snakes=False):
+        """The observation as cell codes (msnake_render_cells): uint8 [num_envs, V, dim, dim], one plane per selected view
+        in ascending view order, entry [c0, c1] = what frame pixel [c0 + 1, c1 + 1] of that view shows: 0 empty, 1 fruit,
+        2 / 3 body / head of the view's own snake, 4 / 5 body / head of another snake.  `views`: None = every view of
+        the frame (cells_shape[0]), an int, or a strictly ascending sequence; the empty sequence writes no plane.
+        `snakes_out`, an int32 [num_envs, n_snakes, 8] device tensor (snakes=True: a fresh one), gets every snake's
+        (len, head c0, head c1, v0, v1, grow_to, alive, in_dead).  `out` must be a contiguous uint8 tensor of the shape
+        above on this device; it needs no alignment.  Returns the planes, (planes, table) when the table was asked for,
+        or the table alone when no view is selected; nothing is synchronised.  Draws no random numbers and changes no
+        env state."""
+        torch = self._torch
+        n_views, dim = self.cells_shape[0], self.cells_shape[1]
+        mask, sel = normalize_views(views, n_views)
+        if snakes_out is None and snakes:
+            with torch.cuda.device(self.device):
+                snakes_out = torch.empty((self.num_envs, self.n_snakes, 8), dtype=torch.int32, device=self.device)
+        elif snakes_out is not None:
+            want = (self.num_envs, self.n_snakes, 8)
+            if (not isinstance(snakes_out, torch.Tensor) or snakes_out.dtype != torch.int32 or snakes_out.device != self.device or
+                    tuple(snakes_out.shape) != want or not snakes_out.is_contiguous()):
+                raise ValueError(f"snakes_out must be a contiguous int32 tensor of shape {want} on {self.device}")
+        want = (self.num_envs, len(sel), dim, dim)
+        if not sel:
+            if out is not None:
+                raise ValueError("out is given but no view is selected")
+            if snakes_out is None:
+                raise ValueError("nothing to write: no view is selected and no table is asked for (snakes=True / snakes_out)")
+        elif out is None:
+            with torch.cuda.device(self.device):
+                out = torch.empty(want, dtype=torch.uint8, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device or
+              tuple(out.shape) != want or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {want} on {self.device}")
+        rc = self._cells_fn(self._h, mask, out.data_ptr() if sel else None,
+                            snakes_out.data_ptr() if snakes_out is not None else None, self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_render_cells")
+        if not sel:
+            return snakes_out
+        return out if snakes_out is None else (out, snakes_out)
+
     def rollout_device(self, tape, persistent=True, keep_obs=True):
         """T lockstep steps from an action tape int32 cuda [T, num_envs, >= n_snakes] in ONE call.
 
@@ -522,7 +592,11 @@ class MultiSnakeVecEnv:
         return self.step_wait()
 
     def render(self, mode="rgb_array"):
-        return self.render_device().cpu().numpy()  # always a fresh array
+        """mode "rgb_array": the frames of every env; mode "cells": env 0's cell-code planes, uint8 [views, dim, dim]
+        (render_cells_device), as the host convenience.  Always a fresh array."""
+        if mode == "cells":
+            return self.render_cells_device()[0].cpu().numpy()
+        return self.render_device().cpu().numpy()
 
     def close(self):
         if not self.closed and self._h:
