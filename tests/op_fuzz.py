@@ -1,16 +1,32 @@
-"""Model-based differential test of every entry point on ONE handle: a seeded random sequence of operations goes to a
-handle and to the CPU oracle side by side, and after every operation everything the operation returns is compared and
-everything it must leave alone is checked.  Integer and byte arithmetic throughout: every comparison is bit-exact.
+"""Model-based differential test of every entry point on ONE handle, and of the state two handles hand each other: a
+seeded random sequence of operations goes to a handle (and its twin) and to the CPU oracle side by side, and after every
+operation everything the operation returns is compared and everything it must leave alone is checked.  Integer and byte
+arithmetic throughout: every comparison is bit-exact.
 
 What this is for: the state one kernel leaves in HBM for a DIFFERENT kernel to pick up (parked Philox draws, the
 finished bit, the overflow ring's head, chunk 0 of the adversarial fruit list, the persistent kernel's 16-step batches,
-the device-side episode totals), and a state made on one record policy and continued on the other.
+the device-side episode totals), a state made on one record policy and continued on the other, a state the copy kernel
+wrote (ring rewritten from position 0, parked draws zeroed, totals kept), and a state that changes hands between the
+step kernels compiled for the handle's shape and the generic ones.
 
   gen_ops(cfg, seed, n_ops)  pure host: a list of plain-dict operations, every random choice made (bulk data such as
                              action tensors is named by a seed in the op and derived from it alone)
-  run(adapter, cfg, ops)     drives an adapter and an Oracle; ops[:k] replays a failure up to the op where it appeared
+  run(adapter, cfg, ops)     drives an adapter and two Oracles; ops[:k] replays a failure up to the op where it appeared
   HipAdapter                 the library (msnake.MultiSnakeVecEnv and, for NULL outputs / strides, its C entry points)
-  OracleAdapter              the same interface over a second Oracle (no GPU needed); fault= injects one silent defect
+  OracleAdapter              the same interface over further Oracles (no GPU needed); fault= injects one silent defect
+
+The twin: the adapter owns a second handle of the same shape (num_envs, dim, n_snakes, n_fruits, rules, max_steps,
+auto_reset, obs_scale) that is the neighbouring shard (env_id_base + num_envs) with another seed, the opposite record
+policy where the rule set has two, and another envs_per_block (twin_cfg); it is reset once at open.  The driver keeps
+a Model for each.  `fork` copies envs between the two with msnake_copy_envs (either direction; the identity, a
+permutation, a sparse map with duplicates and negative entries, or one with entries >= num_envs, which the header
+defines: untouched, errors + 1), then compares BOTH handles' states in full and both stats().  `swap` exchanges the
+roles: everything after it, every older op kind included, runs on the handle the copy kernel last wrote, on its
+record policy and launch shape.  `space` (msnake_space_actions) and `cells` (msnake_render_cells) change no state and
+go anywhere; their outputs are compared with tests/space_play.py and tests/cells_play.py on the oracle's states.
+
+Entry points not fuzzed, host-only and tested elsewhere: msnake_state_blob_info, msnake_kernel_name and
+msnake_kernel_name_for_config (the GPU adapter asks msnake_kernel_name once at open, as a precondition).
 
 A plain helper module (like scripted_play), imported by tests/test_op_fuzz_host.py and tests/test_op_fuzz_gpu.py.
 
@@ -23,23 +39,31 @@ import struct
 
 import numpy as np
 
+import cells_play as cp
 import scripted_play as sp
+import space_play as spp
 
 GUARD, SENT = 64, 0xA5
 ROLLOUT_STEPS = (1, 2, 15, 16, 17, 31, 32, 33, 48)
 INVALID_ACTIONS = (-1, 5, 7)      # as tools/gen_golden.py random_configs mixes them in
 OBS_CAP = 400 << 20               # no single observation buffer above this many bytes
 KINDS = ("step", "step_tape", "rollout", "reset_all", "reset_mask", "render", "scripted", "checkpoint_self", "set_words",
-         "migrate", "stats")
+         "migrate", "stats", "space", "cells", "fork", "swap")
 PAIR_CLASS = {"step": "S", "step_tape": "S", "rollout": "R", "reset_mask": "K", "checkpoint_self": "C", "set_words": "C",
-              "migrate": "M"}
-PAIR_CLASSES = "SRKCM"
+              "migrate": "M", "fork": "F"}     # (swap has no class of its own: it completes the F node in front of it)
+PAIR_CLASSES = "SRKCMF"
+FORK_MODES = ("identity", "perm", "sparse", "oob")
+FORK_DIRS = ("main<-twin", "twin<-main")
+SPEC_SHAPES = ((19, 3), (19, 2), (10, 1))      # boards x snakes the step kernels are compiled for (include/msnake.h)
 RULE_NAMES = {0: "snake_env", 1: "new_world", 2: "adversarial"}
 
 
 # ----------------------------------------------------------------------------------------------- configurations
+BIG_N_OPS = 66   # what gen_ops fixes for the batch above 8 192 envs (spine, long-body block, quotas), nothing random on top
+
+
 def _cfg(name, rules, dim, ns, n, max_steps, auto_reset, scale=1, nf=None, seed=1, base=0, rec="full", epb=0,
-         store="auto", n_ops=60, seeds=(1, 2, 3)):
+         store="auto", n_ops=84, seeds=(1, 2, 3)):
     return dict(name=name, rules=sp.RULES[rules], dim=dim, n_snakes=ns, n_fruits=ns if nf is None else nf, num_envs=n,
                 max_steps=max_steps, auto_reset=bool(auto_reset), obs_scale=scale, seed=seed, env_id_base=base,
                 tuning=dict(record_policy=rec, envs_per_block=epb, obs_store_policy=store), n_ops=n_ops, seeds=tuple(seeds))
@@ -48,7 +72,9 @@ def _cfg(name, rules, dim, ns, n, max_steps, auto_reset, scale=1, nf=None, seed=
 # Between them (not as a cross product): the three rule sets; 1..3 snakes and 4 for new_world; boards 3x3 .. 19x19;
 # max_steps 5..12; auto reset on and off; obs_scale 1 and 4; a start on the full and on the short record; batches of
 # 1, 130, 257, 333, 777 envs; non-zero env_id_base and seeds with a non-zero high word; one batch above 8 192 envs with
-# the launch shape the library picks itself (short record, 4 envs per workgroup) and a short sequence.
+# the launch shape the library picks itself (short record, 4 envs per workgroup) and a short sequence (the minimum that
+# holds the quotas of gen_ops); two 19x19 starts on the step kernels compiled for the handle's shape (S10x1 is the third
+# compiled shape), with env counts that are no multiple of the 8 envs per workgroup.
 CONFIGS = [
     _cfg("S3x2_n1", "snake_env", 3, 2, 1, 5, 1, seed=7, rec="full", epb=1),
     _cfg("S3x2", "snake_env", 3, 2, 130, 6, 0, seed=11, base=5, rec="short", epb=8),
@@ -61,7 +87,9 @@ CONFIGS = [
     _cfg("N6x4", "new_world", 6, 4, 130, 8, 1, nf=9, seed=37, rec="auto", epb=0),
     _cfg("N10x2_x4", "new_world", 10, 2, 100, 10, 0, scale=4, nf=4, seed=(1 << 40) | 41, base=9, rec="auto", epb=2),
     _cfg("N19x3", "new_world", 19, 3, 257, 12, 1, nf=3, seed=43, base=(1 << 32) + 6, rec="auto", epb=8),
-    _cfg("S19x3_big", "snake_env", 19, 3, 8201, 10, 1, seed=47, base=12, rec="auto", epb=0, n_ops=48, seeds=(1,)),
+    _cfg("S19x3_big", "snake_env", 19, 3, 8201, 10, 1, seed=47, base=12, rec="auto", epb=0, n_ops=BIG_N_OPS, seeds=(1,)),
+    _cfg("S19x3_spec", "snake_env", 19, 3, 130, 12, 1, seed=53, rec="full", epb=8, store="plain"),
+    _cfg("S19x2_spec", "snake_env", 19, 2, 65, 12, 1, seed=(7 << 32) | 59, base=(1 << 34) + 21, rec="full", epb=8, store="plain"),
 ]
 BY_NAME = {c["name"]: c for c in CONFIGS}
 
@@ -69,6 +97,23 @@ BY_NAME = {c["name"]: c for c in CONFIGS}
 def cases():
     """(cfg, seed) of every run of the GPU file (and so of the host file)."""
     return [(c, s) for c in CONFIGS for s in c["seeds"]]
+
+
+def twin_cfg(cfg):
+    """The configuration of the twin handle: the same shape, the neighbouring shard, another seed, the opposite record
+    policy where the rule set has two, another envs_per_block."""
+    t = dict(cfg["tuning"])
+    if cfg["rules"] != 1:
+        t["record_policy"] = "short" if effective_record(cfg, t) == "full" else "full"
+    t["envs_per_block"] = {0: 2, 1: 2, 2: 4, 4: 8, 8: 1}[t["envs_per_block"]]
+    return dict(cfg, seed=cfg["seed"] ^ 0x5A5A5A5A, env_id_base=cfg["env_id_base"] + cfg["num_envs"], tuning=t)
+
+
+def compiled_shape(cfg, tuning):
+    """The handle of this tuning steps with the kernels compiled for its shape (as msnake_create decides it; the host
+    file asks msnake_kernel_name_for_config for the configurations it counts this on)."""
+    return (cfg["rules"] == 0 and cfg["obs_scale"] == 1 and cfg["auto_reset"] and (cfg["dim"], cfg["n_snakes"]) in SPEC_SHAPES
+            and effective_record(cfg, tuning) == "full")
 
 
 def effective_record(cfg, tuning):
@@ -91,10 +136,11 @@ def row_bytes(cfg):
 
 # ----------------------------------------------------------------------------------------------- the generator
 def _euler(rng):
-    """A closed walk over the five classes of state-changing ops that takes every ordered pair (A, B), A == B included,
-    exactly once: 26 nodes (Hierholzer on the complete digraph with loops, edge order shuffled)."""
-    out_edges = {a: [PAIR_CLASSES[j] for j in rng.permutation(5)] for a in PAIR_CLASSES}
-    stack, walk = [PAIR_CLASSES[int(rng.integers(0, 5))]], []
+    """A closed walk over the six classes of state-changing ops that takes every ordered pair (A, B), A == B included,
+    exactly once: 37 nodes (Hierholzer on the complete digraph with loops, edge order shuffled)."""
+    k = len(PAIR_CLASSES)
+    out_edges = {a: [PAIR_CLASSES[j] for j in rng.permutation(k)] for a in PAIR_CLASSES}
+    stack, walk = [PAIR_CLASSES[int(rng.integers(0, k))]], []
     while stack:
         v = stack[-1]
         if out_edges[v]:
@@ -102,14 +148,15 @@ def _euler(rng):
         else:
             walk.append(stack.pop())
     walk.reverse()
-    assert len(walk) == 26
+    assert len(walk) == k * k + 1
     return walk
 
 
 class _Gen:
     def __init__(self, cfg, rng):
         self.cfg, self.rng = cfg, rng
-        self.tuning = dict(cfg["tuning"])
+        self.tuning = dict(cfg["tuning"])                  # of the handle that is main right now
+        self.twin_tuning = dict(twin_cfg(cfg)["tuning"])   # ... and of the other one; swap() exchanges them
         self.n_c = 0
 
     def seed(self):
@@ -183,6 +230,30 @@ class _Gen:
     def stats(self):
         return dict(kind="stats", reset=bool(self.rng.random() < 0.4))
 
+    def space(self):
+        ns, r = self.cfg["n_snakes"], self.rng
+        bits = int(r.integers(0, 1 << ns))
+        safe, space = bool(r.random() < 0.5), bool(r.random() < 0.7)
+        if bits == 0 and not (safe or space):
+            safe, space = bool(r.random() < 0.5), True
+        return dict(kind="space", snakes=bits, stride=self.stride(), safe=safe, space=space, seed=self.seed())
+
+    def cells(self):
+        nv, r = cp.n_views(self.cfg["rules"], self.cfg["n_snakes"]), self.rng
+        how = self.pick(["all", "one", "any", "table"])
+        mask = {"all": (1 << nv) - 1, "one": 1 << int(r.integers(0, nv)), "any": int(r.integers(1, 1 << nv)), "table": 0}[how]
+        return dict(kind="cells", views=mask, table=bool(mask == 0 or r.random() < 0.5))
+
+    def fork(self, form, mode):
+        """One F node: fork(main<-twin), or fork(twin<-main) and the swap that makes the written handle the main one."""
+        if form == "m":
+            return [dict(kind="fork", dir="main<-twin", mode=mode, seed=self.seed())]
+        return [dict(kind="fork", dir="twin<-main", mode=mode, seed=self.seed()), self.swap()]
+
+    def swap(self):
+        self.tuning, self.twin_tuning = self.twin_tuning, self.tuning
+        return dict(kind="swap")
+
     def of_class(self, c, n_step):
         if c == "S":
             return self.step() if n_step[0] < 3 or self.rng.random() < 0.5 else self.step_tape()
@@ -195,47 +266,81 @@ class _Gen:
 def gen_ops(cfg, seed, n_ops):
     """The op list of (cfg, seed).  Built so that the coverage conditions of tests/test_op_fuzz_host.py hold by
     construction where they can: a spine that takes every ordered pair of state-changing op classes (cut into segments
-    that re-enter on the node they left, so no pair is lost), a block `set_words(long body) -> migrate ->
-    checkpoint_self -> step` where the board allows a body over 64 cells, at least three ops of every kind, migrations
-    that flip the record policy every time -- and random ops (weights below) for the rest, in the gaps."""
+    that re-enter on the node they left, so no pair is lost), in which every F node leaves the ACTIVE handle freshly
+    written by the copy kernel -- fork(main<-twin), or fork(twin<-main) and a swap; the first of them the latter, so the
+    twin first receives played state; the index modes in turn; a stats() behind the first out-of-range fork --, a block
+    `set_words(long body) -> fork(twin<-main, identity) + swap -> migrate -> checkpoint_self -> step` where the board
+    allows a body over 64 cells, a block `(migrate onto the full record) -> step, rollout, step_tape with stride ==
+    n_snakes -> step, rollout with a padded stride` where the start is on the step kernels compiled for the shape, at
+    least three ops of every kind (one each of space and cells above 8 192 envs, where the NumPy flood fill costs
+    seconds), migrations that flip the record policy of the handle they act on every time -- and random ops (weights
+    below) for the rest, in the gaps."""
     rng = np.random.default_rng([0x6F70, int(seed), cfg["rules"], cfg["dim"], cfg["n_snakes"], cfg["num_envs"]])
     g = _Gen(cfg, rng)
     walk = _euler(rng)
-    cuts = sorted(int(x) for x in rng.choice(np.arange(3, 23), 2, replace=False))
+    cuts = sorted(int(x) for x in rng.choice(np.arange(3, len(walk) - 3), 2, replace=False))
     segments = [walk[:cuts[0] + 1], walk[cuts[0]:cuts[1] + 1], walk[cuts[1]:]]
-    n_fixed = 1 + sum(len(s) for s in segments) + (4 if long_body_allowed(cfg) else 0)
-    quota = ["render"] * 3 + ["scripted"] * 3 + ["stats"] * 3 + ["reset_all"] * 2 + ["step_tape"] * 3 + ["set_words"]
+    n_f = sum(seg.count("F") for seg in segments)
+    forms = ["t"] + [("m", "t")[int(j) % 2] for j in rng.permutation(n_f - 1)]      # both directions, the first twin<-main
+    modes = [FORK_MODES[int(j)] for j in rng.permutation(4)]
+    modes = [modes[j % 4] for j in range(n_f)]                                      # every index mode, in turn
+    first_oob = modes.index("oob")
+    spec = compiled_shape(cfg, cfg["tuning"])
+    n_fixed = 1 + sum(len(s) for s in segments) + forms.count("t") + 1 + (6 if long_body_allowed(cfg) else 0) + (6 if spec else 0)
+    few = cfg["num_envs"] > 8192
+    quota = ["render"] * 3 + ["scripted"] * 3 + ["stats"] * 2 + ["reset_all"] * 2 + ["step_tape"] * 3 + ["set_words"] + \
+            ["space"] * (1 if few else 3) + ["cells"] * (1 if few else 3)
     weights = dict(step=5, step_tape=2, rollout=4, reset_all=1, reset_mask=3, render=1, scripted=3, checkpoint_self=2,
-                   set_words=2, migrate=2, stats=1)
+                   set_words=2, migrate=2, stats=1, space=2, cells=2)
     if not cfg["auto_reset"]:     # finished envs step no further: reset them more often
         weights["reset_mask"] = 7
+    assert n_ops >= n_fixed + len(quota), (cfg["name"], seed, n_ops, n_fixed + len(quota))
     names = list(weights)
     p = np.array([weights[k] for k in names], float)
-    extra = quota + [names[int(i)] for i in rng.choice(len(names), max(0, n_ops - n_fixed - len(quota)), p=p / p.sum())]
+    extra = quota + [names[int(i)] for i in rng.choice(len(names), n_ops - n_fixed - len(quota), p=p / p.sum())]
     extra = [extra[int(i)] for i in rng.permutation(len(extra))]
-    quiet = [k for k in extra if k in ("render", "scripted", "stats")]       # change no state: go anywhere
-    loud = [k for k in extra if k not in ("render", "scripted", "stats")]    # go into the gaps between segments
+    QUIET = ("render", "scripted", "stats", "space", "cells")                # change no state: go anywhere
+    quiet = [k for k in extra if k in QUIET]
+    loud = [k for k in extra if k not in QUIET]                              # go into the gaps between segments
     gaps = [[], [], []]
     for k in loud:
         gaps[int(rng.integers(0, 3))].append(k)
-    # the order the ops are MADE in is the order they run in (migrate tracks the tuning it leaves)
-    plan = []
+    # the order the ops are MADE in is the order they run in (migrate and swap track the tunings they leave)
+    plan, k_f = [], 0
     for seg, gap in zip(segments, gaps):
-        plan += [("class", c) for c in seg] + [("kind", k) for k in gap]
+        for c in seg:
+            if c == "F":
+                plan.append(("fork", (forms[k_f], modes[k_f], k_f == first_oob)))
+                k_f += 1
+            else:
+                plan.append(("class", c))
+        plan += [("kind", k) for k in gap]
         if seg is segments[0] and long_body_allowed(cfg):
             plan += [("long", None)]
+        if seg is segments[1] and spec:
+            plan += [("spec", None)]
     for k in quiet:
         plan.insert(int(rng.integers(0, len(plan) + 1)), ("kind", k))
     ops, n_step = [dict(kind="reset_all", gen_seed=int(seed), cfg=cfg["name"])], [0]
+    after_f = False                       # the S node behind an F node is a plain step (not a tape)
     for what, arg in plan:
         if what == "class":
-            op = g.of_class(arg, n_step)
+            op = g.step() if arg == "S" and after_f else g.of_class(arg, n_step)
             n_step[0] += op["kind"] == "step"
             ops.append(op)
+        elif what == "fork":
+            ops += g.fork(arg[0], arg[1]) + ([dict(kind="stats", reset=False)] if arg[2] else [])
         elif what == "long":
-            ops += [g.set_words(edit="long"), g.migrate(), g.checkpoint_self(), g.step()]
+            ops += [g.set_words(edit="long")] + g.fork("t", "identity") + [g.migrate(), g.checkpoint_self(), g.step()]
+        elif what == "spec":      # on the compiled kernels: three stepping ops that run them, two that fall back for the call
+            ns = cfg["n_snakes"]
+            ops += [g.checkpoint_self() if compiled_shape(cfg, g.tuning) else g.migrate()]
+            ops += [dict(g.step(), stride=ns), dict(g.rollout(), stride=ns), dict(g.step_tape(), stride=ns),
+                    dict(g.step(), stride=ns + 2), dict(g.rollout(), stride=ns + 1)]
         else:
             ops.append(getattr(g, arg)())
+        after_f = what == "fork" or (after_f and what == "kind" and arg in QUIET)
+    assert len(ops) == n_ops
     return ops
 
 
@@ -290,7 +395,7 @@ class Totals:
     """msnake_get_stats as a model: an episode counts on the step it ends and, while its env stays finished, only once."""
 
     def __init__(self):
-        self.episodes = self.ep_len_sum = self.ep_return_sum = self.env_steps = 0
+        self.episodes = self.ep_len_sum = self.ep_return_sum = self.env_steps = self.errors = 0
 
     def count(self, done, fin, er, el):
         new = (done != 0) & ~fin
@@ -300,11 +405,11 @@ class Totals:
 
     def dict(self):
         return {"episodes": self.episodes, "ep_len_sum": self.ep_len_sum, "ep_return_sum": self.ep_return_sum,
-                "env_steps": self.env_steps, "errors": 0}
+                "env_steps": self.env_steps, "errors": self.errors}
 
 
 class Model:
-    """An Oracle behind the op interface: payloads as the library must write them (SENT where it must not write), the
+    """An Oracle behind the op interface (one per handle: cfg carries the handle's seed and env_id_base): payloads as the library must write them (SENT where it must not write), the
     finished bits and the episode totals -- all from the oracle's outputs alone."""
 
     def __init__(self, cfg, hook=None):
@@ -406,6 +511,56 @@ class Model:
             out["safe"] = np.array([sp.np_safe_mask(st, dim, ns) for st in states], np.uint8).reshape(self.n, ns)
         return out
 
+    def space(self, bits, act, want_safe, want_space):
+        """space_play's counts and space_greedy (eps = 0), and the NumPy safe mask, on the oracle's canonical states."""
+        dim, ns = self.cfg["dim"], self.ns
+        states = [self.state(e) for e in range(self.n)]
+        out = {}
+        if bits:
+            want = np.array([spp.space_greedy(st, dim, ns, None, 0.0) for st in states], np.int32).reshape(self.n, ns)
+            act = act.copy()
+            for s in range(ns):
+                if bits >> s & 1:
+                    act[:, s] = want[:, s]
+            out["act"] = act
+        if want_safe:
+            out["safe"] = np.array([sp.np_safe_mask(st, dim, ns) for st in states], np.uint8).reshape(self.n, ns)
+        if want_space:
+            out["space"] = np.array([spp.np_space(st, dim, ns) for st in states]).astype(np.uint16).reshape(self.n, ns, 4)
+        return out
+
+    def cells(self, mask, want_table):
+        """cells_play's planes of the selected views (ascending) and its table, on the oracle's canonical states; and
+        the header's equivalence claim on every one of these states: decode_frame of the oracle's own frame gives the
+        planes of every view."""
+        dim, ns, rules = self.cfg["dim"], self.ns, self.cfg["rules"]
+        nv = cp.n_views(rules, ns)
+        states = [self.state(e) for e in range(self.n)]
+        planes = np.stack([cp.np_cells(st, dim, ns, rules, list(range(nv))) for st in states])
+        decoded = cp.decode_frame(self.ora.render(), list(range(nv)))
+        if not np.array_equal(decoded, planes):
+            e = int(np.flatnonzero((decoded != planes).reshape(self.n, -1).any(1))[0])
+            raise Mismatch(f"op_fuzz: decode_frame(oracle frame) differs from np_cells in env {e}: state {states[e]}")
+        out = {}
+        views = [v for v in range(nv) if mask >> v & 1]
+        if views:
+            out["cells"] = np.ascontiguousarray(planes[:, views])
+        if want_table:
+            out["table"] = np.stack([cp.np_snake_rows(st, ns) for st in states]).astype(np.int32)
+        return out
+
+    def all_words(self):
+        return [self.words(e) for e in range(self.n)]
+
+    def copy_from(self, src_words, idx):
+        """msnake_copy_envs on the oracle: export from the source (all of it read first: `src_words`), import here.  The
+        totals stay; an entry >= the source's env count leaves the env alone and counts one error."""
+        for e, i in enumerate(range(self.n) if idx is None else [int(i) for i in idx]):
+            if i >= len(src_words):
+                self.totals.errors += 1
+            elif i >= 0:
+                self.install(e, src_words[i])
+
 
 # ----------------------------------------------------------------------------------------------- adapters
 class OracleAdapter:
@@ -414,14 +569,20 @@ class OracleAdapter:
       "ctr_lag"      after a rollout, an env's draw counter is re-installed one lower
       "fruit_moved"  after a migrate, a fruit of one env lies on another free cell
       "fin_dropped"  a checkpoint_self drops the finished bit of one finished env
-      "double_count" one finished episode is counted twice in the totals"""
+      "double_count" one finished episode is counted twice in the totals
+      "fork_row_shifted"         a fork gives one destination env the state of source index + 1
+      "fork_touched_unselected"  a fork changes the draw counter of an env whose index entry is negative
+      "fork_totals_copied"       a fork makes the destination's episode total the source's
+      "space_off_by_one"         one reachable-space count is one too high
+      "cells_head_as_body"       one code 3 (own head) of a plane is 2 (own body)"""
 
     def __init__(self, fault=None):
         self.fault, self.fault_at, self.op_index = fault, None, -1
 
     def open(self, cfg):
-        self.cfg = cfg
-        self.m = Model(cfg)
+        self.cfg, self.cfg_tw = cfg, twin_cfg(cfg)      # of the main model and of the twin; swap() exchanges them
+        self.m, self.tw = Model(self.cfg), Model(self.cfg_tw)
+        self.tw.reset_all()
         self.kept = []
 
     def _due(self, kind):
@@ -466,14 +627,56 @@ class OracleAdapter:
     def scripted(self, policy, bits, act, want_safe):
         return self._wrap(self.m.scripted(policy, bits, act, want_safe))
 
+    def space(self, bits, act, want_safe, want_space):
+        out = self.m.space(bits, act, want_safe, want_space)
+        if want_space and self._due("space_off_by_one") and out["space"].any():
+            at = np.flatnonzero(out["space"].reshape(-1))
+            out["space"].reshape(-1)[at[len(at) // 2]] += 1
+            self.fault_at = self.op_index
+        return self._wrap(out)
+
+    def cells(self, mask, want_table):
+        out = self.m.cells(mask, want_table)
+        if "cells" in out and self._due("cells_head_as_body") and (out["cells"] == 3).any():
+            at = np.flatnonzero(out["cells"].reshape(-1) == 3)
+            out["cells"].reshape(-1)[at[len(at) // 2]] = 2
+            self.fault_at = self.op_index
+        return self._wrap(out)
+
+    def fork(self, to_main, idx):
+        dst, src = (self.m, self.tw) if to_main else (self.tw, self.m)
+        words, n = src.all_words(), self.cfg["num_envs"]
+        plain = np.arange(n) if idx is None else np.asarray(idx, np.int64)
+        if self._due("fork_row_shifted"):
+            ok = [e for e in range(n) if 0 <= plain[e] < n - 1 and not np.array_equal(words[plain[e]], words[plain[e] + 1])]
+            if ok:
+                plain = plain.copy()
+                plain[ok[len(ok) // 2]] += 1
+                self.fault_at = self.op_index
+        dst.copy_from(words, plain)
+        if idx is not None and self._due("fork_touched_unselected") and (plain < 0).any():
+            e = int(np.flatnonzero(plain < 0)[0])
+            w = dst.words(e)
+            w[1] ^= 1
+            dst.install(e, w)
+            self.fault_at = self.op_index
+        if self._due("fork_totals_copied") and dst.totals.episodes != src.totals.episodes:
+            dst.totals.episodes = src.totals.episodes
+            self.fault_at = self.op_index
+
+    def swap(self):
+        self.m, self.tw = self.tw, self.m
+        self.cfg, self.cfg_tw = self.cfg_tw, self.cfg
+
     def get_words(self, e):
         return self.m.words(e)
 
     def set_words(self, e, words):
         self.m.install(e, words)
 
-    def get_blob(self):
-        return pack_blob(self.cfg, [self.m.words(e) for e in range(self.cfg["num_envs"])])
+    def get_blob(self, twin=False):
+        m = self.tw if twin else self.m
+        return pack_blob(self.cfg, m.all_words())
 
     def set_blob(self, blob, _migrating=False):
         words = [w.copy() for w in unpack_blob(blob)]
@@ -506,17 +709,18 @@ class OracleAdapter:
                     self.fault_at = self.op_index
                     break
 
-    def stats(self, reset):
-        out = self.m.totals.dict()
+    def stats(self, reset, twin=False):
+        m = self.tw if twin else self.m
+        out = m.totals.dict()
         if reset:
-            self.m.totals = Totals()
+            m.totals = Totals()
         return out
 
     def kept_stats(self):
         return list(self.kept)
 
     def close(self):
-        self.m = None
+        self.m = self.tw = None
 
 
 class HipAdapter:
@@ -529,14 +733,20 @@ class HipAdapter:
 
     def open(self, cfg):
         import torch
-        self.torch, self.cfg = torch, cfg
+        self.torch = torch
+        self.cfg, self.cfg_tw = cfg, twin_cfg(cfg)      # of the main handle and of the twin; swap() exchanges them
         self.stream = torch.cuda.Stream()
         self.kept = []
-        self.env = self._make(cfg["tuning"])
+        self.env = self._make(self.cfg, self.cfg["tuning"])
+        self.twin = self._make(self.cfg_tw, self.cfg_tw["tuning"])
+        for env, c in ((self.env, self.cfg), (self.twin, self.cfg_tw)):
+            if compiled_shape(c, c["tuning"]):     # or the case would test the generic kernels twice, silently
+                assert env.kernel_name().endswith(f", {c['dim']}>"), env.kernel_name()
+        with torch.cuda.stream(self.stream):
+            self.twin.reset_device()
 
-    def _make(self, tuning):
+    def _make(self, c, tuning):
         import msnake
-        c = self.cfg
         with self.torch.cuda.stream(self.stream):
             return msnake.MultiSnakeVecEnv(c["num_envs"], dim=c["dim"], n_snakes=c["n_snakes"], n_fruits=c["n_fruits"],
                                            rules=c["rules"], seed=c["seed"], env_id_base=c["env_id_base"],
@@ -628,14 +838,52 @@ class HipAdapter:
                        bufs["safe"][1] if want_safe else None, self._s())
             return self._back(bufs)
 
+    def space(self, bits, act, want_safe, want_space):
+        n, ns = self.cfg["num_envs"], self.cfg["n_snakes"]
+        with self.torch.cuda.stream(self.stream):
+            bufs = {}
+            if bits:
+                bufs["act"] = self._put(act)
+            if want_safe:
+                bufs["safe"] = self._new(n * ns)
+            if want_space:
+                bufs["space"] = self._new(2 * n * ns * 4)
+            ptr = lambda k: bufs[k][1] if k in bufs else None  # noqa: E731
+            self._call("msnake_space_actions", bits, ptr("act"), int(act.shape[1]) if bits else 0, ptr("safe"), ptr("space"),
+                       self._s())
+            return self._back(bufs)
+
+    def cells(self, mask, want_table):
+        n, ns, dim = self.cfg["num_envs"], self.cfg["n_snakes"], self.cfg["dim"]
+        with self.torch.cuda.stream(self.stream):
+            bufs = {}
+            if mask:
+                bufs["cells"] = self._new(n * bin(mask).count("1") * dim * dim)
+            if want_table:
+                bufs["table"] = self._new(4 * n * ns * 8)
+            ptr = lambda k: bufs[k][1] if k in bufs else None  # noqa: E731
+            self._call("msnake_render_cells", mask, ptr("cells"), ptr("table"), self._s())
+            return self._back(bufs)
+
+    def fork(self, to_main, idx):
+        from msnake import _capi
+        dst, src = (self.env, self.twin) if to_main else (self.twin, self.env)
+        with self.torch.cuda.stream(self.stream):
+            t = None if idx is None else self.torch.from_numpy(np.ascontiguousarray(idx, np.int32)).to(dst.device)
+            _capi.check(dst._L.msnake_copy_envs(dst._h, src._h, None if t is None else t.data_ptr(), self._s()), "msnake_copy_envs")
+
+    def swap(self):
+        self.env, self.twin = self.twin, self.env
+        self.cfg, self.cfg_tw = self.cfg_tw, self.cfg
+
     def get_words(self, e):
         return self.env.get_state_words(e)
 
     def set_words(self, e, words):
         self.env.set_state_words(e, words)
 
-    def get_blob(self):
-        return self.env.get_state_all()
+    def get_blob(self, twin=False):
+        return (self.twin if twin else self.env).get_state_all()
 
     def set_blob(self, blob):
         self.env.set_state_all(blob)
@@ -645,20 +893,20 @@ class HipAdapter:
             self.kept.append(self.env)
         else:
             self.env.close()
-        self.env = self._make(tuning)
+        self.env = self._make(self.cfg, tuning)
         with self.torch.cuda.stream(self.stream):
             self.env.reset_device()        # a fresh handle is reset, then takes the blob (as a checkpoint restore does)
         self.env.set_state_all(blob)
 
-    def stats(self, reset):
-        return self.env.stats(reset=reset)
+    def stats(self, reset, twin=False):
+        return (self.twin if twin else self.env).stats(reset=reset)
 
     def kept_stats(self):
         return [e.stats() for e in self.kept]
 
     def close(self):
         self.stream.synchronize()
-        for e in self.kept + [self.env]:
+        for e in self.kept + [self.env, self.twin]:
             e.close()
         self.kept = []
 
@@ -671,14 +919,30 @@ class Mismatch(AssertionError):
 def new_cov():
     return dict(kinds={k: 0 for k in KINDS}, migrate_dirs={}, pairs=set(), stepping=0, with_end=0, with_respawn=0,
                 rollout_cross16_end=0, wraps=0, long_migrate=0, long_checkpoint=0, fin_across=0, resets_of_finished=0,
-                episodes=0, env_steps=0)
+                episodes=0, env_steps=0, fork_dirs={d: 0 for d in FORK_DIRS}, fork_modes={m: 0 for m in FORK_MODES},
+                fork_dst_finished=0, fork_src_finished=0, fork_src_long=0, stats_saw_errors=0,
+                after_fork={"step": 0, "rollout": 0, "reset_mask": 0}, compiled_steps=0, fallback_steps=0,
+                to_generic=0, to_compiled=0)
+
+
+def max_body(words):
+    """The longest body of an env's canonical words."""
+    k, out = 8 + 2 * int(words[6]), 0
+    for _ in range(int(words[7]) & 0xFF):
+        out = max(out, int(words[k]))
+        k += 6 + 2 * int(words[k])
+    return out
 
 
 class _Driver:
     def __init__(self, adapter, cfg, count):
         self.a, self.cfg, self.count = adapter, cfg, count
         self.n, self.ns = cfg["num_envs"], cfg["n_snakes"]
-        self.m = Model(cfg, hook=self._on_step if count else None)
+        self.m = Model(cfg, hook=self._on_step if count else None)             # of the handle that is main right now
+        self.tw = Model(twin_cfg(cfg), hook=self._on_step if count else None)  # ... and of the other one
+        self.tw.reset_all()
+        self.tuning, self.tuning_tw = dict(cfg["tuning"]), dict(twin_cfg(cfg)["tuning"])
+        self.prev_kind = None
         self.cov = new_cov()
         self.touched = []                 # envs set_words installed into (most recent last): always in the sample
         self.pending = None               # actions a scripted op filled, for the next step
@@ -688,7 +952,7 @@ class _Driver:
         self.watch = list(range(min(self.n, 128)))   # envs whose draw counter / fruit count is read around every step (coverage)
         self.seen_r = np.zeros(self.n, bool)
         self.seen_c = np.zeros(self.n, bool)
-        self.ctr_of = {}
+        self.ctr_of, self.ctr_of_tw = {}, {}     # (per handle, like seen_r / seen_c below: they follow a swap)
 
     # ---- failure message
     def fail(self, i, op, what, env=None, detail=""):
@@ -716,7 +980,8 @@ class _Driver:
 
     def _sizes(self, stride=0):
         rb = row_bytes(self.cfg)
-        return {"obs": rb, "final": rb, "trunc": 1, "rew": 4, "done": 1, "info": 16, "act": 4 * max(stride, 1), "safe": self.ns}
+        return {"obs": rb, "final": rb, "trunc": 1, "rew": 4, "done": 1, "info": 16, "act": 4 * max(stride, 1), "safe": self.ns,
+                "space": 8 * self.ns, "cells": 1, "table": 32 * self.ns}
 
     # ---- coverage hooks (count=True only; numbers of the oracle alone)
     def _ctr(self, e):
@@ -743,6 +1008,10 @@ class _Driver:
     def _end_stepping(self, op):
         cov = self.cov
         cov["stepping"] += 1
+        if compiled_shape(self.cfg, self.tuning):     # stride == n_snakes runs compiled, a padded one the generic fallback
+            cov["compiled_steps" if self._stride == self.ns else "fallback_steps"] += 1
+        if self.prev_kind == "fork" and op["kind"] in cov["after_fork"]:
+            cov["after_fork"][op["kind"]] += 1
         cov["with_end"] += self._ended
         cov["with_respawn"] += self._respawn
         if op["kind"] == "rollout" and op["n_steps"] > 16 and self._ended:
@@ -760,6 +1029,7 @@ class _Driver:
             act, self.pending = self.pending, None
         else:
             act = make_actions(self.cfg, op["seed"], (self.n, op["stride"]))
+        self._stride = int(act.shape[1])
         self._begin_stepping()
         want = self.m.step(act, op["obs"])
         self.eq(i, op, self.a.step(act, op["obs"]), want, self._sizes())
@@ -769,6 +1039,7 @@ class _Driver:
         tape = make_actions(self.cfg, op["seed"], (op["n_steps"], self.n, op["stride"]))
         inplace = op.get("inplace", False)
         fin_before = self.m.fin.copy()
+        self._stride = op["stride"]
         self._begin_stepping()
         want = self.m.tape(tape, op["obs"], inplace)
         self.eq(i, op, self.a.tape(tape, persistent, op["obs"], inplace), want, self._sizes())
@@ -789,6 +1060,7 @@ class _Driver:
                (fin & (rs.random(self.n) < op["p_fin"]))
         mask = np.where(mask, np.array([1, 2, 0x80, 0xFF], np.uint8)[np.arange(self.n) % 4], 0).astype(np.uint8)
         self.cov["resets_of_finished"] += int((fin & (mask != 0)).sum())
+        self.cov["after_fork"]["reset_mask"] += self.prev_kind == "fork"
         want = self.m.reset_mask(mask, op["obs"], op["final"], op["trunc"])
         self.eq(i, op, self.a.reset_mask(mask, op["obs"], op["final"], op["trunc"]), want, self._sizes())
 
@@ -798,6 +1070,94 @@ class _Driver:
         self.eq(i, op, self.a.scripted(op["policy"], op["snakes"], act, op["safe"]), want, self._sizes(op["stride"]))
         if op["policy"] is not None:
             self.pending = want["act"]
+
+    def op_space(self, i, op):
+        act = make_actions(self.cfg, op["seed"], (self.n, op["stride"]))
+        want = self.m.space(op["snakes"], act, op["safe"], op["space"])
+        self.eq(i, op, self.a.space(op["snakes"], act, op["safe"], op["space"]), want, self._sizes(op["stride"]))
+        if op["snakes"]:
+            self.pending = want["act"]
+
+    def op_cells(self, i, op):
+        sizes = dict(self._sizes(), cells=bin(op["views"]).count("1") * self.cfg["dim"] ** 2)
+        self.eq(i, op, self.a.cells(op["views"], op["table"]), self.m.cells(op["views"], op["table"]), sizes)
+
+    def _fork_index(self, op):
+        """None (the identity), a permutation, a random map with duplicates, unused sources and at least n / 8 negative
+        entries, or such a map with a few entries >= num_envs."""
+        n, mode = self.n, op["mode"]
+        rs = np.random.default_rng([0xF02C, op["seed"]])
+        if mode == "identity":
+            return None
+        if mode == "perm":
+            return rs.permutation(n).astype(np.int32)
+        idx = rs.integers(-1, n, n).astype(np.int64)
+        idx[rs.choice(n, min(n, max(2, n // 8)) if n > 1 else int(rs.integers(0, 2)), replace=False)] = -1
+        if mode == "oob":
+            at = rs.choice(n, min(n, 3), replace=False)
+            idx[at] = np.array([n, n + 1, 2**31 - 1], np.int64)[:len(at)]
+        return idx.astype(np.int32)
+
+    def _words_fail(self, i, op, what, got_blob, want):
+        got = unpack_blob(got_blob)
+        if len(got) != len(want):
+            self.fail(i, op, f"num_envs of the blob of {what} ({len(got)})")
+        for e, (g, w) in enumerate(zip(got, want)):
+            if not np.array_equal(g, w):
+                self.fail(i, op, f"state of {what} after the copy", env=e, detail=f"got words {list(g)[:40]} want {list(w)[:40]}")
+
+    def op_fork(self, i, op):
+        to_main = op["dir"] == "main<-twin"
+        dst, src = (self.m, self.tw) if to_main else (self.tw, self.m)
+        idx = self._fork_index(op)
+        s0, d0 = src.all_words(), dst.all_words()
+        plain = np.arange(self.n) if idx is None else idx.astype(np.int64)
+        sel = (plain >= 0) & (plain < self.n)
+        cov = self.cov
+        cov["fork_dirs"][op["dir"]] += 1
+        cov["fork_modes"][op["mode"]] += 1
+        cov["fork_dst_finished"] += int((dst.fin & sel).any())
+        cov["fork_src_finished"] += int(src.fin[plain[sel]].any())
+        cov["fork_src_long"] += int(any(max_body(s0[j]) > 64 for j in set(plain[sel].tolist())))
+        # the header's three statements, from the words of BEFORE the call: selected destination envs hold the source's,
+        # the others (negative and out-of-range entries) their own, and the source is unchanged
+        want = [s0[j] if ok else d0[e] for e, (j, ok) in enumerate(zip(plain.tolist(), sel.tolist()))]
+        dst.copy_from(s0, plain)
+        for e, w in enumerate(dst.all_words()):
+            if not np.array_equal(w, want[e]):
+                self.fail(i, op, "the model's own copy (driver error)", env=e)
+        self.a.fork(to_main, idx)
+        self._words_fail(i, op, "the destination (" + ("main" if to_main else "twin") + ")", self.a.get_blob(twin=not to_main), want)
+        self._words_fail(i, op, "the source (" + ("twin" if to_main else "main") + ")", self.a.get_blob(twin=to_main), s0)
+        for twin, m in ((False, self.m), (True, self.tw)):
+            got = self.a.stats(False, twin=twin)
+            if got != m.totals.dict():
+                self.fail(i, op, f"stats() of the {'twin' if twin else 'main'} handle after the copy ({got} vs {m.totals.dict()})")
+        # coverage bookkeeping follows the states: what was watched on a source env is watched on its copies
+        c_dst, c_src = (self.ctr_of, self.ctr_of_tw) if to_main else (self.ctr_of_tw, self.ctr_of)
+        moved = {e: int(j) for e, (j, ok) in enumerate(zip(plain.tolist(), sel.tolist())) if ok}
+        new = {e: c_src[j] for e, j in moved.items() if j in c_src}
+        for e in moved:
+            c_dst.pop(e, None)
+        c_dst.update(new)
+        if to_main:
+            self.seen_r[sel] = False
+            self.seen_c[sel] = False
+
+    def op_swap(self, i, op):
+        self.a.swap()
+        was = compiled_shape(self.cfg, self.tuning)
+        self.m, self.tw = self.tw, self.m
+        self.tuning, self.tuning_tw = self.tuning_tw, self.tuning
+        self.ctr_of, self.ctr_of_tw = self.ctr_of_tw, self.ctr_of
+        self.seen_r[:] = False
+        self.seen_c[:] = False
+        self._hand_over(was)
+
+    def _hand_over(self, was):
+        now = compiled_shape(self.cfg, self.tuning)
+        self.cov["to_generic"] += was and not now
+        self.cov["to_compiled"] += now and not was
 
     def _check_blob(self, i, op, blob):
         words = unpack_blob(blob)
@@ -826,6 +1186,9 @@ class _Driver:
         self.a.migrate(op["tuning"], op["keep"], blob)
         self._check_blob(i, op, self.a.get_blob())
         self.m.totals = Totals()
+        was = compiled_shape(self.cfg, self.tuning)
+        self.tuning = dict(op["tuning"])
+        self._hand_over(was)
         d = op["direction"]
         self.cov["migrate_dirs"][d] = self.cov["migrate_dirs"].get(d, 0) + 1
         self.cov["long_migrate"] += self._long_touched()
@@ -834,6 +1197,7 @@ class _Driver:
         got, want = self.a.stats(op["reset"]), self.m.totals.dict()
         if got != want:
             self.fail(i, op, f"stats() ({got} vs the model {want})")
+        self.cov["stats_saw_errors"] += want["errors"] > 0
         if op["reset"]:
             self.cov["episodes"] += want["episodes"]
             self.cov["env_steps"] += want["env_steps"]
@@ -930,6 +1294,8 @@ class _Driver:
                 self.prev_class = cls
             elif kind == "reset_all":
                 self.prev_class = None
+            if kind not in ("render", "scripted", "stats", "space", "cells", "swap"):   # (what the next stepping op follows)
+                self.prev_kind = kind
             self.seen_r &= self.m.fin
             self.seen_c &= self.m.fin
             self.cov["fin_across"] = max(self.cov["fin_across"], int((self.seen_r & self.seen_c).sum()))
@@ -942,13 +1308,17 @@ class _Driver:
             self.fail(len(ops), end, f"stats() ({got} vs the model {want})")
         self.cov["episodes"] += want["episodes"]
         self.cov["env_steps"] += want["env_steps"]
+        self._words_fail(len(ops), end, "the twin", self.a.get_blob(twin=True), self.tw.all_words())
+        got, want = self.a.stats(False, twin=True), self.tw.totals.dict()
+        if got != want:
+            self.fail(len(ops), end, f"stats() of the twin ({got} vs the model {want})")
         got = self.a.kept_stats()
         if got != self.kept:
             self.fail(len(ops), end, f"stats() of the handles kept open after a migration ({got} vs {self.kept})")
 
 
 def run(adapter, cfg, ops, count=True):
-    """Drive `adapter` and an Oracle through `ops` side by side (ops[:k] of a generated list is as good as the list).
+    """Drive `adapter` (its handle and the twin) and two Oracles through `ops` side by side (ops[:k] of a generated list is as good as the list).
     Raises Mismatch (an AssertionError) at the first difference; returns the coverage counters (count=False skips the
     ones that cost per-step reads of the oracle)."""
     d = _Driver(adapter, cfg, count)

@@ -1,8 +1,25 @@
-"""Random interleavings of every entry point on one handle against the CPU oracle (tests/op_fuzz.py), and a state made
-on one record policy continued on the other, with no randomness in the path.  Bit-exact throughout.
+"""Random interleavings of every entry point on one handle, and of device-side copies between it and a twin handle,
+against the CPU oracle (tests/op_fuzz.py); and a state made on one record policy continued on the other, with no
+randomness in the path.  Bit-exact throughout.
+
+The adapter owns two handles: the main one and its twin (the neighbouring shard, another seed, the opposite record
+policy, another envs_per_block; reset once at open).  Besides the older op kinds the sequences hold `space`
+(msnake_space_actions: counts, safe mask and the space_greedy columns, whose actions drive the next step), `cells`
+(msnake_render_cells: planes of a random view mask and the snake table), `fork` (msnake_copy_envs in either direction
+with the identity, a permutation, a sparse map or one with out-of-range entries; both handles' states and stats() are
+compared in full afterwards) and `swap` (main and twin exchange roles, so every later op runs on the handle the copy
+kernel last wrote).  S10x1, S19x3_spec and S19x2_spec start on the step kernels compiled for the handle's shape: a
+padded stride falls back to the generic kernel for the call, a migration or a swap hands the state to a generic
+handle and back.  The adapter asserts at open that the full-record handle of these reports a kernel name that carries
+the board size.  Every call goes through the C entry points on the adapter's one stream.
+
+Not fuzzed, host-only and tested elsewhere: msnake_state_blob_info, msnake_kernel_name_for_config (and
+msnake_kernel_name beyond the assertion above).
 
 The sequences are the ones tests/test_op_fuzz_host.py runs on the oracle alone, where their coverage is counted and
-asserted.  Only calls that include/msnake.h documents as valid are issued.
+asserted, and where each of the nine silent defects OracleAdapter can inject (among them fork_row_shifted,
+fork_touched_unselected, fork_totals_copied, space_off_by_one, cells_head_as_body) is shown to be caught.  Only calls
+that include/msnake.h documents as valid are issued.
 
 Regression cases (a (configuration, seed, op index) that once exposed a product bug, kept by name): none so far."""
 import numpy as np

@@ -1,6 +1,9 @@
-"""tests/op_fuzz.py on the CPU: the driver, its stats model and its guards against a second Oracle (the null test), the
-coverage the generated sequences reach (counted on the oracle alone, for every (configuration, seed) the GPU file runs),
-the four injected silent defects (each must be caught), and the generator's determinism."""
+"""tests/op_fuzz.py on the CPU: the driver, its stats models and its guards against further Oracles (the null test), the
+coverage the generated sequences reach (counted on the oracle alone, for every (configuration, seed) the GPU file runs:
+op kinds, class pairs, the copies between the handle and its twin, the compiled-shape step kernels and the hand-overs
+to and from the generic ones), the nine injected silent defects (each must be caught), and the generator's
+determinism."""
+import ctypes
 import hashlib
 import re
 
@@ -31,8 +34,9 @@ def test_null_run_and_coverage_of_every_case(cfg, seed):
     cov, ops = _null(cfg, seed)
     print(cfg["name"], seed, {k: (sorted(v) if isinstance(v, set) else v) for k, v in cov.items()})
     assert len(ops) == cfg["n_ops"]
-    # 1. every op kind at least 3 times
-    assert all(cov["kinds"][k] >= 3 for k in _applicable(cfg)), cov["kinds"]
+    # 1. every op kind at least 3 times (above 8 192 envs: space, cells and fork at least once; swap follows fork)
+    few = ("space", "cells", "fork", "swap") if cfg["num_envs"] > 8192 else ("swap",)
+    assert all(cov["kinds"][k] >= (1 if k in few else 3) for k in _applicable(cfg)), cov["kinds"]
     # 2. at least 2 migrations in each direction ([N] has no short record: envs_per_block only)
     if cfg["rules"] != 1:
         assert cov["migrate_dirs"].get("full>short", 0) >= 2 and cov["migrate_dirs"].get("short>full", 0) >= 2, cov["migrate_dirs"]
@@ -44,13 +48,24 @@ def test_null_run_and_coverage_of_every_case(cfg, seed):
     assert cov["with_end"] >= 0.2 * cov["stepping"] and cov["with_respawn"] >= 0.2 * cov["stepping"], cov
     # 5. a rollout across a 16-step boundary with an episode end inside
     assert cov["rollout_cross16_end"] >= 1, cov
+    # 9. copies in each direction at least twice, and a copy directly in front of each of step, rollout and reset_mask
+    # on the handle it wrote
+    assert all(cov["fork_dirs"][d] >= 2 for d in of.FORK_DIRS), cov["fork_dirs"]
+    assert all(v >= 1 for v in cov["after_fork"].values()), cov["after_fork"]
+    # 10. the step kernels compiled for the shape: stepping ops that run them, stepping ops that fall back to the
+    # generic kernel for one call (padded stride), hand-overs of the state to a generic handle and back
+    if cfg["name"] in SPEC:
+        assert cov["compiled_steps"] >= 3 and cov["fallback_steps"] >= 2, cov
+        assert cov["to_generic"] >= 2 and cov["to_compiled"] >= 2, cov
 
 
 @pytest.mark.parametrize("cfg", of.CONFIGS, ids=[c["name"] for c in of.CONFIGS])
 def test_coverage_over_the_seeds_of_a_configuration(cfg):
     covs = [_null(cfg, s)[0] for s in cfg["seeds"]]
-    total = {k: sum(c[k] for c in covs) for k in ("wraps", "long_migrate", "long_checkpoint", "fin_across", "resets_of_finished")}
-    print(cfg["name"], total)
+    total = {k: sum(c[k] for c in covs) for k in ("wraps", "long_migrate", "long_checkpoint", "fin_across", "resets_of_finished",
+                                                    "fork_dst_finished", "fork_src_finished", "fork_src_long", "stats_saw_errors")}
+    modes = {m: sum(c["fork_modes"][m] for c in covs) for m in of.FORK_MODES}
+    print(cfg["name"], total, modes)
     # 6. a 2^32 wrap of the draw counter (asked for per rule set; held per configuration)
     assert total["wraps"] >= 1, total
     # 7. a body over 64 cells survives a migration and a checkpoint_self, where the board has room for one
@@ -59,6 +74,38 @@ def test_coverage_over_the_seeds_of_a_configuration(cfg):
     # 8. without auto reset: an env stays finished across a rollout and a checkpoint_self before it is reset
     if not cfg["auto_reset"]:
         assert total["fin_across"] >= 1 and total["resets_of_finished"] >= 1, total
+    # 11. every index mode of the copy; an out-of-range one that a later stats() sees as errors > 0
+    assert all(v >= 1 for v in modes.values()), modes
+    assert total["stats_saw_errors"] >= 1, total
+    # 12. a copy from a finished source env, and (without auto reset) onto a finished destination env
+    if not cfg["auto_reset"]:
+        assert total["fork_dst_finished"] >= 1 and total["fork_src_finished"] >= 1, total
+    # 13. a copy of a body over 64 cells (the overflow ring), where the board has room for one
+    if of.long_body_allowed(cfg):
+        assert total["fork_src_long"] >= 1, total
+
+
+SPEC = ("S10x1", "S19x3_spec", "S19x2_spec")
+
+
+@pytest.mark.parametrize("name", SPEC)
+def test_the_compiled_shape_configurations_start_on_a_compiled_kernel(name):
+    """Asked of the library's own host glue (no GPU), as tests/test_shape_spec_host.py does: the starting tuning names
+    an instantiation with the fifth template argument, the same configuration on the short record names none."""
+    import msnake
+    C = msnake._capi
+    cfg = of.BY_NAME[name]
+
+    def kernel(record):
+        c = C.MsnakeConfig(ctypes.sizeof(C.MsnakeConfig), 0, cfg["num_envs"], cfg["dim"], cfg["n_snakes"], cfg["n_fruits"],
+                           cfg["rules"], cfg["max_steps"], int(cfg["auto_reset"]), cfg["obs_scale"], cfg["seed"],
+                           cfg["env_id_base"], cfg["tuning"]["envs_per_block"], C.RECORD_POLICY[record],
+                           C.STORE_POLICY[cfg["tuning"]["obs_store_policy"]], 0)
+        return C.kernel_name_for_config(c)
+
+    assert of.compiled_shape(cfg, cfg["tuning"]) and not of.compiled_shape(cfg, of.twin_cfg(cfg)["tuning"])
+    assert kernel(cfg["tuning"]["record_policy"]) == "msnake_step_kernel<0, %d, 0, 1, %d>" % (cfg["n_snakes"], cfg["dim"])
+    assert kernel("short") == "msnake_step_kernel<0, %d, 0, 1>" % cfg["n_snakes"]
 
 
 def test_the_table_covers_what_it_is_there_for():
@@ -80,7 +127,9 @@ def test_the_table_covers_what_it_is_there_for():
 
 
 # ---------------------------------------------------------------------------------------------- sensitivity
-FAULTS = [("ctr_lag", "S12x3", 1, 15), ("fruit_moved", "A10x2", 2, 15), ("fin_dropped", "A6x3", 1, 15), ("double_count", "N6x4", 3, 15)]
+FAULTS = [("ctr_lag", "S12x3", 1, 15), ("fruit_moved", "A10x2", 2, 15), ("fin_dropped", "A6x3", 1, 15), ("double_count", "N6x4", 3, 15),
+          ("fork_row_shifted", "S19x2_spec", 1, 15), ("fork_touched_unselected", "A6x3", 2, 15), ("fork_totals_copied", "N10x2_x4", 1, 15),
+          ("space_off_by_one", "S12x3", 3, 15), ("cells_head_as_body", "N6x4", 2, 15)]
 
 
 @pytest.mark.parametrize("kind,name,seed,after", FAULTS, ids=[f[0] for f in FAULTS])
@@ -135,4 +184,4 @@ def test_the_generator_is_deterministic_and_pinned():
     assert hashlib.sha256(repr(a).encode()).hexdigest() == PINNED
 
 
-PINNED = "fae5313f975b794a1b96991c2b08e565f283633b8dd327631e50953f24477c09"
+PINNED = "ebe9a9959e16d3a1448f86efa607091cc1896e28df13cdc0ac708ed95ff36d8c"
