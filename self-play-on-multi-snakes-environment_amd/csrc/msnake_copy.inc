@@ -3,6 +3,7 @@
 // Off the step path: nothing here is referenced by msnake_step_kernel.
 //
 // One wavefront per DESTINATION env.  Its source index is wave-uniform; a negative one ends the wave before any load.
+// The source env is read through EnvReader (msnake_envread.inc).
 // Everything a step reads sits at addresses that depend only on the env index, so the copy is a handful of coalesced
 // wave instructions, and its traffic follows the state that exists, not the capacity of the rings:
 //   * the 256-byte record, lane l <-> word l: one load from the source, one store to the destination.  Merged by lane:
@@ -19,86 +20,68 @@
 namespace msnake {
 
 struct CopyArgs {
-    const uint32_t* s_hdr; const uint16_t* s_body0; const uint16_t* s_ovf; const uint16_t* s_fl0; const uint16_t* s_flist;
-    uint32_t* d_hdr; uint16_t* d_body0; uint16_t* d_ovf; uint16_t* d_fl0; uint16_t* d_flist;
-    const int32_t* index;  // [d_nenv] source env of every destination env; NULL = the identity
-    int32_t s_nenv, d_nenv, ns, s_cap, d_cap, fcap, rules;
+    StateView src, dst;    // same rules, dim and snake count, hence fcap (msnake_copy_envs checks); only `dst` is written
+    const int32_t* index;  // [dst.nenv] source env of every destination env; NULL = the identity
 };
 
 __global__ __launch_bounds__(256) void msnake_copy_envs_kernel(CopyArgs a) {
     const int lane = (int)(threadIdx.x & 63u);
     const int e = (int)uni(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-    if (e >= a.d_nenv) return;
+    if (e >= a.dst.nenv) return;
     const int src = a.index ? (int)uni((uint32_t)a.index[e]) : e;
     if (src < 0) return;  // not selected: no load, no store
-    uint32_t* dh = a.d_hdr + (size_t)e * MSNAKE_HDR_WORDS;
+    const StateView& d = a.dst;
+    uint32_t* dh = d.hdr + (size_t)e * MSNAKE_HDR_WORDS;
     const bool acc = lane >= HDR_ACC_EPISODES && lane <= HDR_ACC_LEN_HI;
-    if (src >= a.s_nenv) {  // nothing of the source is read
+    if (src >= a.src.nenv) {  // nothing of the source is read
         if (lane == HDR_ACC_ERRORS) dh[lane] += 1u;
         return;
     }
-    const int ns = a.ns;
-    const uint32_t sv = a.s_hdr[(size_t)src * MSNAKE_HDR_WORDS + lane];
+    const int ns = d.ns;
+    const EnvReader rd(a.src, src, lane);
     const uint32_t dv = acc ? dh[lane] : 0u;
-    uint32_t ring[MSNAKE_MAX_SNAKES];
-#pragma unroll
-    for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s)
-        ring[s] = s < ns ? (uint32_t)a.s_body0[((size_t)src * ns + s) * 64 + lane] : 0u;
-    const bool adv = a.rules == MSNAKE_RULES_ADVERSARIAL;
+    const bool adv = d.rules == MSNAKE_RULES_ADVERSARIAL;
     uint32_t fr = 0u;
-    if (adv) fr = a.s_fl0[(size_t)src * 64 + lane];
+    if (adv) fr = a.src.fl0[(size_t)src * 64 + lane];
 
-    int len[MSNAKE_MAX_SNAKES];
+    SnakeRef sn[MSNAKE_MAX_SNAKES];
     bool fits = true;
 #pragma unroll
     for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
-        len[s] = s < ns ? (int)(rdlane(sv, SN_A(s)) >> 16) : 0;
-        fits = fits && len[s] <= a.d_cap - 1;  // the step kernel's own bound on a body
+        sn[s] = rd.snake(s);
+        fits = fits && sn[s].len <= d.cap - 1;  // the step kernel's own bound on a body
     }
     if (!fits) {
         if (lane == HDR_ACC_ERRORS) dh[lane] = dv + 1u;
         return;
     }
 
-    uint32_t hv = acc ? dv : sv;
+    uint32_t hv = acc ? dv : rd.hv;
     if (lane < ns) hv &= 0xFFFF0000u;  // SN_A: len stays, the overflow ring is written from position 0
-    if (a.rules != MSNAKE_RULES_NEW_WORLD && lane >= MSNAKE_HDR_SHORT_WORDS) hv = 0u;  // no parked draws (new_world: fruits)
+    if (d.rules != MSNAKE_RULES_NEW_WORLD && lane >= MSNAKE_HDR_SHORT_WORDS) hv = 0u;  // no parked draws (new_world: fruits)
     dh[lane] = hv;
 #pragma unroll
     for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s)
-        if (s < ns) a.d_body0[((size_t)e * ns + s) * 64 + lane] = (uint16_t)ring[s];
+        if (s < ns) d.body0[((size_t)e * ns + s) * 64 + lane] = (uint16_t)rd.ring[s];
 
 #pragma unroll
-    for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
-        if (s >= ns || len[s] <= 64) continue;
-        const int ohp = (int)(rdlane(sv, SN_A(s)) & 0xFFFFu);
-        const int n = len[s] - 64 < a.s_cap ? len[s] - 64 : a.s_cap;  // (<= d_cap - 65: checked above)
-        const uint16_t* so = a.s_ovf + ((size_t)src * ns + s) * a.s_cap;
-        uint16_t* dk = a.d_ovf + ((size_t)e * ns + s) * a.d_cap;
-        for (int base = 0; base < n; base += 64) {
-            const int j = base + lane;
-            int idx = ohp + j;
-            idx = idx >= a.s_cap ? idx - a.s_cap : idx;
-            idx = idx >= a.s_cap ? a.s_cap - 1 : idx;  // (a well-formed record never gets here)
-            if (j < n) dk[j] = so[idx];
-        }
+    for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {  // (at most d.cap - 65 overflow pieces: checked above)
+        uint16_t* dk = d.ovf + ((size_t)e * ns + s) * d.cap;
+        rd.for_each_piece(sn[s], [&](int i, uint32_t c, bool valid) {
+            if (valid && i >= 64) dk[i - 64] = (uint16_t)c;
+        });
     }
     if (adv) {
-        a.d_fl0[(size_t)e * 64 + lane] = (uint16_t)fr;
-        int nl = (int)rdlane(sv, HDR_NLIST);
-        nl = nl > a.fcap ? a.fcap : nl;
-        const uint16_t* sl = a.s_flist + (size_t)src * a.fcap;
-        uint16_t* dl = a.d_flist + (size_t)e * a.fcap;
-        for (int base = 0; base < nl; base += 64) {
-            const int f = base + lane;
-            if (f < nl) dl[f] = sl[f];
-        }
+        d.fl0[(size_t)e * 64 + lane] = (uint16_t)fr;
+        uint16_t* dl = d.flist + (size_t)e * d.fcap;
+        rd.for_each_fruit([&](int f, uint32_t c, bool valid) {
+            if (valid) dl[f] = (uint16_t)c;
+        });
     }
 }
 
 hipError_t launch_copy_envs(const StepParams& dst, const StepParams& src, int rules, const int32_t* src_index, hipStream_t stream) {
-    const CopyArgs a{src.hdr, src.body0, src.ring, src.fl0, src.flist, dst.hdr, dst.body0, dst.ring, dst.fl0, dst.flist, src_index,
-                     src.nenv, dst.nenv, dst.n_snakes, src.rest.cap, dst.rest.cap, dst.fcap, rules};
+    const CopyArgs a{state_view(src, rules), state_view(dst, rules), src_index};
     hipLaunchKernelGGL(msnake_copy_envs_kernel, dim3((unsigned)((dst.nenv + 3) / 4)), dim3(256), 0, stream, a);
     return hipGetLastError();
 }

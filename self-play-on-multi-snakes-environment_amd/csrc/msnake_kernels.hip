@@ -1716,28 +1716,21 @@ hipError_t launch_stats(uint32_t* hdr, int nenv, unsigned long long* stats, int 
     return hipGetLastError();
 }
 
+}  // namespace msnake
+
+#include "msnake_envread.inc"  // StateView and EnvReader: how the kernels off the step path read an env's state
+
+namespace msnake {
+
 // ------------------------------------------------------------------------------------------------
 // canonical state export / import (msnake_get_state[_all] / msnake_set_state[_all]; checkpoint and
 // test path, off the step path).  Word layout per env: include/msnake.h.  One wave per env.
 // ------------------------------------------------------------------------------------------------
-struct StateView {
-    uint32_t* hdr; uint16_t* body0; uint16_t* ovf; uint16_t* fl0; uint16_t* flist;
-    int32_t nenv, dim, ns, nf, cap, fcap, rules;
-};
-
-static StateView state_view(const StepParams& p, int rules) {
-    return StateView{p.hdr, p.body0, p.ring, p.fl0, p.flist, p.nenv, p.dim, p.n_snakes, p.n_fruits, p.rest.cap, p.fcap, rules};
-}
-
-__device__ __forceinline__ int state_fruit_count(const StateView& v, const uint32_t* h) {
-    return v.rules == MSNAKE_RULES_ADVERSARIAL ? (int)h[HDR_NLIST] : v.nf;
-}
-
 __global__ __launch_bounds__(256) void msnake_state_sizes_kernel(StateView v, int env0, int count, uint32_t* __restrict__ need) {
     const int w = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (w >= count) return;
     const uint32_t* h = v.hdr + (size_t)(env0 + w) * MSNAKE_HDR_WORDS;
-    uint32_t n = 8u + 2u * (uint32_t)state_fruit_count(v, h);
+    uint32_t n = 8u + 2u * (uint32_t)fruit_count(v, h[HDR_NLIST]);
     for (int s = 0; s < v.ns; ++s) n += 6u + 2u * (h[SN_A(s)] >> 16);
     need[w] = n;
 }
@@ -1745,49 +1738,45 @@ __global__ __launch_bounds__(256) void msnake_state_sizes_kernel(StateView v, in
 __global__ __launch_bounds__(256) void msnake_state_pack_kernel(StateView v, int env0, int count,
                                                                 const uint64_t* __restrict__ offsets, int32_t* __restrict__ words) {
     const int lane = (int)(threadIdx.x & 63u);
-    const int w = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    const int w = (int)uni(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     if (w >= count) return;
-    const int e = env0 + w;
-    const uint32_t* h = v.hdr + (size_t)e * MSNAKE_HDR_WORDS;
+    const EnvReader rd(v, env0 + w, lane);
     int32_t* out = words + offsets[w];
-    const bool adv = v.rules == MSNAKE_RULES_ADVERSARIAL, nw = v.rules == MSNAKE_RULES_NEW_WORLD;
-    const int nfr = state_fruit_count(v, h), fr0 = nw ? HDR_FRUIT0_N : HDR_FRUIT0_S;
+    const bool nw = v.rules == MSNAKE_RULES_NEW_WORLD;
+    const int nfr = rd.n_fruits();
+    const uint32_t flags = rd.flags();
     if (lane == 0) {
-        out[0] = (int32_t)h[HDR_T]; out[1] = (int32_t)h[HDR_CTR_LO]; out[2] = (int32_t)h[HDR_CTR_HI];
-        out[3] = (int32_t)h[HDR_SPARE]; out[4] = (int32_t)h[HDR_EP_LEN]; out[5] = (int32_t)h[HDR_EP_RETURN];
-        out[6] = nfr; out[7] = v.ns | ((h[HDR_FLAGS] & HDR_FLAG_FINISHED) ? 0x100 : 0);
+        out[0] = (int32_t)rd.word(HDR_T); out[1] = (int32_t)rd.word(HDR_CTR_LO); out[2] = (int32_t)rd.word(HDR_CTR_HI);
+        out[3] = (int32_t)rd.word(HDR_SPARE); out[4] = (int32_t)rd.word(HDR_EP_LEN); out[5] = (int32_t)rd.word(HDR_EP_RETURN);
+        out[6] = nfr; out[7] = v.ns | ((flags & HDR_FLAG_FINISHED) ? 0x100 : 0);
     }
     size_t k = 8;
-    for (int f = lane; f < nfr; f += 64) {
-        const uint32_t c = adv ? (uint32_t)v.flist[(size_t)e * v.fcap + f] : (h[fr0 + f] & 0xFFFFu);
-        out[k + 2 * f] = (int32_t)(c >> 8) - 1;
-        out[k + 2 * f + 1] = (int32_t)(c & 255u) - 1;
-    }
+    rd.for_each_fruit([&](int f, uint32_t c, bool valid) {
+        if (valid) {
+            out[k + 2 * f] = (int32_t)(c >> 8) - 1;
+            out[k + 2 * f + 1] = (int32_t)(c & 255u) - 1;
+        }
+    });
     k += 2 * (size_t)nfr;
-    for (int s = 0; s < v.ns; ++s) {
-        const uint32_t wA = h[SN_A(s)], wC = h[SN_C(s)];
-        const int len = (int)(wA >> 16), ohp = (int)(wA & 0xFFFFu), hp0 = (int)((wC >> SN_C_HP0_SHIFT) & 63u);
-        const int vel = (int)((wC >> 16) & 7u);
+#pragma unroll
+    for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
+        if (s >= v.ns) continue;
+        const SnakeRef sn = rd.snake(s);
+        const int len = sn.len, vel = (int)((rd.word(SN_C(s)) >> 16) & 7u);
         if (lane == 0) {
             out[k] = len;
             out[k + 1] = vel == 1 ? 1 : vel == 3 ? -1 : 0;
             out[k + 2] = vel == 2 ? 1 : vel == 4 ? -1 : 0;
-            out[k + 3] = (int32_t)h[SN_B(s)];
-            out[k + 4] = nw ? (int32_t)((h[HDR_FLAGS] >> s) & 1u) : 1;
-            out[k + 5] = nw ? (int32_t)((h[HDR_FLAGS] >> (4 + s)) & 1u) : 0;
+            out[k + 3] = (int32_t)rd.word(SN_B(s));
+            out[k + 4] = nw ? (int32_t)((flags >> s) & 1u) : 1;
+            out[k + 5] = nw ? (int32_t)((flags >> (4 + s)) & 1u) : 0;
         }
-        for (int i = lane; i < len; i += 64) {
-            uint32_t c;
-            if (i < 64) {
-                c = v.body0[((size_t)e * v.ns + s) * 64 + ((hp0 + i) & 63)];
-            } else {
-                int idx = ohp + i - 64;
-                idx = idx >= v.cap ? idx - v.cap : idx;
-                c = v.ovf[((size_t)e * v.ns + s) * v.cap + idx];
+        rd.for_each_piece(sn, [&](int i, uint32_t c, bool valid) {
+            if (valid) {
+                out[k + 6 + 2 * (size_t)i] = (int32_t)(c >> 8) - 1;
+                out[k + 6 + 2 * (size_t)i + 1] = (int32_t)(c & 255u) - 1;
             }
-            out[k + 6 + 2 * (size_t)i] = (int32_t)(c >> 8) - 1;
-            out[k + 6 + 2 * (size_t)i + 1] = (int32_t)(c & 255u) - 1;
-        }
+        });
         k += 6 + 2 * (size_t)len;
     }
 }

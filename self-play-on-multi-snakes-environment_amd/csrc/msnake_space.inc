@@ -2,8 +2,7 @@
 // Included behind msnake_scripted.inc at the end of msnake_kernels.hip: it uses that file's wave helpers and
 // wave_reduce, and must stay in its translation unit.  Off the step path.
 //
-// One wavefront per env; the wave only READS the handle's state (record by lane, 64-slot rings, overflow rings
-// strided in whole waves, the adversarial `flist`), exactly as msnake_scripted_kernel does.
+// One wavefront per env; the wave only READS the handle's state, through EnvReader (msnake_envread.inc).
 //   * Occupancy: lane y owns row y of the board as ONE 64-bit mask, bit x <-> cell (x, y) = (c0, c1).  The body
 //     cells arrive lane-distributed (lane <-> ring slot), so they are scattered through a wave-private 512-byte
 //     slice of static LDS: one ds_or per cell, then every lane reads its own row once.  DS operations of one wave
@@ -29,9 +28,9 @@
 namespace msnake {
 
 struct SpaceArgs {
-    const uint32_t* hdr; const uint16_t* body0; const uint16_t* ovf; const uint16_t* flist;
+    StateView v;
     int32_t* actions; uint8_t* safe; uint16_t* space;
-    int32_t nenv, dim, ns, nf, cap, fcap, rules, stride;
+    int32_t stride;
     uint32_t mask;
 };
 
@@ -76,13 +75,9 @@ __global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArg
     const int lane = (int)(threadIdx.x & 63u);
     const int wave = (int)uni(threadIdx.x >> 6);
     const int e = (int)uni(blockIdx.x * SPACE_WAVES + (threadIdx.x >> 6));
-    if (e >= a.nenv) return;  // (no workgroup barrier below)
-    const int ns = a.ns, dim = a.dim;
-    const uint32_t hv = a.hdr[(size_t)e * MSNAKE_HDR_WORDS + lane];
-    uint32_t ring[MSNAKE_MAX_SNAKES];
-#pragma unroll
-    for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s)
-        ring[s] = s < ns ? (uint32_t)a.body0[((size_t)e * ns + s) * 64 + lane] : 0u;
+    if (e >= a.v.nenv) return;  // (no workgroup barrier below)
+    const int ns = a.v.ns, dim = a.v.dim;
+    const EnvReader rd(a.v, e, lane);
     uint32_t* my = occ[wave];
     my[lane] = 0u;
     my[64 + lane] = 0u;
@@ -97,28 +92,9 @@ __global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArg
     int len[MSNAKE_MAX_SNAKES], hx[MSNAKE_MAX_SNAKES], hy[MSNAKE_MAX_SNAKES];
 #pragma unroll
     for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
-        len[s] = 0; hx[s] = hy[s] = -2;
-        if (s >= ns) continue;
-        len[s] = (int)(rdlane(hv, SN_A(s)) >> 16);
-        const int hp0 = (int)((rdlane(hv, SN_C(s)) >> SN_C_HP0_SHIFT) & 63u);
-        if (len[s] > 0) {
-            const uint32_t head = rdlane(ring[s], hp0);  // piece 0 sits in ring slot hp0
-            hx[s] = (int)(head >> 8) - 1; hy[s] = (int)(head & 255u) - 1;
-        }
-        const int n0 = len[s] < 64 ? len[s] : 64;
-        mark(ring[s], ((lane - hp0) & 63) < n0);
-        if (len[s] > 64) {  // pieces >= 64: the overflow ring, piece i at (ohp + i - 64) % cap
-            const int ohp = (int)(rdlane(hv, SN_A(s)) & 0xFFFFu);
-            const int n = len[s] < 64 + a.cap ? len[s] : 64 + a.cap;
-            for (int base = 64; base < n; base += 64) {
-                const int i = base + lane;
-                int idx = ohp + i - 64;
-                idx = idx >= a.cap ? idx - a.cap : idx;
-                idx = idx >= a.cap ? a.cap - 1 : idx;  // (a well-formed record never gets here)
-                idx = idx < 0 ? 0 : idx;
-                mark((uint32_t)a.ovf[((size_t)e * ns + s) * a.cap + idx], i < n);
-            }
-        }
+        const SnakeRef sn = rd.snake(s);
+        len[s] = sn.len; hx[s] = sn.x; hy[s] = sn.y;
+        rd.for_each_piece(sn, [&](int, uint32_t c, bool valid) { mark(c, valid); });
     }
     wave_sync();
     const uint64_t used = (uint64_t)my[2 * lane] | ((uint64_t)my[2 * lane + 1] << 32);
@@ -174,14 +150,11 @@ __global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArg
 #pragma unroll
         for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) elig[s] = (elig_all >> (4 * s)) & 15u;
 
-        const bool adv = a.rules == MSNAKE_RULES_ADVERSARIAL;
-        const int fr0 = a.rules == MSNAKE_RULES_NEW_WORLD ? HDR_FRUIT0_N : HDR_FRUIT0_S;
-        int nfr = adv ? (int)rdlane(hv, HDR_NLIST) : a.nf;
-        if (adv && nfr > a.fcap) nfr = a.fcap;
+        const int nfr = rd.n_fruits();
         uint32_t key[MSNAKE_MAX_SNAKES];  // min over this lane's fruits and the eligible moves of distance << 3 | move
 #pragma unroll
         for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) key[s] = 0xFFFFFFFFu;
-        auto fruit = [&](uint32_t c, bool valid) {
+        rd.for_each_fruit([&](int, uint32_t c, bool valid) {
             const int fx = (int)(c >> 8) - 1, fy = (int)(c & 255u) - 1;
 #pragma unroll
             for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s)
@@ -190,18 +163,11 @@ __global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArg
                     const int qx = hx[s] + (m == 0 ? 1 : m == 2 ? -1 : 0), qy = hy[s] + (m == 1 ? 1 : m == 3 ? -1 : 0);
                     const int dx = fx - qx, dy = fy - qy;
                     const uint32_t kk = ((uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy)) << 3) | (uint32_t)(m + 1);
-                    if (valid && ((elig[s] >> m) & 1u) && kk < key[s]) key[s] = kk;
+                    const uint32_t out = 0u - ((~elig[s] >> m) & 1u);  // all ones where the move is not eligible
+                    const uint32_t cand = valid ? kk | out : 0xFFFFFFFFu;
+                    key[s] = cand < key[s] ? cand : key[s];
                 }
-        };
-        if (adv) {
-            for (int base = 0; base < nfr; base += 64) {
-                const int f = base + lane;
-                const int fi = f < nfr ? f : 0;
-                fruit((uint32_t)a.flist[(size_t)e * a.fcap + fi], f < nfr);
-            }
-        } else {
-            fruit(hv & 0xFFFFu, lane >= fr0 && lane < fr0 + nfr);
-        }
+        });
 #pragma unroll
         for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
             if (s >= ns || elig[s] == 0u) continue;
@@ -224,8 +190,7 @@ __global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArg
 
 hipError_t launch_space(const StepParams& p, int rules, uint32_t snake_mask, int32_t* actions, int32_t action_stride, uint8_t* safe,
                         uint16_t* space, hipStream_t stream) {
-    const SpaceArgs a{p.hdr, p.body0, p.ring, p.flist, actions, safe, space, p.nenv, p.dim, p.n_snakes, p.n_fruits, p.rest.cap,
-                      p.fcap, rules, action_stride, snake_mask};
+    const SpaceArgs a{state_view(p, rules), actions, safe, space, action_stride, snake_mask};
     const dim3 grid((unsigned)((p.nenv + SPACE_WAVES - 1) / SPACE_WAVES)), block(SPACE_WAVES * 64);
     const int which = (snake_mask != 0u ? 4 : 0) | (safe ? 2 : 0) | (space ? 1 : 0);
 #define MSNAKE_SPACE(A, S, C) hipLaunchKernelGGL((msnake_space_kernel<A, S, C>), grid, block, 0, stream, a)
