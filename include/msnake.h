@@ -120,7 +120,7 @@ typedef struct msnake_stats {
     int64_t ep_len_sum;    /* sum of their lengths                        */
     int64_t ep_return_sum; /* sum of their returns (rewards are integral) */
     int64_t env_steps;     /* env-steps executed                          */
-    int64_t errors;        /* internal capacity guards tripped (must be 0) */
+    int64_t errors;        /* capacity guards tripped (0 in play from a reset; see msnake_set_state) */
     int64_t reserved[3];
 } msnake_stats;
 
@@ -186,9 +186,31 @@ int msnake_rollout_tape(msnake_handle h, const int32_t* actions_dev, int32_t act
  *  len, v0, v1, grow_to, alive, in_dead, len x (c0,c1) head first.
  * `finished` (bit 8 of word 7): the episode has ended and the env has not been reset since (only ever set
  * with auto_reset = 0); it keeps a restored env from counting that episode into msnake_get_stats again.
- * Heads and the entries of the adversarial fruit list lie in [-1, dim] (one step outside the grid is
- * where the reference can put them); body pieces behind the head and the fruits of snake_env /
- * new_world lie inside the grid [0, dim).  Anything else is MSNAKE_E_STATE.
+ * What msnake_set_state accepts, complete; every accepted state comes back from msnake_get_state word for word, and
+ * anything else is MSNAKE_E_STATE with one of six reasons in the message, the env left untouched.  With
+ *   cap  = the body capacity: dim^2 + 2, under new_world max(dim^2 + 2, max_steps + 2), rounded up to a multiple of 64,
+ *   fcap = the adversarial fruit-list capacity: n_snakes + n_snakes * (dim^2 + 2), rounded up to a multiple of 64,
+ * the checks run in this order and the first that fails names the reason:
+ *   1. at least 8 words (else "too short");
+ *   2. word 7 is n_snakes, or n_snakes | 0x100; any other bit set is "snake count";
+ *   3. t, spare_fruits and ep_len are >= 0 ("scalar").  t has no upper bound (a handle with a lower max_steps may be
+ *      given any t; its next step ends the episode); ctr and the bits of ep_return are free;
+ *   4. n_fruits_cur equals the handle's n_fruits (snake_env, new_world), lies in [0, fcap] (adversarial) ("fruit count");
+ *   5. the words reach to the end of the fruit list ("too short");
+ *   6. every fruit lies inside the grid [0, dim)^2; an entry of the adversarial list lies in [-1, dim]^2, one step
+ *      outside the grid being where the reference can put a dead snake's head ("cell");
+ *   7. then for snake 0, 1, ... in turn: its six header words are there ("too short"); len lies in [0, cap - 2]
+ *      ("length"); its len cells are there ("too short"); (v0, v1) is one of (0,0), (1,0), (0,1), (-1,0), (0,-1),
+ *      grow_to >= 0, alive and in_dead are 0 or 1 under new_world and exactly alive = 1, in_dead = 0 under snake_env and
+ *      adversarial, which is what msnake_get_state reports there ("scalar"); the head lies in [-1, dim]^2 and every
+ *      piece behind it inside the grid ("cell").  Cells may repeat, within a body and between bodies.  (A head
+ *      outside the grid moves the handle to the generic step kernels: see msnake_kernel_name.)
+ * Words behind the last snake are ignored.
+ * Two capacity conditions can only arise in play after such a state was installed, so they are not refused but counted:
+ * a body that would grow beyond cap - 1 pieces stays at cap - 1 (its oldest piece is dropped), and pieces of dying
+ * adversarial snakes that would take the fruit list beyond fcap entries are dropped, the list ending at fcap.  Each
+ * adds 1 per env and step to `errors` of msnake_get_stats; neither is reachable from a reset.  From such a step on the
+ * env no longer follows the reference; every other env does, and every call keeps working.
  * msnake_get_state returns the number of words needed/written (>0) or a negative error. */
 int msnake_get_state(msnake_handle h, int32_t env, int32_t* words, int32_t cap);
 int msnake_set_state(msnake_handle h, int32_t env, const int32_t* words, int32_t n);
@@ -335,7 +357,9 @@ int msnake_get_stats(msnake_handle h, msnake_stats* out, int32_t reset);
  * env-step.  Handles of the shapes 19x19 with 2 or 3 snakes and 10x10 with one snake (snake_env rules,
  * obs_scale 1, auto reset, the full record) run kernels compiled for that shape, named with a fifth template
  * argument, the board size; a call whose action_stride differs runs the generic kernel for that call, with the same
- * results. */
+ * results.  So does, from then on, a handle that msnake_set_state / msnake_set_state_all gave a head outside the grid, or
+ * that msnake_copy_envs filled from such a handle: only the generic kernels draw the wall over a body piece that such a
+ * snake leaves outside the grid when it turns back in (no state that play reaches has one). */
 const char* msnake_kernel_name(msnake_handle h);
 /* The same name for a configuration, decided on the host exactly as msnake_create decides it, without a handle and
  * without touching a GPU (tests, tools).  Writes at most n bytes, NUL-terminated; MSNAKE_E_ARG for a configuration

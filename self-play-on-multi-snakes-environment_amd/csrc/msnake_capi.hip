@@ -60,6 +60,9 @@ struct msnake_env {
     void* d_scratch;       // per-env state import/export staging (grown on demand)
     size_t scratch_bytes;
     char kname[64];
+    // a state with a head outside the grid was installed (msnake_set_state*) or may have been copied in (msnake_copy_envs
+    // from such a handle): see note_offgrid_head
+    int offgrid_head;
     // MSNAKE_DBG_STAGES builds only (tools/span_gap.py): per-launch slots of wave stamps
     unsigned long long* dbg_span;
     uint32_t dbg_span_slots, dbg_launch;
@@ -82,6 +85,19 @@ int ensure_scratch(msnake_env* h, size_t bytes) {
     return MSNAKE_OK;
 }
 
+// A head outside the grid exists in no state that play leaves behind (a snake whose head leaves the grid is cleared in
+// the same step); msnake_set_state accepts it.  If that snake turns back into the grid, its next step leaves a BODY piece
+// outside the grid, which the reference draws under the wall.  The generic step kernels clip such a piece; the kernels
+// compiled for a shape keep the painter that assumes it cannot exist, so a handle that may hold such a state runs the
+// generic kernels from then on (same results; msnake_kernel_name follows).
+void note_offgrid_head(msnake_env* h) {
+    h->offgrid_head = 1;
+    if (h->p.spec_dim != 0) {
+        h->p.spec_dim = 0;
+        msnake::step_kernel_name(h->cfg.rules, h->cfg.n_snakes, h->cfg.obs_scale, 0, h->kname, sizeof(h->kname));
+    }
+}
+
 const char* state_reason(uint32_t code) {
     switch (code) {
         case 1: return "state buffer too short / truncated";
@@ -89,6 +105,7 @@ const char* state_reason(uint32_t code) {
         case 3: return "fruit count differs from the handle's (or exceeds the fruit-list capacity)";
         case 4: return "a cell lies outside [-1, dim], or a body piece behind the head outside the grid";
         case 5: return "a body length is outside [0, capacity]";
+        case 6: return "a scalar field out of range (t, spare_fruits, ep_len or grow_to negative, a velocity that is no unit step, alive / in_dead)";
         default: return "malformed state";
     }
 }
@@ -487,6 +504,7 @@ int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_in
                                   "num_envs %d", s.num_envs, d.num_envs);
     if ((uintptr_t)src_index_dev & 3) return fail(MSNAKE_E_ALIGN, "src_index_dev must be 4-byte aligned");
     DeviceGuard guard(d.device);
+    if (src->offgrid_head) note_offgrid_head(dst);
     hipError_t e = msnake::launch_copy_envs(dst->p, src->p, d.rules, src_index_dev, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     return MSNAKE_OK;
@@ -546,7 +564,8 @@ int state_import(msnake_env* h, int env0, int count, const uint64_t* offsets, co
     const size_t off_bytes = ((size_t)count + 1) * 8, word_bytes = (size_t)offsets[count] * 4;
     if (int rc = ensure_scratch(h, 16 + off_bytes + word_bytes)) return rc;
     uint8_t* d = static_cast<uint8_t*>(h->d_scratch);
-    const uint32_t st0[4] = {0u, 0xFFFFFFFFu, 0u, 0u};  // [0] rejected envs, [1] min over them of (local index + 1) << 8 | reason
+    // [0] rejected envs, [1] min over them of (local index + 1) << 8 | reason, [2] != 0: an accepted env has a head outside the grid
+    const uint32_t st0[4] = {0u, 0xFFFFFFFFu, 0u, 0u};
     HIP_TRY(hipMemcpy(d, st0, 16, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d + 16, offsets, off_bytes, hipMemcpyHostToDevice));
     if (word_bytes) HIP_TRY(hipMemcpy(d + 16 + off_bytes, words, word_bytes, hipMemcpyHostToDevice));
@@ -555,6 +574,7 @@ int state_import(msnake_env* h, int env0, int count, const uint64_t* offsets, co
                                         reinterpret_cast<uint32_t*>(d), nullptr));
     uint32_t st[4];
     HIP_TRY(hipMemcpy(st, d, 16, hipMemcpyDeviceToHost));
+    if (st[2] != 0) note_offgrid_head(h);  // some accepted env has a head outside the grid
     if (st[0] != 0)
         return fail(MSNAKE_E_STATE, "%u env state(s) rejected; first: env %d: %s (the rejected envs were left untouched)", st[0],
                     env0 + (int)(st[1] >> 8) - 1, state_reason(st[1] & 0xFFu));

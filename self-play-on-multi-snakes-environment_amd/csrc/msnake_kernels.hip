@@ -1317,7 +1317,11 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
             const bool dead = in_mask((uint64_t)deadmask);
             if (RULES == MSNAKE_RULES_ADVERSARIAL && deadmask != 0) {
                 // [A]:183-186: every piece of a snake that dies this step (its out-of-grid head
-                // included) joins the fruit list, and spare_fruits grows by len per piece
+                // included) joins the fruit list, and spare_fruits grows by len per piece.
+                // The list holds fcap entries: room for every body of one episode from a reset, but not for what an
+                // installed state can add up to (a list of up to fcap entries plus bodies that still grow).  An entry at
+                // index >= fcap is dropped, the list ends at fcap and the step counts once into `errors`, like the body
+                // guards; spare_fruits keeps the reference's arithmetic.  (Lanes of `fr` are entries < 64 <= fcap.)
                 int nlist = (int)rdlane(hv, HDR_NLIST), spare = (int)rdlane(hv, HDR_SPARE);
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
@@ -1328,11 +1332,15 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
                         if (lane >= nlist && lane < nlist + len_s) fr = moved;
                         fr_dirty = true;
                         for_each_piece(s, cr[s], hp2[s], wc[s], len_s, [&](int i, uint32_t cell) {
-                            flist_of()[nlist + i] = (uint16_t)cell;
+                            if (nlist + i < fcap) flist_of()[nlist + i] = (uint16_t)cell;
                         });
                         nlist += len_s;
                         spare += len_s * len_s;
                     }
+                }
+                if (nlist > fcap) {
+                    nlist = fcap;
+                    HV_SET_C(HDR_ACC_ERRORS, rdlane(hv, HDR_ACC_ERRORS) + 1u);
                 }
                 HV_SET_C(HDR_NLIST, (uint32_t)nlist);
                 HV_SET_C(HDR_SPARE, (uint32_t)spare);
@@ -1443,10 +1451,13 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
             if (RULES == MSNAKE_RULES_NEW_WORLD && !((flags >> j) & 1u)) continue;  // [N]:219
             if (MODE == 2) pidx[j] = (lane - (int)(rdlane(hv, SN_C(j)) >> SN_C_HP0_SHIFT)) & 63;
             for_each_piece_at(j, cr[j], pidx[j], w0, (int)(w0 >> 16), [&](int i, uint32_t cell) {
-                // Only a HEAD can lie outside the grid (msnake_set_state refuses anything else), and after
-                // a step or a reset no live snake's head does ([S]:147-164 / [N]:117-119 clear it): the
-                // clip against the wall ring is needed only when a freshly installed state is rendered.
-                if (MODE == 2 && !in_grid(cell, dim)) return;
+                // Only a HEAD can be installed outside the grid (msnake_set_state refuses anything else), and after
+                // a step or a reset no live snake's head is ([S]:147-164 / [N]:117-119 clear it).  A freshly installed
+                // state can be rendered, and an installed head outside the grid becomes a body piece there if its snake
+                // turns back into the grid: the reference draws the wall over both, so they are clipped.  The kernels
+                // compiled for a shape go without the clip: a handle that may hold such a head does not run them
+                // (msnake_capi.hip: note_offgrid_head).
+                if ((MODE == 2 || !SPEC) && !in_grid(cell, dim)) return;
                 const int off = ((int)(cell >> 8) * W + (int)(cell & 255u)) * (C * K);
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
@@ -1782,12 +1793,14 @@ __global__ __launch_bounds__(256) void msnake_state_pack_kernel(StateView v, int
 }
 
 // status[0]: number of rejected envs, status[1]: min over them of (local index + 1) << 8 | MSNAKE_ST_* reason (ONE
-// atomicMin on ~0u: index and reason of the first rejected env cannot come from two different waves)
+// atomicMin on ~0u: index and reason of the first rejected env cannot come from two different waves), status[2]: != 0 if
+// an accepted env has a head outside the grid
 #define MSNAKE_ST_SHORT 1      // buffer too short / truncated
 #define MSNAKE_ST_SNAKES 2     // snake count differs from the handle
 #define MSNAKE_ST_FRUITS 3     // fruit count differs from the handle / exceeds the list capacity
 #define MSNAKE_ST_CELL 4       // a cell outside [-1, dim]
 #define MSNAKE_ST_LEN 5        // a body length outside [0, cap - 2]
+#define MSNAKE_ST_SCALAR 6     // a scalar field out of range: t, spare_fruits, ep_len, grow_to, a velocity, alive / in_dead
 __global__ __launch_bounds__(256) void msnake_state_unpack_kernel(StateView v, int env0, int count,
                                                                   const uint64_t* __restrict__ offsets,
                                                                   const int32_t* __restrict__ words, uint32_t* __restrict__ status) {
@@ -1802,8 +1815,12 @@ __global__ __launch_bounds__(256) void msnake_state_unpack_kernel(StateView v, i
     // ---- pass 1: validate everything before anything is written
     int bad = 0;
     int nfr = 0;
+    bool off_head = false;  // (lane 0) some head lies outside the grid: reported in status[2] if the env is accepted
     if (n < 8) bad = MSNAKE_ST_SHORT;
     else if ((in[7] & ~0x100) != v.ns) bad = MSNAKE_ST_SNAKES;  // (bit 8: the episode-finished flag)
+    // counters that play only ever raises from 0; a negative spare_fruits also stops the reference's respawns for good
+    // ([A]:137-141 tests > 0 and == 0).  t has no upper bound: a handle with a lower episode cap may receive any t
+    else if (in[0] < 0 || in[3] < 0 || in[4] < 0) bad = MSNAKE_ST_SCALAR;
     else {
         nfr = in[6];
         if (adv ? (nfr < 0 || nfr > v.fcap) : nfr != v.nf) bad = MSNAKE_ST_FRUITS;
@@ -1826,10 +1843,18 @@ __global__ __launch_bounds__(256) void msnake_state_unpack_kernel(StateView v, i
         const int len = in[k];
         if (len < 0 || len > v.cap - 2) { bad = MSNAKE_ST_LEN; break; }
         if (n < k + 6 + 2LL * len) { bad = MSNAKE_ST_SHORT; break; }
+        // what the record cannot hold, or holds as something else: a velocity that is not one of the five, a bit that is
+        // not 0 / 1, a negative grow_to (the vector update compares it unsigned); without the new_world bits a snake
+        // is alive and not in dead_snakes, which is what the export says there
+        const int v0 = in[k + 1], v1 = in[k + 2], al = in[k + 4], ind = in[k + 5];
+        const bool vel_ok = (v0 == 0 && (v1 >= -1 && v1 <= 1)) || (v1 == 0 && (v0 == -1 || v0 == 1));
+        const bool bits_ok = nw ? ((al == 0 || al == 1) && (ind == 0 || ind == 1)) : (al == 1 && ind == 0);
+        if (!vel_ok || in[k + 3] < 0 || !bits_ok) { bad = MSNAKE_ST_SCALAR; break; }
         bool okc = true;
         for (int i = lane; i < len; i += 64) {
             const int c0 = in[k + 6 + 2LL * i], c1 = in[k + 6 + 2LL * i + 1];
             okc = okc && cell_ok(c0, c1);
+            if (i == 0) off_head = off_head || !(c0 >= 0 && c0 < v.dim && c1 >= 0 && c1 < v.dim);
             // only a head may be one step outside the grid (where a reference snake can be, for one step)
             if (i > 0) okc = okc && c0 >= 0 && c0 < v.dim && c1 >= 0 && c1 < v.dim;
         }
@@ -1843,6 +1868,7 @@ __global__ __launch_bounds__(256) void msnake_state_unpack_kernel(StateView v, i
         }
         return;
     }
+    if (off_head) atomicOr(&status[2], 1u);
     // ---- pass 2: the record (lane l builds word l; logging totals are not part of the canonical
     //      state and stay; every other word, the parked Philox draws included, is cleared)
     uint32_t* h = v.hdr + (size_t)e * MSNAKE_HDR_WORDS;
