@@ -37,6 +37,8 @@
  *                      between two handles without the host round trip of msnake_get_state / msnake_set_state.
  *   msnake_render_cells <- get_ob_for_snake / get_multi_snake_ob (snake_multiple_test.py:35-58,93-95) without its last
  *                      step, the colour table: which of six things each cell shows, per view, plus the per-snake facts.
+ *   msnake_render_local: no reference counterpart; the head-centred, heading-aligned window of those cell codes that
+ *                      snake policies outside the reference are trained on, cut on the device.
  *   msnake_get_stats <- the epinfobuf aggregation in ppo_multi_agent.py:288,331,366-390
  *
  * RNG contract (shared with oracle/ and tests/golden): draw i of global env g is word (i & 3) of
@@ -345,6 +347,35 @@ int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_in
  * captured into a HIP graph behind a step.  MSNAKE_E_ARG, before any device work: a view_mask bit >= views; view_mask
  * != 0 with cells_dev NULL; view_mask == 0 with cells_dev non-NULL; nothing to write (view_mask 0 and snakes_dev NULL). */
 int msnake_render_cells(msnake_handle h, uint32_t view_mask, uint8_t* cells_dev, int32_t* snakes_dev, void* stream);
+
+/* Head-centred windows of cell codes, one per selected snake, computed on the device from the current state of every
+ * env: a fixed-size cut of the planes of msnake_render_cells around a snake's head, optionally turned so that the snake
+ * looks along the window's first axis.  The input is the same on every board size and, oriented, from every snake in
+ * every direction.
+ * Shapes: W = 2 * radius + 1, S = popcount(snake_mask).  windows_dev: uint8 [num_envs][S][W][W], the selected snakes in
+ * ascending order.  heading_dev (may be NULL): uint8 [num_envs][S].  Neither needs any alignment (W * W is odd, so blocks
+ * start at every address phase).
+ * Heading k of snake s, from its velocity (v0, v1) in the canonical state: (1,0) -> 0, (0,1) -> 1, (-1,0) -> 2,
+ * (0,-1) -> 3, (0,0) -> 0: the action that keeps the direction, minus 1.  heading_dev receives k whatever `oriented` is.
+ * Let f be move k + 1 and g move ((k + 1) mod 4) + 1 of the move table (1..4 = (+1,0), (0,+1), (-1,0), (0,-1));
+ * with oriented == 0, k is taken as 0 for the window, so f = (1,0) and g = (0,1).
+ * Window entry [i][j] of snake s shows the cell head + (i - radius) * f + (j - radius) * g, where head is piece 0.  If
+ * that cell lies in [0, dim)^2 the entry is the byte the plane of view s of msnake_render_cells holds there: 0..5 with
+ * the same paint order (a later paint wins, a dead new_world snake paints nothing, duplicates are included); view s
+ * exists here for every s < n_snakes under all three rule sets.  Otherwise the entry is MSNAKE_CELL_OUTSIDE.  The centre
+ * [radius][radius] is the head's own cell: usually 3; on installed states it can be another code, or 6 for a head at -1
+ * or dim.  A snake with an empty body gets W * W zeros and heading 0.
+ * Relative actions: under oriented == 1, relative action r in 1..4 means forward (+f), the +g side, backward, the -g
+ * side; it is the absolute action ((r - 1 + k) mod 4) + 1, and 0 stays 0.
+ * Like msnake_render_cells the call only reads the handle's state (no random numbers are drawn, the Philox counter
+ * stays), allocates nothing, does not synchronise and adds nothing to env_steps; asynchronous on `stream`, and it can be
+ * captured into a HIP graph behind a step.  MSNAKE_E_ARG, before any device work: radius outside [1,
+ * MSNAKE_LOCAL_MAX_RADIUS]; snake_mask 0 or with a bit >= n_snakes; oriented not 0 or 1; windows_dev NULL.
+ * MSNAKE_E_HANDLE for a NULL handle. */
+#define MSNAKE_LOCAL_MAX_RADIUS 31
+#define MSNAKE_CELL_OUTSIDE 6 /* a window entry that lies outside the grid */
+int msnake_render_local(msnake_handle h, int32_t radius, uint32_t snake_mask, int32_t oriented, uint8_t* windows_dev,
+                        uint8_t* heading_dev, void* stream);
 
 /* Copy the aggregate statistics to the host.  Blocking: waits for the device (every step issued so
  * far, on any stream) before it sums the per-env totals.  episodes / ep_len_sum / ep_return_sum /

@@ -20,7 +20,7 @@ SYMBOLS = [
     "msnake_get_state_all", "msnake_set_state_all", "msnake_state_blob_info",
     "msnake_render", "msnake_get_stats", "msnake_kernel_name", "msnake_algorithmic_bytes_per_env_step",
     "msnake_scripted_actions", "msnake_copy_envs", "msnake_kernel_name_for_config",
-    "msnake_set_generic_kernels", "msnake_space_actions", "msnake_render_cells",
+    "msnake_set_generic_kernels", "msnake_space_actions", "msnake_render_cells", "msnake_render_local",
 ]
 
 
@@ -89,6 +89,8 @@ def load():
     L.msnake_space_actions.argtypes = [vp, ctypes.c_uint32, vp, i32, u8p, vp, vp]
     # h, view_mask, cells_dev (uint8 [num_envs][V][dim][dim]), snakes_dev (int32 [num_envs][n_snakes][8] or NULL), stream
     L.msnake_render_cells.argtypes = [vp, ctypes.c_uint32, u8p, vp, vp]
+    # h, radius, snake_mask, oriented, windows_dev (uint8 [num_envs][S][W][W]), heading_dev (uint8 [num_envs][S] or NULL), stream
+    L.msnake_render_local.argtypes = [vp, i32, ctypes.c_uint32, i32, u8p, u8p, vp]
     L.msnake_copy_envs.argtypes = [vp, vp, vp, vp]  # dst, src, src_index_dev (int32 [dst.num_envs] or NULL), stream
     L.msnake_step_tape.argtypes = [vp, vp, i32, i32, u8p, ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, vp]
     L.msnake_rollout_tape.argtypes = L.msnake_step_tape.argtypes
@@ -110,7 +112,7 @@ def load():
     for name in ("msnake_create", "msnake_destroy", "msnake_obs_shape", "msnake_reset", "msnake_reset_envs", "msnake_render",
                  "msnake_step", "msnake_step_tape", "msnake_rollout_tape", "msnake_get_state", "msnake_set_state", "msnake_set_state_all",
                  "msnake_state_blob_info", "msnake_get_stats", "msnake_scripted_actions", "msnake_copy_envs",
-                 "msnake_space_actions", "msnake_render_cells"):
+                 "msnake_space_actions", "msnake_render_cells", "msnake_render_local"):
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L

@@ -525,6 +525,23 @@ int msnake_render_cells(msnake_handle h, uint32_t view_mask, uint8_t* cells_dev,
     return MSNAKE_OK;
 }
 
+int msnake_render_local(msnake_handle h, int32_t radius, uint32_t snake_mask, int32_t oriented, uint8_t* windows_dev,
+                        uint8_t* heading_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    const int ns = h->p.n_snakes;
+    if (radius < 1 || radius > MSNAKE_LOCAL_MAX_RADIUS)
+        return fail(MSNAKE_E_ARG, "msnake_render_local: radius %d must lie in [1, %d]", radius, MSNAKE_LOCAL_MAX_RADIUS);
+    if (!snake_mask) return fail(MSNAKE_E_ARG, "msnake_render_local: snake_mask is 0 (no window to write)");
+    if (snake_mask >> ns) return fail(MSNAKE_E_ARG, "msnake_render_local: snake_mask 0x%x has a bit >= n_snakes=%d", snake_mask, ns);
+    if (oriented != 0 && oriented != 1) return fail(MSNAKE_E_ARG, "msnake_render_local: oriented must be 0 or 1, got %d", oriented);
+    if (!windows_dev) return fail(MSNAKE_E_ARG, "msnake_render_local: windows_dev is NULL");
+    DeviceGuard guard(h->cfg.device);
+    hipError_t e = msnake::launch_local(h->p, h->cfg.rules, radius, snake_mask, oriented, windows_dev, heading_dev,
+                                        static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return MSNAKE_OK;
+}
+
 // ---- canonical state import / export.  The device packs / unpacks (msnake_state_*_kernel); the host
 //      only sizes buffers and copies.  Blocking: every call starts with a device synchronise. ----
 namespace {

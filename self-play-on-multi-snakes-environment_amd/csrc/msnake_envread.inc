@@ -11,7 +11,7 @@
 //     (adversarial).
 // len, ohp and HDR_NLIST come straight out of HBM and turn into addresses here, under one set of bounds: a body is
 // walked up to 64 + cap pieces, an overflow index lies in [0, cap), a fruit index in [0, fcap).  Used by the space,
-// copy_envs and state export kernels; msnake_scripted.inc and msnake_cells.inc keep their own walk (DESIGN.md, section 12:
+// copy_envs, state export and local-window kernels; msnake_scripted.inc and msnake_cells.inc keep their own walk (DESIGN.md, section 12:
 // on this reader they measured slower).
 namespace msnake {
 

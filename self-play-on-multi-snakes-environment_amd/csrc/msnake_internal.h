@@ -138,6 +138,9 @@ hipError_t launch_copy_envs(const StepParams& dst, const StepParams& src, int ru
 // the observation as cell codes and the per-snake table (msnake_cells.inc); view_mask 0 / snakes NULL = that output is not
 // written.  Reads the handle's state only
 hipError_t launch_cells(const StepParams& p, int rules, uint32_t view_mask, uint8_t* cells, int32_t* snakes, hipStream_t stream);
+// head-centred cell-code windows of the snakes in snake_mask (msnake_local.inc); heading NULL = not written
+hipError_t launch_local(const StepParams& p, int rules, int radius, uint32_t snake_mask, int oriented, uint8_t* windows,
+                        uint8_t* heading, hipStream_t stream);
 // the DIM of the compile-time-shape instantiation that fits the configuration in `p` in every folded field, or 0 (host only)
 int spec_dim_of(const StepParams& p, int rules);
 // the instantiation that per-step launches run (spec_dim 0: the generic four-parameter one)

@@ -31,6 +31,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .vec_env import check_radius, relative_to_absolute
+
 
 # ----------------------------------------------------------------------------- policy
 def _ortho(module, scale):
@@ -94,6 +96,57 @@ class CnnPolicy(nn.Module):
         return self(ob_u8)[1]
 
 
+class WindowPolicy(CnnPolicy):
+    """CnnPolicy's four-conv trunk, fc512 and two heads (same initialisation) over a head-centred window of cell codes
+    (MultiSnakeVecEnv.render_local_device): the input is uint8 [B, W, W], W = 2 * radius + 1, one-hot encoded over the seven
+    codes (0 empty, 1 fruit, 2 / 3 own body / head, 4 / 5 another snake's, 6 outside the grid) into seven NCHW channels.
+    The input has one shape on every board, and with oriented windows it looks the same from every snake in every
+    direction, so one set of weights can play any column of the action buffer.  The radius and the orientation flag the
+    weights were trained under travel with them as the buffer `local_window` (load_weights refuses the other kind)."""
+
+    N_CODES = 7
+
+    def __init__(self, radius, n_actions=5, amp_dtype=None, oriented=True):
+        radius = check_radius(radius)
+        w = 2 * radius + 1
+        super().__init__((w, w, self.N_CODES), n_actions=n_actions, atari_size=False, amp_dtype=amp_dtype)
+        self.radius, self.oriented = radius, bool(oriented)
+        self.register_buffer("local_window", torch.tensor([radius, int(self.oriented)], dtype=torch.int64))
+        self.register_buffer("codes", torch.arange(self.N_CODES, dtype=torch.uint8).view(1, self.N_CODES, 1, 1), persistent=False)
+
+    def forward(self, win_u8):
+        """win_u8: uint8 [B, W, W] cell codes -> logits [B, A], value [B]."""
+        w = 2 * self.radius + 1
+        if win_u8.dim() != 3 or tuple(win_u8.shape[1:]) != (w, w) or win_u8.dtype != torch.uint8:
+            raise ValueError(f"expected uint8 windows of shape [B, {w}, {w}], got {win_u8.dtype} {tuple(win_u8.shape)}")
+        feats = []
+        with torch.autocast(win_u8.device.type, dtype=self.amp_dtype or torch.bfloat16, enabled=self.amp_dtype is not None):
+            for i in range(0, win_u8.shape[0], self.CONV_CHUNK):
+                x = (win_u8[i:i + self.CONV_CHUNK].unsqueeze(1) == self.codes).float()  # plain NCHW, one channel per code
+                feats.append(self.convs(x).flatten(1))
+            x = F.relu(self.fc1(torch.cat(feats) if len(feats) > 1 else feats[0]))
+            logits, v = self.pi(x), self.v(x)[:, 0]
+        return logits.float(), v.float()
+
+
+def window_kind(state_dict):
+    """What a weights file was trained on: None for full frames, (radius, oriented) for windows."""
+    t = state_dict.get("local_window")
+    return None if t is None else (int(t[0]), bool(int(t[1])))
+
+
+def _kind_text(kind):
+    return "full frames" if kind is None else f"windows of radius {kind[0]}, {'oriented' if kind[1] else 'not oriented'}"
+
+
+def check_kind(model, state_dict, path):
+    want = (model.radius, model.oriented) if isinstance(model, WindowPolicy) else None
+    got = window_kind(state_dict)
+    if got != want:
+        raise RuntimeError(f"{path} holds a policy trained on {_kind_text(got)}; this run trains on {_kind_text(want)} "
+                           "(local_radius / oriented): the weights cannot be loaded")
+
+
 def neglogp(logits, actions):
     return F.cross_entropy(logits, actions, reduction="none")
 
@@ -155,7 +208,9 @@ def save_weights(model, path):
 
 def load_weights(model, path):
     """Model.load (ppo_multi_agent.py:124-132).  weights_only: nothing in the file is executed."""
-    model.load_state_dict(torch.load(path, map_location=next(model.parameters()).device, weights_only=True))
+    state_dict = torch.load(path, map_location=next(model.parameters()).device, weights_only=True)
+    check_kind(model, state_dict, path)
+    model.load_state_dict(state_dict)
 
 
 class OpponentPool:
@@ -395,14 +450,49 @@ def refresh_scripted(opponents):
 class Runner:
     """ppo_multi_agent.py:145-216 with everything on the device."""
 
-    def __init__(self, env, model, opponents, nsteps, gamma, lam):
+    def __init__(self, env, model, opponents, nsteps, gamma, lam, local_radius=None, oriented=True):
         self.env, self.model, self.opponents = env, model, opponents
         self.nsteps, self.gamma, self.lam = nsteps, gamma, lam
+        self.local_radius, self.oriented = local_radius, bool(oriented)
         self.obs = env.reset_device()
+        if local_radius is not None:
+            # the learner and every network opponent see their own snake's window: one env call for all of them
+            self.win_snakes = [0] + [i + 1 for i, opp in enumerate(opponents) if isinstance(opp, nn.Module)]
+            self.slot = {s: q for q, s in enumerate(self.win_snakes)}
+            shape = (env.num_envs,) + env.local_shape(local_radius, self.win_snakes)
+            self.win = torch.empty(shape, dtype=torch.uint8, device=self.obs.device)
+            self.heading = torch.empty(shape[:2], dtype=torch.uint8, device=self.obs.device)
+            self.observe_local()
         self.dones = torch.zeros(env.num_envs, dtype=torch.float32, device=self.obs.device)
         self.tstart = time.time()
 
+    def observe_local(self):
+        self.env.render_local_device(self.local_radius, snakes=self.win_snakes, oriented=self.oriented, out=self.win,
+                                     heading_out=self.heading)
+
+    def learner_obs(self):
+        return self.obs[..., 0:3] if self.local_radius is None else self.win[:, 0]
+
+    def absolute(self, a, snake):
+        """A window policy's sampled action as the step takes it: relative to the heading under oriented windows."""
+        return relative_to_absolute(a, self.heading[:, self.slot[snake]]) if self.oriented else a
+
+    def multi_step_local(self):
+        a, v, nlp = self.model.step(self.win[:, 0])
+        acts = [self.absolute(a, 0)]
+        refresh_scripted(self.opponents)
+        for i, opp in enumerate(self.opponents):
+            if opp is None:
+                acts.append(torch.ones_like(a))
+            elif isinstance(opp, nn.Module):
+                acts.append(self.absolute(opp.step(self.win[:, self.slot[i + 1]])[0], i + 1))
+            else:
+                acts.append(opp.step(None)[0])
+        return a, v, nlp, torch.stack(acts, dim=1).to(torch.int32)
+
     def multi_step(self):
+        if self.local_radius is not None:
+            return self.multi_step_local()
         a, v, nlp = self.model.step(self.obs[..., 0:3])
         acts = [a]
         refresh_scripted(self.opponents)
@@ -416,21 +506,23 @@ class Runner:
     def run(self):
         T, N = self.nsteps, self.env.num_envs
         dev = self.obs.device
-        mb_obs = torch.empty((T, N) + tuple(self.obs.shape[1:3]) + (3,), dtype=torch.uint8, device=dev)
+        mb_obs = torch.empty((T, N) + tuple(self.learner_obs().shape[1:]), dtype=torch.uint8, device=dev)
         mb_rew = torch.empty((T, N), device=dev); mb_val = torch.empty((T, N), device=dev)
         mb_nlp = torch.empty((T, N), device=dev); mb_done = torch.empty((T, N), device=dev)
         mb_act = torch.empty((T, N), dtype=torch.long, device=dev)
         ep_r, ep_l = [], []
         for t in range(T):
             a, v, nlp, full = self.multi_step()
-            mb_obs[t] = self.obs[..., 0:3]
+            mb_obs[t] = self.learner_obs()
             mb_act[t], mb_val[t], mb_nlp[t], mb_done[t] = a, v, nlp, self.dones
             self.obs, rew, done, info = self.env.step_device(full)
+            if self.local_radius is not None:
+                self.observe_local()
             mb_rew[t] = rew
             self.dones = done.float()
             ep_r.append(torch.where(done.bool(), info[:, 0].view(torch.float32), torch.full_like(rew, float("nan"))))
             ep_l.append(info[:, 1].clone())  # `info` is the env's buffer: the next step overwrites it
-        last_values = self.model.value(self.obs[..., 0:3])
+        last_values = self.model.value(self.learner_obs())
         returns, _ = gae(mb_rew, mb_val, mb_done, last_values, self.dones, self.gamma, self.lam)
         # episode infos: one host sync per rollout instead of one per step
         r = torch.stack(ep_r).flatten(); l = torch.stack(ep_l).flatten()
@@ -445,7 +537,8 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
           max_grad_norm=0.5, gamma=0.99, lam=0.95, log_interval=1, nminibatches=8, noptepochs=4,
           cliprange=lambda f: f * 0.1, opponent_save_interval=50, max_saved_opponents=1000, csv_path=None,
           monitor_path=None, seed=0, log_fn=print, amp_dtype=None, json_path=None, tb_dir=None,
-          save_dir=None, save_interval=0, load_path=None, resume=False, scripted_opponents=None):
+          save_dir=None, save_interval=0, load_path=None, resume=False, scripted_opponents=None, local_radius=None,
+          oriented=True):
     """ppo_multi_agent.py:231-404 (hyper-parameters of test/ppo1_single_test.py:42-47 as defaults).
 
     Checkpoints (ppo_multi_agent.py:112-133, 296-306, 349-364, 392-404), weights only, under `save_dir`
@@ -457,18 +550,26 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
     continues a run from save_dir/trainer_state.pt (weights, Adam moments, update counter, pool
     positions -- the reference cannot do this; schedules continue where they stopped).
     `scripted_opponents`, e.g. {1: "safe_greedy"}: those snakes are played by a ScriptedOpponent (a fixed yardstick
-    from update 1 on) instead of a past self; no pool is kept, saved or loaded for them."""
+    from update 1 on) instead of a past self; no pool is kept, saved or loaded for them.
+    `local_radius`: the learner and its network opponents are WindowPolicies over their own snake's head-centred window
+    of that radius (render_local_device) instead of CnnPolicies over the frame; under `oriented` the windows are turned
+    along the heading and the sampled actions are relative to it (relative_to_absolute).  Weights and trainer states
+    carry the radius and the flag: loading the other kind is refused."""
     torch.manual_seed(seed); random.seed(seed)
     dev = env.device
     n_snakes = env.n_snakes
     H, W, _ = env.obs_shape
-    model = CnnPolicy((H, W, 3), amp_dtype=amp_dtype).to(dev)
+    if local_radius is None:
+        make_policy = lambda: CnnPolicy((H, W, 3), amp_dtype=amp_dtype).to(dev)
+    else:
+        make_policy = lambda: WindowPolicy(local_radius, amp_dtype=amp_dtype, oriented=oriented).to(dev)
+    model = make_policy()
     scripted = dict(scripted_opponents or {})
     if any(not 1 <= int(k) < n_snakes for k in scripted):
         raise ValueError(f"scripted_opponents: snake indices must lie in [1, {n_snakes}), got {sorted(scripted)}")
     team = ScriptedColumns(env) if scripted else None   # this run's own: nothing is left behind on the env
     opponents = [ScriptedOpponent(env, scripted[i + 1], i + 1, columns=team) if i + 1 in scripted else
-                 CnnPolicy((H, W, 3), amp_dtype=amp_dtype).to(dev) for i in range(n_snakes - 1)]
+                 make_policy() for i in range(n_snakes - 1)]
     learned = [i for i in range(n_snakes - 1) if i + 1 not in scripted]  # opponent slots played by past selves
     if save_dir:
         os.makedirs(save_dir, exist_ok=True)
@@ -487,6 +588,7 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
                            "pass resume=False to start over (the pool is overwritten) or restore the state file")
     if not fresh:
         ts = torch.load(state_file, map_location=dev, weights_only=True)
+        check_kind(model, ts["model"], state_file)
         model.load_state_dict(ts["model"])
         opt.load_state_dict(ts["optimizer"])
         first_update, model_idx, next_highscore = ts["update"] + 1, ts["model_idx"], ts["next_highscore"]
@@ -511,7 +613,7 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
             pool.save(model)
         if save_dir:  # from the first pool file on there is a state a resume can start from
             save_trainer_state(0)
-    runner = Runner(env, model, opponents, nsteps, gamma, lam)
+    runner = Runner(env, model, opponents, nsteps, gamma, lam, local_radius=local_radius, oriented=oriented)
     nbatch = env.num_envs * nsteps
     nbatch_train = nbatch // nminibatches
     assert nbatch % nminibatches == 0

@@ -110,6 +110,51 @@ def normalize_views(views, n_views):
     return sum(1 << v for v in sel), sel
 
 
+LOCAL_MAX_RADIUS = 31  # MSNAKE_LOCAL_MAX_RADIUS
+CELL_OUTSIDE = 6       # MSNAKE_CELL_OUTSIDE: a window entry of render_local_device() that lies outside the grid
+
+
+def normalize_snakes(snakes, n_snakes):
+    """Selection of snakes for render_local_device -> (snake_mask, list of the selected snakes).
+
+    None = every snake; an int = that snake alone; otherwise a non-empty sequence of strictly ascending snake indices (the
+    windows come out in ascending snake order, so any other order would mislabel them)."""
+    try:
+        mask, sel = normalize_views(snakes, n_snakes)
+    except TypeError:
+        raise ValueError(f"snakes must be None, an int or a sequence of ints, got {snakes!r}") from None
+    except ValueError as err:
+        raise ValueError(str(err).replace("views", "snakes").replace("view indices", "snake indices")
+                         .replace("the planes", "the windows").replace("view order", "snake order")) from None
+    if not sel:
+        raise ValueError("snakes selects no snake: there is no window to write")
+    return mask, sel
+
+
+def check_radius(radius):
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= LOCAL_MAX_RADIUS:
+        raise ValueError(f"radius must be an int in [1, {LOCAL_MAX_RADIUS}], got {radius!r}")
+    return int(radius)
+
+
+def relative_to_absolute(rel, heading):
+    """Relative actions of a heading-aligned window policy -> the absolute actions the step takes (include/msnake.h,
+    msnake_render_local): relative action r in 1..4 = forward, the +j side of the window, backward, the -j side, is the
+    absolute action ((r - 1 + k) mod 4) + 1 under heading k; 0 stays 0.  `rel` and `heading` are integer tensors of one
+    shape, [num_envs] or [num_envs, S] (the heading as render_local_device returns it); the result has rel's dtype and
+    stays on its device."""
+    import torch
+    if not isinstance(rel, torch.Tensor) or not isinstance(heading, torch.Tensor):
+        raise ValueError("rel and heading must be torch tensors")
+    if rel.is_floating_point() or heading.is_floating_point() or rel.dtype == torch.bool or heading.dtype == torch.bool:
+        raise ValueError(f"rel and heading must be integer tensors, got {rel.dtype} and {heading.dtype}")
+    if rel.shape != heading.shape or rel.dim() not in (1, 2):
+        raise ValueError(f"rel and heading must have one shape, [num_envs] or [num_envs, S], got {tuple(rel.shape)} and "
+                         f"{tuple(heading.shape)}")
+    k = heading.to(device=rel.device, dtype=rel.dtype)
+    return torch.where(rel > 0, (rel - 1 + k) % 4 + 1, torch.zeros_like(rel))
+
+
 # constructor arguments that may differ between the two handles of a device-side copy (include/msnake.h,
 # msnake_copy_envs): what MultiSnakeVecEnv.clone() lets a caller override
 CLONE_OVERRIDES = ("record_policy", "envs_per_block", "obs_scale", "auto_reset", "max_steps", "seed", "env_id_base")
@@ -252,6 +297,7 @@ class MultiSnakeVecEnv:
         self._scripted_out = None  # scripted_actions_device(out=None): allocated on first use
         self._space_fn = self._L.msnake_space_actions
         self._cells_fn = self._L.msnake_render_cells
+        self._local_fn = self._L.msnake_render_local
 
     # ------------------------------------------------------------------ device-side API
     def _stream(self):
@@ -464,6 +510,51 @@ class MultiSnakeVecEnv:
         if not sel:
             return snakes_out
         return out if snakes_out is None else (out, snakes_out)
+
+    def local_shape(self, radius, snakes=None):
+        """(S, W, W): one env's windows of render_local_device(radius, snakes), W = 2 * radius + 1."""
+        w = 2 * check_radius(radius) + 1
+        return (len(normalize_snakes(snakes, self.n_snakes)[1]), w, w)
+
+    def render_local_device(self, radius, snakes=None, oriented=True, out=None, heading_out=None, heading=False):
+        """Head-centred windows of cell codes (msnake_render_local): uint8 [num_envs, S, W, W], W = 2 * radius + 1, one
+        window per selected snake in ascending snake order.  Entry [i, j] of snake s shows the cell head + (i - radius) * f
+        + (j - radius) * g in the codes of view s of render_cells_device() (0 empty, 1 fruit, 2 / 3 own body / head, 4 / 5
+        another snake's), or 6 outside the grid; oriented: f is the snake's direction of travel and g the move after it in
+        the move table, so the snake looks along +i whatever its heading; otherwise f = (1, 0), g = (0, 1).  `snakes`:
+        None = every snake, an int, or a strictly ascending sequence.  `heading_out`, a uint8 [num_envs, S] device tensor
+        (heading=True: a fresh one), gets every selected snake's heading 0..3 (relative_to_absolute() takes it).  `out`
+        must be a contiguous uint8 tensor of the shape above on this device; it needs no alignment.  Returns the windows,
+        or (windows, heading) when the heading was asked for; nothing is synchronised.  Draws no random numbers and
+        changes no env state."""
+        torch = self._torch
+        radius = check_radius(radius)
+        mask, sel = normalize_snakes(snakes, self.n_snakes)
+        if isinstance(oriented, (int, np.integer)) and oriented in (0, 1):
+            oriented = int(oriented)
+        else:
+            raise ValueError(f"oriented must be True or False, got {oriented!r}")
+        w = 2 * radius + 1
+        want = (self.num_envs, len(sel), w, w)
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.empty(want, dtype=torch.uint8, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device or
+              tuple(out.shape) != want or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {want} on {self.device}")
+        want = (self.num_envs, len(sel))
+        if heading_out is None and heading:
+            with torch.cuda.device(self.device):
+                heading_out = torch.empty(want, dtype=torch.uint8, device=self.device)
+        elif heading_out is not None:
+            if (not isinstance(heading_out, torch.Tensor) or heading_out.dtype != torch.uint8 or heading_out.device != self.device or
+                    tuple(heading_out.shape) != want or not heading_out.is_contiguous()):
+                raise ValueError(f"heading_out must be a contiguous uint8 tensor of shape {want} on {self.device}")
+        rc = self._local_fn(self._h, radius, mask, oriented, out.data_ptr(),
+                            heading_out.data_ptr() if heading_out is not None else None, self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_render_local")
+        return out if heading_out is None else (out, heading_out)
 
     def rollout_device(self, tape, persistent=True, keep_obs=True):
         """T lockstep steps from an action tape int32 cuda [T, num_envs, >= n_snakes] in ONE call.

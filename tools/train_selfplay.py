@@ -29,7 +29,13 @@ def main():
     ap.add_argument("--resume", action="store_true", help="continue from <--save DIR>/trainer_state.pt")
     ap.add_argument("--opponent", choices=("pool", "safe_greedy", "hamiltonian", "space_greedy"), default="pool",
                     help="who plays the other snakes: past selves from the pool, or a fixed on-device scripted policy")
+    ap.add_argument("--local-radius", type=int, default=None, metavar="R",
+                    help="train window policies on each snake's head-centred (2R+1)x(2R+1) cell-code window instead of the frame")
+    ap.add_argument("--no-orient", action="store_true",
+                    help="with --local-radius: windows in board orientation and absolute actions (default: turned along the heading)")
     args = ap.parse_args()
+    if args.no_orient and args.local_radius is None:
+        ap.error("--no-orient needs --local-radius")
     import torch
     import msnake
     from msnake import selfplay
@@ -39,7 +45,7 @@ def main():
     selfplay.learn(env, nsteps=args.nsteps, total_timesteps=args.timesteps, csv_path=args.csv,
                    monitor_path=args.monitor, json_path=args.json, tb_dir=args.tensorboard,
                    amp_dtype=torch.bfloat16 if args.bf16 else None, save_dir=args.save, save_interval=args.save_interval,
-                   load_path=args.load, resume=args.resume,
+                   load_path=args.load, resume=args.resume, local_radius=args.local_radius, oriented=not args.no_orient,
                    scripted_opponents=None if args.opponent == "pool" else {s: args.opponent for s in range(1, args.snakes)})
     print(env.stats())
     env.close()
