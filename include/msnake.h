@@ -403,6 +403,23 @@ int msnake_kernel_name_for_config(const msnake_config* cfg, char* out, size_t n)
  * process-wide value, so a thread that flips it while another thread is inside msnake_create (or the call above)
  * decides which kernels that handle gets; callers that create handles from several threads set it once, before. */
 int msnake_set_generic_kernels(int32_t on);
+/* Which per-step kernel ONE msnake_step call of a handle with this configuration runs, decided on the host exactly as
+ * the launch glue decides it per call, without a handle and without touching a GPU (tests, tools): the pointers are
+ * only looked at, never dereferenced.
+ *   MSNAKE_CALL_GENERIC  the generic kernel: the configuration has no compile-time shape, the generic kernels are
+ *                        switched on, or action_stride differs from n_snakes
+ *   MSNAKE_CALL_SHAPE    the kernel compiled for the shape
+ *   MSNAKE_CALL_PLAIN    its "plain call" variant: obs, rew, done and info are all given, obs_dev sits on a 128-byte
+ *                        line and num_envs * (observation bytes per env) < 2^31, so the kernel tests no pointer, forms
+ *                        every output address from a 32-bit offset and derives the layout of its observation stores
+ *                        from the env index alone.  Same results, bit for bit.
+ * msnake_kernel_name reports the same name for the last two.  MSNAKE_E_ARG for a configuration msnake_create would
+ * refuse or an action_stride msnake_step would refuse. */
+#define MSNAKE_CALL_GENERIC 0
+#define MSNAKE_CALL_SHAPE 1
+#define MSNAKE_CALL_PLAIN 2
+int msnake_call_shape_for_config(const msnake_config* cfg, int32_t action_stride, const void* obs_dev, const void* rew_dev,
+                                 const void* done_dev, const void* info_dev, int32_t* out);
 int64_t msnake_algorithmic_bytes_per_env_step(msnake_handle h);
 
 #ifdef __cplusplus

@@ -21,6 +21,7 @@ SYMBOLS = [
     "msnake_render", "msnake_get_stats", "msnake_kernel_name", "msnake_algorithmic_bytes_per_env_step",
     "msnake_scripted_actions", "msnake_copy_envs", "msnake_kernel_name_for_config",
     "msnake_set_generic_kernels", "msnake_space_actions", "msnake_render_cells", "msnake_render_local",
+    "msnake_call_shape_for_config",
 ]
 
 
@@ -106,6 +107,9 @@ def load():
     L.msnake_kernel_name_for_config.argtypes = [ctypes.POINTER(MsnakeConfig), ctypes.c_char_p, ctypes.c_size_t]
     L.msnake_kernel_name_for_config.restype = ctypes.c_int
     L.msnake_set_generic_kernels.argtypes = [i32]
+    # cfg, action_stride, obs / rew / done / info (addresses, only looked at), out
+    L.msnake_call_shape_for_config.argtypes = [ctypes.POINTER(MsnakeConfig), i32, vp, vp, vp, vp, ctypes.POINTER(i32)]
+    L.msnake_call_shape_for_config.restype = ctypes.c_int
     L.msnake_set_generic_kernels.restype = ctypes.c_int
     L.msnake_algorithmic_bytes_per_env_step.argtypes = [vp]
     L.msnake_algorithmic_bytes_per_env_step.restype = ctypes.c_int64
@@ -132,6 +136,20 @@ def kernel_name_for_config(cfg):
     buf = ctypes.create_string_buffer(64)
     check(load().msnake_kernel_name_for_config(ctypes.byref(cfg), buf, len(buf)), "msnake_kernel_name_for_config")
     return buf.value.decode()
+
+
+CALL_SHAPE = {0: "generic", 1: "shape", 2: "plain"}  # MSNAKE_CALL_*
+
+
+def call_shape_for_config(cfg, action_stride, obs, rew, done, info):
+    """Which per-step kernel one msnake_step call with these device addresses (integers, 0 / None = absent) gets on a handle
+    created from `cfg` right now: "generic", "shape" (the kernel compiled for the shape) or "plain" (its plain-call
+    variant).  Decided by the library's host glue without a GPU."""
+    apply_kernel_switch()
+    out = ctypes.c_int32(-1)
+    check(load().msnake_call_shape_for_config(ctypes.byref(cfg), action_stride, obs or None, rew or None, done or None,
+                                              info or None, ctypes.byref(out)), "msnake_call_shape_for_config")
+    return CALL_SHAPE[out.value]
 
 
 def check(rc, what="msnake call"):

@@ -728,6 +728,26 @@ int msnake_kernel_name_for_config(const msnake_config* cfg_in, char* out, size_t
     return MSNAKE_OK;
 }
 
+int msnake_call_shape_for_config(const msnake_config* cfg_in, int32_t action_stride, const void* obs_dev, const void* rew_dev,
+                                 const void* done_dev, const void* info_dev, int32_t* out) {
+    if (!cfg_in || !out) return fail(MSNAKE_E_ARG, "msnake_call_shape_for_config: NULL argument");
+    msnake_config cfg;
+    if (int rc = validate_config(cfg_in, &cfg)) return rc;
+    msnake::StepParams p;
+    memset(&p, 0, sizeof(p));
+    if (int rc = derive_shape(&cfg, p)) return rc;
+    if (action_stride < p.n_snakes || action_stride > 7)
+        return fail(MSNAKE_E_ARG, "action_stride %d must be in [n_snakes=%d, 7]", action_stride, p.n_snakes);
+    p.spec_dim = pick_spec_dim(p, cfg.rules);
+    p.action_stride = action_stride;
+    p.obs = static_cast<uint8_t*>(const_cast<void*>(obs_dev));
+    p.rest.rew = static_cast<float*>(const_cast<void*>(rew_dev));
+    p.rest.done = static_cast<uint8_t*>(const_cast<void*>(done_dev));
+    p.rest.info = static_cast<msnake_info*>(const_cast<void*>(info_dev));
+    *out = msnake::call_shape_of(p, 0);
+    return MSNAKE_OK;
+}
+
 int msnake_set_generic_kernels(int32_t on) { return g_generic_kernels.exchange(on ? 1 : 0, std::memory_order_relaxed); }
 
 int64_t msnake_algorithmic_bytes_per_env_step(msnake_handle h) {

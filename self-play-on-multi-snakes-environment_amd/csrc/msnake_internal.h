@@ -143,6 +143,8 @@ hipError_t launch_local(const StepParams& p, int rules, int radius, uint32_t sna
                         uint8_t* heading, hipStream_t stream);
 // the DIM of the compile-time-shape instantiation that fits the configuration in `p` in every folded field, or 0 (host only)
 int spec_dim_of(const StepParams& p, int rules);
+// which kernel one launch gets: MSNAKE_CALL_GENERIC / _SHAPE / _PLAIN of include/msnake.h (host only, no HIP call)
+int call_shape_of(const StepParams& p, int mode);
 // the instantiation that per-step launches run (spec_dim 0: the generic four-parameter one)
 void step_kernel_name(int rules, int n_snakes, int obs_scale, int spec_dim, char* out, size_t n);
 

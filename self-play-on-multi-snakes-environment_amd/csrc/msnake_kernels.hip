@@ -228,6 +228,34 @@ __device__ __forceinline__ void paint_pixel(uint8_t* p, bool head) {
     }
 }
 
+// Plain calls of the compile-time shapes (msnake_step_kernel<.., PLAIN = 1>): what the aligned copy-out of an S-byte image
+// needs, as a function of the env index alone.  kind(i): whether store instruction i (lane l <-> chunk 64 i + l - lead -
+// kmin of nk) is full, empty or partly filled, over every shift (0..15) and lead (0..7) -- only the last kind needs a mask.
+enum { PG_NEVER = 0, PG_PARTIAL = 1, PG_ALWAYS = 2 };
+template <int S_>
+struct PlainGeom {
+    static constexpr int S = S_;
+    static constexpr int kind(int i) {
+        bool any = false, all = true;
+        for (int shift = 0; shift < 16; ++shift) {
+            const int kmin = shift != 0 ? 1 : 0, nk = ((shift + S) >> 4) - kmin;
+            for (int lead = 0; lead < 8; ++lead) {
+                // (the lanes that are on form one run: the first and the last lane decide)
+                const int lo = 64 * i - lead - kmin, hi = lo + 63;
+                const bool lo_on = lo >= 0 && lo < nk, hi_on = hi >= 0 && hi < nk;
+                any = any || lo_on || hi_on || (lo < 0 && hi >= nk && nk > 0);
+                all = all && lo_on && hi_on;
+            }
+        }
+        return all ? PG_ALWAYS : any ? PG_PARTIAL : PG_NEVER;
+    }
+    uint64_t m[4];   // lane masks of the partly filled store instructions
+    uint64_t edge;   // lanes that store one of the <= 15 bytes in front of the first / behind the last whole chunk
+    uint32_t gal;    // (e * S) & ~15: the observation byte of LDS buffer byte 0, behind the base
+    uint32_t k0off;  // -16 * lead
+    uint32_t tail;   // (end & ~15) - 16
+};
+
 // MODE 0: step, 1: reset every env (msnake_reset), 2: render only (msnake_render), 3: n_steps steps of
 //      an action tape in ONE launch with the env kept in registers (msnake_rollout_tape)
 // K: integer pixel replication of the observation fused into the copy-out (the reference's WarpFrame,
@@ -241,7 +269,11 @@ __device__ __forceinline__ void paint_pixel(uint8_t* p, bool head) {
 //      full record.  Everything that follows from those -- S, W, n2, cap, the LDS layout, the divisor -- is a constant
 //      instead of scalar arithmetic that every wave repeats (the scalar port is this kernel's bottleneck).  The launch
 //      glue picks such an instantiation only for a handle and a call that match it in every folded field (spec_dim_of).
-template <int RULES, int NS, int MODE, int K, int DIM = 0>
+// PLAIN: 1 = a "plain call" of a compile-time shape's per-step kernel (plain_call_of: every output present, the observation
+//      base 128-byte aligned, nenv * S < 2^31).  The null tests of obs / info are gone, every output address is a preloaded
+//      SGPR base plus a 32-bit offset (no 64-bit scalar chains), and the geometry of the aligned copy-out is a function of
+//      the env index alone, set up while the wave waits for its loads.  0 = any other call: the code as it was.
+template <int RULES, int NS, int MODE, int K, int DIM = 0, int PLAIN = 0>
 __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     uint8_t* __restrict__ state, uint8_t* __restrict__ obs, const int32_t* __restrict__ actions,
     float* __restrict__ rew_out, uint8_t* __restrict__ done_out, const int32_t nenv, const uint32_t pk0,
@@ -251,6 +283,10 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     constexpr bool SPEC = DIM > 0;
     static_assert(!SPEC || (RULES == MSNAKE_RULES_SNAKE_ENV && K == 1 && (MODE == 0 || MODE == 3) && DIM <= MSNAKE_MAX_DIM),
                   "compile-time shapes: snake_env, native size, step / tape kernels");
+    static_assert(PLAIN == 0 || (SPEC && MODE == 0), "plain calls: the per-step kernels of the compile-time shapes");
+    // the parts of a plain call (each was measured against the build without it, DESIGN.md 4 "Plain calls")
+    constexpr bool FOLD = PLAIN != 0;   // no null tests; reward / done / info / record addresses as base + 32-bit offset
+    constexpr bool EGEOM = PLAIN != 0;  // copy-out geometry from e * S, computed under the load wait and held in SGPRs
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     int lane = (int)(threadIdx.x & 63u);  // (not const: MODE 3 hides it from loop-invariant hoisting, see the step loop)
     const int wave = (int)uni(threadIdx.x >> 6);
@@ -784,10 +820,15 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     }
     // aligned copy-out: where in its LDS buffer the image starts (see CAN_ALIGN)
     // (derived where it is used -- three scalar instructions -- instead of being held in an SGPR for the whole kernel)
+    // (a plain call: the base is 128-byte aligned, so the shift is that of e * S -- computed once, here, for the background
+    //  selection, the painters and the copy-out)
+    const uint32_t pc_eo = EGEOM ? (uint32_t)e * (uint32_t)S : 0u;  // the env's observation, bytes behind the base (< 2^31)
+    const uint32_t pc_shift = pc_eo & 15u;
     auto obs_shift_of = [&]() -> uint32_t {
+        if constexpr (EGEOM) return pc_shift;
         uint32_t ee = (uint32_t)e;
         if (FENCED) asm volatile("" : "+s"(ee));
-        return (align_now && obs_t) ? (((uint32_t)(uintptr_t)obs_t + ee * (uint32_t)S) & 15u) : 0u;
+        return (align_now && (FOLD || obs_t)) ? (((uint32_t)(uintptr_t)obs_t + ee * (uint32_t)S) & 15u) : 0u;
     };
     // background image (black interior, white wall ring): one L1/L2-resident copy shared by every
     // wave, a whole number of 1 KiB wave-instructions so that no lane needs a predicate.
@@ -798,9 +839,9 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     // (Issuing it only after the state has arrived, so that no wave's state load queues behind
     //  another wave's 4 KB of background, was measured too: 6.88 instead of 6.79 us, same box.)
 #ifdef MSNAKE_DBG_STAGES
-    if (obs_t && (!LDSBG || step_i == 0) && !(dbg & 0x100)) {  // (stage bit 8: timing without the background DMA -- wrong images)
+    if ((FOLD || obs_t) && (!LDSBG || step_i == 0) && !(dbg & 0x100)) {  // (stage bit 8: timing without the background DMA -- wrong images)
 #else
-    if (obs_t && (!LDSBG || step_i == 0)) {
+    if ((FOLD || obs_t) && (!LDSBG || step_i == 0)) {
 #endif
         // (aligned copy-out: background number `shift`, the image starts `shift` bytes into it; the offset joins the scalar base)
         const uint4* tsrc = reinterpret_cast<const uint4*>(tmpl_of() + (CAN_ALIGN ? obs_shift_of() * (uint32_t)img_bytes : 0u)) + lane;
@@ -868,6 +909,45 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
             early = philox_draws(b_lo, b_hi, lane, (uint32_t)gid, (uint32_t)(gid >> 32), k0, k1);
             SPAN_FLAG(8u);
         }
+    }
+    // Plain call: the geometry of the aligned copy-out (step 7a) from the env index alone.  With a 128-byte-aligned base the
+    // env's observation starts pc_eo = e * S bytes behind it: shift = pc_eo & 15, lead = (pc_eo >> 4) & 7, and every lane
+    // mask of the copy-out follows.  Computed HERE, between the issue of the loads and their wait, where a scalar
+    // instruction costs the launch nothing, and held in SGPRs; behind the wait the same arithmetic sat on the scalar port
+    // that 16 env-waves share.  What needs a VGPR (addresses) is rebuilt from these by a few VALU instructions at the
+    // point of use.
+    using PG = PlainGeom<(DIM + 2) * (DIM + 2) * C>;
+    PG pg = {};
+    auto plain_geom = [&]() {
+        if constexpr (EGEOM) {
+            const uint32_t lead = (pc_eo >> 4) & 7u;           // chunks between the start of the 128-byte line and the image's first
+            const uint32_t kmin = (pc_shift + 15u) >> 4;       // = shift != 0
+            const uint32_t end = pc_shift + (uint32_t)PG::S;   // the image = buffer bytes [shift, end)
+            const uint32_t nk = (end >> 4) - kmin;
+            const uint32_t rel = (uint32_t)lane - lead - kmin;
+            // (store instruction i: lanes with rel + 64 i < nk; only the instructions that some (shift, lead) leaves partly
+            //  filled get a mask -- the first and the fourth at 19x19, the first and the second at 10x10)
+            if constexpr (PG::kind(0) == PG_PARTIAL) pg.m[0] = ballot(rel < nk);
+            if constexpr (PG::kind(1) == PG_PARTIAL) pg.m[1] = ballot(rel + 64u < nk);
+            if constexpr (PG::kind(2) == PG_PARTIAL) pg.m[2] = ballot(rel + 128u < nk);
+            if constexpr (PG::kind(3) == PG_PARTIAL) pg.m[3] = ballot(rel + 192u < nk);
+            pg.gal = pc_eo - pc_shift;     // LDS buffer byte x <-> observation byte gal + x behind the base
+            pg.k0off = 0u - 16u * lead;    // lane l's first chunk starts at buffer byte 16 l + k0off
+            pg.tail = (end & ~15u) - 16u;  // lanes 16..31: tail byte tail + l
+            const bool head = lane < 16;
+            const uint32_t first = head ? pc_shift : 16u;
+            const uint32_t count = head ? ((16u - pc_shift) & 15u) : (end & 15u);
+            pg.edge = ballot((uint32_t)lane - first < count);
+        }
+    };
+    if constexpr (EGEOM) {
+        plain_geom();
+        // (these pin the values in front of the wait below: left alone, the compiler sinks the arithmetic to the copy-out)
+        if constexpr (PG::kind(0) == PG_PARTIAL) asm volatile("" : "+s"(pg.m[0]));
+        if constexpr (PG::kind(1) == PG_PARTIAL) asm volatile("" : "+s"(pg.m[1]));
+        if constexpr (PG::kind(2) == PG_PARTIAL) asm volatile("" : "+s"(pg.m[2]));
+        if constexpr (PG::kind(3) == PG_PARTIAL) asm volatile("" : "+s"(pg.m[3]));
+        asm volatile("" : "+s"(pg.edge), "+s"(pg.gal), "+s"(pg.k0off), "+s"(pg.tail));
     }
     // every load issued so far (state, actions, background) has landed past this point: the env
     // logic needs the state right away, and the painters must find the background in LDS.  In MODES
@@ -1398,7 +1478,20 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
         STAMP_FLAG((unsigned long long)(any_eat ? 1 : 0) | (done ? 2ull : 0ull));
         SPAN_FLAG((any_eat ? 1u : 0u) | (done ? 2u : 0u));
         SPAN(2);
-        if (lane == 0) {
+        if (FOLD) {
+            if (lane == 0) {
+                // (every output is there, and its address is the preloaded base plus a 32-bit VECTOR offset, the form the
+                //  state loads use; the asm hides that the offset is uniform -- as a scalar it becomes a 64-bit
+                //  shift / add / add-with-carry chain per output on the scalar port)
+                uint32_t ev = (uint32_t)e;
+                asm volatile("" : "+v"(ev));
+                *reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(rew_t) + (size_t)(ev * 4u)) = reward;
+                done_t[(size_t)ev] = (uint8_t)done;
+                int4 iv;
+                iv.x = (int)__float_as_uint(out_ret); iv.y = (int)out_len; iv.z = num_alive; iv.w = (int)done;
+                *reinterpret_cast<int4*>(reinterpret_cast<uint8_t*>(info_t) + (size_t)(ev * 16u)) = iv;
+            }
+        } else if (lane == 0) {
             rew_t[e] = reward;
             done_t[e] = (uint8_t)done;
             if (info_t) {
@@ -1412,7 +1505,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     // ---- 6. paint the observation over the background, in reference order ----------------------
     LANE_FENCE();
     CONFIG_FENCE();
-    if (obs_t) {
+    if (FOLD || obs_t) {
 #ifdef MSNAKE_PRIO_PAINT
         __builtin_amdgcn_s_setprio(MSNAKE_PRIO_PAINT);
 #endif
@@ -1484,7 +1577,38 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
             if (pad == 0xDEADBEEFu) hv = pad;
         }
 #endif
-        if (align_now) {
+        if constexpr (EGEOM) {
+            // ---- 7a'. the aligned copy-out of a plain call: the same chunks, lanes and bytes as 7a below, from the
+            //           geometry that plain_geom derived from the env index; both addresses are 32-bit offsets (the global
+            //           one joins the preloaded base in the store itself)
+            const uint32_t k0b = ((uint32_t)lane << 4) + pg.k0off;  // 16 * (lane - lead)
+            const uint8_t* lsrc = img + (int32_t)k0b;
+            uint8_t* gdst = obs_t + (size_t)(pg.gal + k0b);          // (>= the base: gal - 16 lead is the start of a 128-byte line)
+            auto chunks = [&](auto NT) {
+                auto one = [&](auto I) {
+                    constexpr int i = decltype(I)::value;
+                    if constexpr (PG::kind(i) != PG_NEVER) {
+                        if (PG::kind(i) == PG_ALWAYS || in_mask(pg.m[i])) {
+                            const u32x4 v = *reinterpret_cast<const u32x4*>(lsrc + 1024 * i);
+                            if constexpr (decltype(NT)::value) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(gdst + 1024 * i));
+                            else *reinterpret_cast<u32x4*>(gdst + 1024 * i) = v;
+                            // (keeps the two copies of the store apart, see 7a)
+                            if constexpr (decltype(NT)::value) asm volatile("; streaming copy-out" ::: "memory");
+                            else asm volatile("; plain copy-out" ::: "memory");
+                        }
+                    }
+                };
+                one(std::integral_constant<int, 0>{}); one(std::integral_constant<int, 1>{});
+                one(std::integral_constant<int, 2>{}); one(std::integral_constant<int, 3>{});
+            };
+            static_assert(!EGEOM || ((PG::S + 15) >> 4) + 7 <= 256, "plain calls: the image fits the four store instructions");
+            if (pk2 & PK2_STREAM_OBS) chunks(std::true_type{});
+            else chunks(std::false_type{});
+            if (in_mask(pg.edge)) {
+                const uint32_t byte = lane < 16 ? (uint32_t)lane : pg.tail + (uint32_t)lane;
+                obs_t[(size_t)(pg.gal + byte)] = img[byte];
+            }
+        } else if (align_now) {
             // ---- 7a. aligned copy-out (per-step launches; tapes whose step stride is a multiple of 16 bytes): LDS byte x of the buffer <-> global byte g_al + x, both sides
             //          16-byte aligned; wave instruction i covers the i-th KiB counted from the 128-byte line the image
             //          starts in, so every store instruction writes whole lines (WRITE_SIZE 1.00-1.02 x the image; the
@@ -1680,7 +1804,9 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
             // (round 3: the nt hint on this store, on the ring-sector stores and on the reward store -- nothing left dirty in the
             //  L2s for the end-of-kernel release -- changes nothing: 5.77-5.79 / 5.76-5.79 vs 5.75-5.78 us, and costs with the
             //  4-byte reward stores in: 5.92-5.95)
-            (reinterpret_cast<uint32_t*>(state) + (size_t)ee * MSNAKE_HDR_WORDS)[lane] = hv;
+            if (FOLD)  // (32-bit offset, like the load)
+                *reinterpret_cast<uint32_t*>(state + (size_t)(ee * (uint32_t)(MSNAKE_HDR_WORDS * 4) + (uint32_t)lane * 4u)) = hv;
+            else (reinterpret_cast<uint32_t*>(state) + (size_t)ee * MSNAKE_HDR_WORDS)[lane] = hv;
         }
         if (RULES == MSNAKE_RULES_ADVERSARIAL && fr_dirty) fl0_of()[lane] = (uint16_t)fr;
     }
@@ -1963,6 +2089,24 @@ static int spec_dim_now(const StepParams& p, int mode) {
     return (p.spec_dim != 0 && (mode == 0 || mode == 3) && p.action_stride == p.n_snakes) ? p.spec_dim : 0;
 }
 
+// Which per-step kernel one call gets (host only, no HIP call): the generic one, the handle's compile-time shape, or the
+// shape's plain-call variant -- every output present, the observation base on a 128-byte line, and byte offsets into the
+// observations that fit 31 bits.  Chosen per launch, like the action_stride test above.
+int call_shape_of(const StepParams& p, int mode) {
+    if (spec_dim_now(p, mode) == 0) return MSNAKE_CALL_GENERIC;
+    if (mode != 0) return MSNAKE_CALL_SHAPE;
+    const bool plain = p.obs && p.rest.info && p.rest.rew && p.rest.done && ((uintptr_t)p.obs & 127u) == 0 &&
+                       (uint64_t)p.nenv * (uint64_t)p.S < (1ull << 31);
+    return plain ? MSNAKE_CALL_PLAIN : MSNAKE_CALL_SHAPE;
+}
+// (the stage bits that thin out the observation stores, and the A/B build without the aligned copy-out, live in the
+//  variant-0 code only: those builds never launch the plain-call variant)
+#if defined(MSNAKE_DBG_STAGES) || defined(MSNAKE_NO_ALIGN)
+static constexpr bool PLAIN_BUILT = false;
+#else
+static constexpr bool PLAIN_BUILT = true;
+#endif
+
 template <int RULES, int NS, int K>
 static hipError_t launch_k(const StepParams& p, int mode, int epb, hipStream_t stream) {
     const uint32_t pk0 = (uint32_t)p.dim | ((uint32_t)p.n_fruits << 6) | ((uint32_t)p.action_stride << 12) |
@@ -1989,15 +2133,17 @@ static hipError_t launch_k(const StepParams& p, int mode, int epb, hipStream_t s
                          (div_magic((uint32_t)p.dim) << PK2_DIVM_SHIFT);
     const dim3 grid((unsigned)((((p.nenv + epb - 1) / epb) + 63) & ~63));  // whole groups of 64: see the kernel's XCD swap
     const dim3 block(64u * (unsigned)epb);
-#define MSNAKE_LAUNCH_D(M, D)                                                                                     \
-    hipLaunchKernelGGL((msnake_step_kernel<RULES, NS, M, K, D>), grid, block, lds, stream, p.state, p.obs, p.actions, \
+#define MSNAKE_LAUNCH_DP(M, D, P)                                                                                    \
+    hipLaunchKernelGGL((msnake_step_kernel<RULES, NS, M, K, D, P>), grid, block, lds, stream, p.state, p.obs, p.actions, \
                        p.rest.rew, p.rest.done, p.nenv, pk0, pk1, pk2, p.rest)
+#define MSNAKE_LAUNCH_D(M, D) MSNAKE_LAUNCH_DP(M, D, 0)
 #define MSNAKE_LAUNCH(M) MSNAKE_LAUNCH_D(M, 0)
     constexpr int SPEC_DIM = has_spec(RULES, NS, K, 19) ? 19 : has_spec(RULES, NS, K, 10) ? 10 : 0;
     if constexpr (SPEC_DIM != 0) {
         if (spec_dim_now(p, mode) == SPEC_DIM) {
-            if (mode == 0) MSNAKE_LAUNCH_D(0, SPEC_DIM);
-            else MSNAKE_LAUNCH_D(3, SPEC_DIM);
+            if (mode == 3) MSNAKE_LAUNCH_D(3, SPEC_DIM);
+            else if (PLAIN_BUILT && call_shape_of(p, mode) == MSNAKE_CALL_PLAIN) MSNAKE_LAUNCH_DP(0, SPEC_DIM, 1);
+            else MSNAKE_LAUNCH_D(0, SPEC_DIM);
             return hipGetLastError();
         }
     }
@@ -2009,6 +2155,7 @@ static hipError_t launch_k(const StepParams& p, int mode, int epb, hipStream_t s
     }
 #undef MSNAKE_LAUNCH
 #undef MSNAKE_LAUNCH_D
+#undef MSNAKE_LAUNCH_DP
     return hipGetLastError();
 }
 

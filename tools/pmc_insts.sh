@@ -19,7 +19,7 @@ print("bench: us/step", d["roofline"]["launch_us"], "frac", d["roofline"]["frac"
 f = glob.glob("$OUT/pmc_insts/**/*counter_collection.csv", recursive=True)
 acc = collections.defaultdict(list)
 for r in csv.DictReader(open(f[0])):
-    if re.search(r"msnake_step_kernel<\\d, \\d, 0, 1(, \\d+)?>", r["Kernel_Name"]):  # (generic or compile-time shape)
+    if re.search(r"msnake_step_kernel<\\d, \\d, 0, 1(, \\d+){0,2}>", r["Kernel_Name"]):  # (generic or compile-time shape)
         acc[r["Counter_Name"]].append(float(r["Counter_Value"]))
 w = statistics.median(acc["SQ_WAVES"])
 print("per wave:", {k.replace("SQ_INSTS_", ""): round(statistics.median(v) / w, 1) for k, v in sorted(acc.items())})
