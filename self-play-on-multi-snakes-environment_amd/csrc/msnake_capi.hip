@@ -100,12 +100,12 @@ void note_offgrid_head(msnake_env* h) {
 
 const char* state_reason(uint32_t code) {
     switch (code) {
-        case 1: return "state buffer too short / truncated";
-        case 2: return "snake count differs from the handle's";
-        case 3: return "fruit count differs from the handle's (or exceeds the fruit-list capacity)";
-        case 4: return "a cell lies outside [-1, dim], or a body piece behind the head outside the grid";
-        case 5: return "a body length is outside [0, capacity]";
-        case 6: return "a scalar field out of range (t, spare_fruits, ep_len or grow_to negative, a velocity that is no unit step, alive / in_dead)";
+        case MSNAKE_ST_SHORT: return "state buffer too short / truncated";
+        case MSNAKE_ST_SNAKES: return "snake count differs from the handle's";
+        case MSNAKE_ST_FRUITS: return "fruit count differs from the handle's (or exceeds the fruit-list capacity)";
+        case MSNAKE_ST_CELL: return "a cell lies outside [-1, dim], or a body piece behind the head outside the grid";
+        case MSNAKE_ST_LEN: return "a body length is outside [0, capacity]";
+        case MSNAKE_ST_SCALAR: return "a scalar field out of range (t, spare_fruits, ep_len or grow_to negative, a velocity that is no unit step, alive / in_dead)";
         default: return "malformed state";
     }
 }
@@ -150,7 +150,7 @@ int validate_config(const msnake_config* cfg_in, msnake_config* cfg_full) {
     }
     if (cfg->max_steps < 1 || cfg->max_steps > 60000)
         return fail(MSNAKE_E_ARG, "max_steps must be in [1, 60000]");
-    if ((uint64_t)cfg->num_envs * (uint64_t)(MSNAKE_HDR_WORDS * 4 + MSNAKE_MAX_SNAKES * 128) >= (1ull << 32))
+    if ((uint64_t)cfg->num_envs * (uint64_t)msnake::shape::fixed_bytes(MSNAKE_MAX_SNAKES) >= (1ull << 32))
         return fail(MSNAKE_E_ARG, "num_envs %d: records and body rings of one handle must stay below 4 GB (the kernel "
                                   "addresses them with 32-bit offsets); use several handles", cfg->num_envs);
     if (cfg->obs_scale != 1 && cfg->obs_scale != 4 && cfg->obs_scale != 7)
@@ -168,6 +168,7 @@ int validate_config(const msnake_config* cfg_in, msnake_config* cfg_full) {
 // Everything of StepParams that follows from the configuration alone: the shape of the observation, of the state and of
 // the LDS image, and the record policy.  No GPU involved (msnake_kernel_name_for_config runs it without one).
 int derive_shape(const msnake_config* cfg, msnake::StepParams& p) {
+    namespace shape = msnake::shape;
     const int dim = cfg->dim, W = dim + 2, n2 = dim * dim;
     p.nenv = cfg->num_envs;
     p.dim = dim;
@@ -175,7 +176,7 @@ int derive_shape(const msnake_config* cfg, msnake::StepParams& p) {
     p.n_fruits = cfg->n_fruits;
     p.views = cfg->rules == MSNAKE_RULES_NEW_WORLD ? cfg->n_snakes : 3;
     p.C = 3 * p.views;
-    p.S = W * W * p.C;
+    p.S = shape::obs_bytes(dim, p.C);
     p.obs_scale = cfg->obs_scale;
     p.rest.max_steps = cfg->max_steps;
     p.auto_reset = cfg->auto_reset ? 1 : 0;
@@ -183,11 +184,11 @@ int derive_shape(const msnake_config* cfg, msnake::StepParams& p) {
     // new_world bodies can stack duplicates and are only bounded by the episode length
     int need = n2 + 2;
     if (cfg->rules == MSNAKE_RULES_NEW_WORLD && cfg->max_steps + 2 > need) need = cfg->max_steps + 2;
-    p.rest.cap = (need + 63) / 64 * 64;
+    p.rest.cap = shape::ring_cap(need);
     const int K = cfg->obs_scale;
     if (K > 1 && (W * K * p.C) % 4 != 0) return fail(MSNAKE_E_ARG, "obs_scale %d: output rows must be whole dwords", K);
-    p.img_bytes = (p.S * K + (K == 1 ? 15 : 0) + 1023) / 1024 * 1024;  // K-fold wide image, whole 1 KiB wave-instructions
-    p.lds_per_wave = p.img_bytes + (n2 + 15) / 16 * 16;  // composed image + respawn occupancy
+    p.img_bytes = shape::img_bytes(p.S, K);
+    p.lds_per_wave = shape::lds_per_wave(p.img_bytes, n2, false);
     if ((size_t)p.lds_per_wave > 64 * 1024 - 16 || p.S > 0xFFFF)
         return fail(MSNAKE_E_ARG, "observation image of %d bytes does not fit in LDS", p.S);
     // record_policy: snake_env / adversarial steps can run on the first 128 bytes of the 256-byte
@@ -244,16 +245,11 @@ int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
     h->epb = p.nenv <= 8192 ? MSNAKE_MAX_ENVS_PER_BLOCK : 4;
     while (h->epb > 1 && (size_t)h->epb * p.lds_per_wave > 64 * 1024) h->epb >>= 1;
 
-    const size_t hdr_bytes = (size_t)p.nenv * MSNAKE_HDR_WORDS * 4;
-    const size_t body0_bytes = (size_t)p.nenv * p.n_snakes * 64 * 2;
     const int tmpl_copies = K == 1 ? MSNAKE_TMPL_COPIES : 1;
     const size_t tmpl_bytes = (size_t)p.img_bytes * tmpl_copies;
-    const size_t ring_bytes = (size_t)p.nenv * p.n_snakes * p.rest.cap * 2;
-    const bool adv = cfg->rules == MSNAKE_RULES_ADVERSARIAL;
-    p.fcap = (p.n_snakes + p.n_snakes * (n2 + 2) + 63) / 64 * 64;  // n fruits + every body of one episode
-    const size_t fl0_bytes = adv ? (size_t)p.nenv * 64 * 2 : 0;
-    const size_t flist_bytes = adv ? (size_t)p.nenv * p.fcap * 2 : 0;
-    const size_t state_bytes = hdr_bytes + body0_bytes + tmpl_bytes + ring_bytes + fl0_bytes + flist_bytes;
+    p.fcap = msnake::shape::fruit_cap(p.n_snakes, n2);
+    const auto sec = msnake::shape::sections(p.nenv, p.n_snakes, tmpl_bytes, p.rest.cap, p.fcap, cfg->rules);
+    const size_t state_bytes = sec.total;
     hipError_t e;
     if ((e = hipMalloc(&h->d_state, state_bytes)) != hipSuccess || (e = hipMalloc(&h->d_stats, 64)) != hipSuccess ||
         (e = hipMemset(h->d_state, 0, state_bytes)) != hipSuccess || (e = hipMemset(h->d_stats, 0, 64)) != hipSuccess) {
@@ -262,12 +258,12 @@ int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
         return fail(MSNAKE_E_HIP, "allocating %zu bytes of env state failed: %s", state_bytes, hipGetErrorString(e));
     }
     p.state = static_cast<uint8_t*>(h->d_state);
-    p.hdr = reinterpret_cast<uint32_t*>(p.state);
-    p.body0 = reinterpret_cast<uint16_t*>(p.state + hdr_bytes);
-    p.tmpl = p.state + hdr_bytes + body0_bytes;
-    p.ring = reinterpret_cast<uint16_t*>(p.state + hdr_bytes + body0_bytes + tmpl_bytes);
-    p.fl0 = reinterpret_cast<uint16_t*>(p.state + hdr_bytes + body0_bytes + tmpl_bytes + ring_bytes);
-    p.flist = reinterpret_cast<uint16_t*>(p.state + hdr_bytes + body0_bytes + tmpl_bytes + ring_bytes + fl0_bytes);
+    p.hdr = reinterpret_cast<uint32_t*>(p.state + sec.hdr);
+    p.body0 = reinterpret_cast<uint16_t*>(p.state + sec.body0);
+    p.tmpl = p.state + sec.tmpl;
+    p.ring = reinterpret_cast<uint16_t*>(p.state + sec.ovf);
+    p.fl0 = reinterpret_cast<uint16_t*>(p.state + sec.fl0);
+    p.flist = reinterpret_cast<uint16_t*>(p.state + sec.flist);
     p.stats = static_cast<unsigned long long*>(h->d_stats);
     // background image: black interior, white 1-px wall ring (snake_multiple_test.py:38,52-56)
     std::vector<uint8_t> tmpl(tmpl_bytes, 0);
@@ -581,7 +577,7 @@ int state_import(msnake_env* h, int env0, int count, const uint64_t* offsets, co
     const size_t off_bytes = ((size_t)count + 1) * 8, word_bytes = (size_t)offsets[count] * 4;
     if (int rc = ensure_scratch(h, 16 + off_bytes + word_bytes)) return rc;
     uint8_t* d = static_cast<uint8_t*>(h->d_scratch);
-    // [0] rejected envs, [1] min over them of (local index + 1) << 8 | reason, [2] != 0: an accepted env has a head outside the grid
+    // [0] rejected envs, [1] min over them of status_pack(local index, reason), [2] != 0: an accepted env has a head outside the grid
     const uint32_t st0[4] = {0u, 0xFFFFFFFFu, 0u, 0u};
     HIP_TRY(hipMemcpy(d, st0, 16, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d + 16, offsets, off_bytes, hipMemcpyHostToDevice));
@@ -594,7 +590,7 @@ int state_import(msnake_env* h, int env0, int count, const uint64_t* offsets, co
     if (st[2] != 0) note_offgrid_head(h);  // some accepted env has a head outside the grid
     if (st[0] != 0)
         return fail(MSNAKE_E_STATE, "%u env state(s) rejected; first: env %d: %s (the rejected envs were left untouched)", st[0],
-                    env0 + (int)(st[1] >> 8) - 1, state_reason(st[1] & 0xFFu));
+                    env0 + msnake::status_env(st[1]), state_reason(msnake::status_reason(st[1])));
     return MSNAKE_OK;
 }
 

@@ -58,14 +58,8 @@ __global__ __launch_bounds__(CELLS_WAVES * 64) void msnake_cells_kernel(CellsArg
             const uint32_t wA = rdlane(hv, SN_A(s)), wB = rdlane(hv, SN_B(s)), wC = rdlane(hv, SN_C(s));
             const int len = (int)(wA >> 16), vel = (int)((wC >> 16) & 7u);
             const uint32_t head = rdlane(ring[s], (int)((wC >> SN_C_HP0_SHIFT) & 63u));  // piece 0 sits in ring slot hp0
-            const int32_t f[8] = {len,
-                                  len > 0 ? (int32_t)(head >> 8) - 1 : -2,
-                                  len > 0 ? (int32_t)(head & 255u) - 1 : -2,
-                                  vel == 1 ? 1 : vel == 3 ? -1 : 0,
-                                  vel == 2 ? 1 : vel == 4 ? -1 : 0,
-                                  (int32_t)wB,
-                                  nw ? (int32_t)((flags >> s) & 1u) : 1,
-                                  nw ? (int32_t)((flags >> (4 + s)) & 1u) : 0};
+            const int32_t f[8] = {len, len > 0 ? cell_c0(head) : -2, len > 0 ? cell_c1(head) : -2, vel_v0(vel), vel_v1(vel),
+                                  (int32_t)wB, snake_alive(flags, s, nw), snake_in_dead(flags, s, nw)};
 #pragma unroll
             for (int k = 0; k < 8; ++k)
                 if (lane == 8 * s + k) field = f[k];
@@ -84,7 +78,7 @@ __global__ __launch_bounds__(CELLS_WAVES * 64) void msnake_cells_kernel(CellsArg
 
     // a cell inside the grid takes, in every plane, the phase's code for that plane; anything else is not stored
     auto paint = [&](uint32_t c, bool valid, int snake, uint32_t own, uint32_t other) {
-        const int c0 = (int)(c >> 8) - 1, c1 = (int)(c & 255u) - 1;
+        const int c0 = cell_c0(c), c1 = cell_c1(c);
         if (valid && c0 >= 0 && c0 < dim && c1 >= 0 && c1 < dim) {
             uint8_t* p = img + c0 * dim + c1;
 #pragma unroll

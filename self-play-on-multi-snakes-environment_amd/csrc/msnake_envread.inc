@@ -67,7 +67,7 @@ struct EnvReader {
             r.hp0 = (int)((word(SN_C(s)) >> SN_C_HP0_SHIFT) & 63u);
             if (r.len > 0) {
                 r.head = rdlane(ring[s], r.hp0);  // piece 0 sits in ring slot hp0
-                r.x = (int)(r.head >> 8) - 1; r.y = (int)(r.head & 255u) - 1;
+                r.x = cell_c0(r.head); r.y = cell_c1(r.head);
             }
         }
         return r;

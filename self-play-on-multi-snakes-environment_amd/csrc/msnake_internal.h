@@ -58,7 +58,86 @@
 
 #define MSNAKE_NO_CELL 0xFFFFu  // never equals a real cell (rows/cols <= 63)
 
+// why msnake_state_unpack_kernel rejects an env (state_reason() in msnake_capi.hip has the texts)
+enum {
+    MSNAKE_ST_SHORT = 1,   // buffer too short / truncated
+    MSNAKE_ST_SNAKES = 2,  // snake count differs from the handle
+    MSNAKE_ST_FRUITS = 3,  // fruit count differs from the handle / exceeds the list capacity
+    MSNAKE_ST_CELL = 4,    // a cell outside [-1, dim]
+    MSNAKE_ST_LEN = 5,     // a body length outside [0, cap - 2]
+    MSNAKE_ST_SCALAR = 6   // a scalar field out of range: t, spare_fruits, ep_len, grow_to, a velocity, alive / in_dead
+};
+
+#define MSNAKE_HD __host__ __device__ __forceinline__ constexpr
+
 namespace msnake {
+
+// ------------------------------------------------------------------------------------------------
+// The shape numbers and the sections of the state allocation: THE definition, for the host glue (derive_shape,
+// msnake_create, spec_dim_of, launch_k) and for the kernels alike.
+// ------------------------------------------------------------------------------------------------
+namespace shape {
+MSNAKE_HD int obs_bytes(int dim, int C) { return (dim + 2) * (dim + 2) * C; }  // S: the wall ring included
+MSNAKE_HD int ring_cap(int need) { return (need + 63) & ~63; }  // overflow ring: `need` cells (dim^2 + 2, new_world max_steps + 2) in whole waves
+// LDS image, K-fold wide, in whole 1 KiB wave-instructions (native size: + room for the image's shift of up to 15 bytes)
+MSNAKE_HD int img_bytes(int S, int K) { return (S * K + (K == 1 ? 15 : 0) + 1023) & ~1023; }
+MSNAKE_HD int occ_bytes(int n2) { return (n2 + 15) & ~15; }  // respawn occupancy behind the image
+// LDS per env: the image being composed, the occupancy, and (the tape kernel at native size) the pristine background
+MSNAKE_HD int lds_per_wave(int img, int n2, bool ldsbg) { return img + occ_bytes(n2) + (ldsbg ? img : 0); }
+MSNAKE_HD int fruit_cap(int ns, int n2) { return (ns + ns * (n2 + 2) + 63) & ~63; }  // [A] list: n fruits + every body of one episode
+MSNAKE_HD int fixed_bytes(int ns) { return MSNAKE_HDR_WORDS * 4 + ns * 128; }  // per env: record + the 64-slot ring of every snake
+
+// byte offsets into the ONE allocation [hdr | body0 | tmpl | ovf | fl0 | flist]; fl0 and flist are empty unless adversarial
+struct Sections { size_t hdr, body0, tmpl, ovf, fl0, flist, total; };
+MSNAKE_HD Sections sections(int nenv, int ns, size_t tmpl_bytes, int cap, int fcap, int rules) {
+    const size_t n = (size_t)nenv, adv = rules == MSNAKE_RULES_ADVERSARIAL ? 1 : 0;
+    const size_t tmpl = n * (size_t)fixed_bytes(ns), ovf = tmpl + tmpl_bytes, fl0 = ovf + n * ns * cap * 2, flist = fl0 + adv * n * 128;
+    return Sections{0, n * (MSNAKE_HDR_WORDS * 4), tmpl, ovf, fl0, flist, flist + adv * n * fcap * 2};
+}
+
+// the compile-time shapes of the step kernel, and one layout by hand
+static_assert(obs_bytes(19, 9) == 3969 && img_bytes(3969, 1) == 4096 && ring_cap(19 * 19 + 2) == 384 && occ_bytes(361) == 368, "19x19x9");
+static_assert(lds_per_wave(4096, 361, false) == 4464 && lds_per_wave(4096, 361, true) == 8560 && fruit_cap(3, 361) == 1152 && fruit_cap(2, 361) == 768, "19x19x9");
+static_assert(obs_bytes(10, 9) == 1296 && img_bytes(1296, 1) == 2048 && ring_cap(10 * 10 + 2) == 128 && occ_bytes(100) == 112, "10x10x9");
+static_assert(lds_per_wave(2048, 100, false) == 2160 && fruit_cap(1, 100) == 128 && img_bytes(3969, 4) == 16384, "10x10x9, fused x4");
+static_assert(fixed_bytes(3) == 640 && fixed_bytes(MSNAKE_MAX_SNAKES) == 768, "record + rings");
+constexpr Sections kPinned = sections(2, 3, 16 * 4096, 384, 1152, MSNAKE_RULES_ADVERSARIAL);
+static_assert(kPinned.hdr == 0 && kPinned.body0 == 512 && kPinned.tmpl == 1280 && kPinned.ovf == 66816 && kPinned.fl0 == 71424 &&
+              kPinned.flist == 71680 && kPinned.total == 76288, "2 adversarial envs, 3 snakes, 19x19");
+static_assert(sections(2, 3, 16 * 4096, 384, 1152, MSNAKE_RULES_SNAKE_ENV).total == 71424, "no fruit list: the rings end the allocation");
+}  // namespace shape
+
+// ------------------------------------------------------------------------------------------------
+// The codes the state is written in.  A cell: 16 bits, (row << 8) | col in PADDED observation coordinates, row = c0 + 1,
+// col = c1 + 1, so the grid is 1..dim and one step outside lands on the wall ring 0 / dim + 1.  A velocity: 0 = at rest,
+// 1..4 = (1, 0), (0, 1), (-1, 0), (0, -1) -- action m + 1 keeps moving by move m's delta.
+// ------------------------------------------------------------------------------------------------
+// (The same as macros, for three sites whose instructions change when the expression goes through a function: the
+//  painters of msnake_space.inc and msnake_local.inc, and the one encoder of velocities, msnake_state_unpack_kernel.)
+#define MSNAKE_CELL_C0(c) ((int)((c) >> 8) - 1)
+#define MSNAKE_CELL_C1(c) ((int)((c) & 255u) - 1)
+#define MSNAKE_VEL_CODE(v0, v1) \
+    (((v0) == 1 && (v1) == 0) ? 1 : ((v0) == 0 && (v1) == 1) ? 2 : ((v0) == -1 && (v1) == 0) ? 3 : ((v0) == 0 && (v1) == -1) ? 4 : 0)
+MSNAKE_HD uint32_t cell_pack(int c0, int c1) { return ((uint32_t)(c0 + 1) << 8) | (uint32_t)(c1 + 1); }
+MSNAKE_HD int cell_c0(uint32_t c) { return MSNAKE_CELL_C0(c); }
+MSNAKE_HD int cell_c1(uint32_t c) { return MSNAKE_CELL_C1(c); }
+MSNAKE_HD int vel_v0(int vel) { return vel == 1 ? 1 : vel == 3 ? -1 : 0; }
+MSNAKE_HD int vel_v1(int vel) { return vel == 2 ? 1 : vel == 4 ? -1 : 0; }
+MSNAKE_HD int move_d0(int m) { return m == 0 ? 1 : m == 2 ? -1 : 0; }  // move m = action m + 1
+MSNAKE_HD int move_d1(int m) { return m == 1 ? 1 : m == 3 ? -1 : 0; }
+static_assert(cell_pack(-1, 18) == 19 && cell_c0(cell_pack(7, 0)) == 7 && cell_c1(cell_pack(7, 0)) == 0, "cell code");
+static_assert(MSNAKE_VEL_CODE(vel_v0(3), vel_v1(3)) == 3 && MSNAKE_VEL_CODE(move_d0(1), move_d1(1)) == 2 && MSNAKE_VEL_CODE(0, 0) == 0, "velocity code");
+
+// the alive / in_dead words of the canonical state and of msnake_render_cells' table, out of HDR_FLAGS (only new_world
+// keeps the bits: elsewhere a snake is alive and not in dead_snakes)
+MSNAKE_HD int32_t snake_alive(uint32_t flags, int s, bool nw) { return nw ? (int32_t)((flags >> s) & 1u) : 1; }
+MSNAKE_HD int32_t snake_in_dead(uint32_t flags, int s, bool nw) { return nw ? (int32_t)((flags >> (4 + s)) & 1u) : 0; }
+
+// msnake_set_state's status word: (local env index + 1) in bits 8.., the MSNAKE_ST_* reason below (ONE atomicMin on ~0u
+// gives index and reason of the first rejected env)
+MSNAKE_HD uint32_t status_pack(int local, int reason) { return (((uint32_t)local + 1u) << 8) | (uint32_t)reason; }
+MSNAKE_HD int status_env(uint32_t st) { return (int)(st >> 8) - 1; }
+MSNAKE_HD uint32_t status_reason(uint32_t st) { return st & 0xFFu; }
 
 // kernel arguments that did not fit the 13 preloaded dwords, passed by value behind them
 struct StepRest {

@@ -133,10 +133,7 @@ __device__ __forceinline__ uint32_t philox_draws(uint32_t base_lo, uint32_t base
     return sel == 0 ? c0 : sel == 1 ? c1 : sel == 2 ? c2 : c3;
 }
 
-// ------------------------------------------------------------------------------------------------
-// cells: 16 bits, (row << 8) | col in PADDED observation coordinates: row = c0 + 1, col = c1 + 1,
-// so the grid is 1..dim and one step outside lands on the wall ring 0 / dim+1.
-// ------------------------------------------------------------------------------------------------
+// the step kernel's own arithmetic on cells (the code itself: msnake_internal.h), in padded coordinates
 __device__ __forceinline__ int cell_step(int v) {  // velocity code -> cell delta
     return v == 1 ? 256 : v == 2 ? 1 : v == 3 ? -256 : v == 4 ? -1 : 0;
 }
@@ -174,7 +171,6 @@ __device__ __forceinline__ uint32_t hv_writelane_unrolled(uint32_t old, uint32_t
     }
 }
 #define HV_SET_U(idx, val) hv = hv_writelane_unrolled(hv, (uint32_t)(val), (uint32_t)(idx))
-#define HV_SET_DYN(idx, val) HV_SET(idx, val)
 
 typedef uint4 __attribute__((aligned(1))) uint4_unaligned;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -256,6 +252,16 @@ struct PlainGeom {
     uint32_t tail;   // (end & ~15) - 16
 };
 
+// The forms in which msnake_step_kernel spells its section offsets (hdr_g, body0_g, tmpl_of, ring_of, fl0_of, flist_of),
+// on one sample, against the definition -- at namespace scope: a constant inside the kernel changes its instructions.
+constexpr bool kernel_sections_ok(int ns, size_t tmpl_bytes) {
+    const shape::Sections sec = shape::sections(5, ns, tmpl_bytes, 192, 320, MSNAKE_RULES_ADVERSARIAL);
+    return sec.hdr == 0 && sec.body0 == 5 * (MSNAKE_HDR_WORDS * 4) && sec.tmpl == 5 * (size_t)shape::fixed_bytes(ns) &&
+           sec.ovf == sec.tmpl + tmpl_bytes && sec.fl0 == sec.ovf + 2 * ((size_t)5 * ns * 192) && sec.flist == sec.fl0 + 2 * ((size_t)5 * 64);
+}
+static_assert(kernel_sections_ok(1, 2048 * MSNAKE_TMPL_COPIES) && kernel_sections_ok(3, 4096 * MSNAKE_TMPL_COPIES) && kernel_sections_ok(4, 16384),
+              "the step kernel's section offsets follow shape::sections()");
+
 // MODE 0: step, 1: reset every env (msnake_reset), 2: render only (msnake_render), 3: n_steps steps of
 //      an action tape in ONE launch with the env kept in registers (msnake_rollout_tape)
 // K: integer pixel replication of the observation fused into the copy-out (the reference's WarpFrame,
@@ -328,11 +334,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     // 16-byte chunk of the copy-out are 16-byte aligned and every wave instruction stores whole 128-byte lines (step 7a).
     // The persistent tape kernel keeps the image at offset 0 and byte-aligned stores (its background lives in LDS).
     constexpr int TMPL_COPIES = K == 1 ? MSNAKE_TMPL_COPIES : 1;
-#ifdef MSNAKE_NO_ALIGN  // (A/B builds: every launch takes the byte-aligned copy-out of rounds 1-2)
-    constexpr bool CAN_ALIGN = false;
-#else
     constexpr bool CAN_ALIGN = K == 1;
-#endif
     // (the persistent tape kernel: only when every step's observations keep the alignment of the first step's, i.e. the
     //  step stride is a multiple of 16 bytes -- the launch glue checks -- so that its LDS-resident background fits all steps)
     const bool align_now = CAN_ALIGN && (MODE != 3 || (pk2 & PK2_TAPE_ALIGNED));
@@ -340,7 +342,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
         if constexpr (SPEC) {  // the shape is a constant (msnake_create derives S and cap the same way); only max_steps is data
             dim = DIM; nf = NS; action_stride = NS; auto_reset = true; short_rec = false;
             max_steps = pk0v >> 16;
-            S = (DIM + 2) * (DIM + 2) * C; cap = (DIM * DIM + 2 + 63) / 64 * 64;
+            S = shape::obs_bytes(DIM, C); cap = shape::ring_cap(DIM * DIM + 2);
             W = DIM + 2; n2 = DIM * DIM;
             return;
         }
@@ -355,9 +357,9 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     auto lds_layout = [&]() {
         // LDS image: W rows of W*K pixels (already replicated horizontally when K > 1), padded to
         // whole 1 KiB wave-instructions
-        img_bytes = (S * K + (K == 1 ? 15 : 0) + 1023) & ~1023;  // (native size: + room for the image's shift, see OBS_SHIFT)
-        occ_bytes = (n2 + 15) & ~15;
-        img = smem + (size_t)wave * (size_t)(img_bytes + occ_bytes + (LDSBG ? img_bytes : 0));  // observation being composed
+        img_bytes = shape::img_bytes(S, K);  // (native size: + room for the image's shift, see OBS_SHIFT)
+        occ_bytes = shape::occ_bytes(n2);
+        img = smem + (size_t)wave * (size_t)(img_bytes + occ_bytes + (LDSBG ? img_bytes : 0));  // observation being composed; the stride = shape::lds_per_wave(img_bytes, n2, LDSBG)
         bg = img + img_bytes + occ_bytes;                             // LDSBG: background, copied to img every step (the respawn occupancy sits in between)
     };
     unpack();
@@ -422,13 +424,15 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
                                                              (uint32_t)e * (uint32_t)(NS * 128)));
     // background image and, behind it, the overflow rings (bodies longer than 64 cells only): the
     // addresses are derived where they are needed -- the asm keeps the compiler from computing them
-    // at kernel entry and holding them in SGPRs for the whole launch
+    // at kernel entry and holding them in SGPRs for the whole launch.
+    // hdr_g, body0_g, tmpl_of, ring_of, fl0_of and flist_of spell the sections of shape::sections() in the kernel's own
+    // arithmetic (32-bit byte offsets up to tmpl, u16 elements behind it): kernel_sections_ok ahead of the kernel.
     auto tmpl_of = [&]() -> const uint8_t* {
         uint32_t n = (uint32_t)nenv;
         if (MODE == 3) asm volatile("" : "+s"(n));
-        return state + n * (uint32_t)(MSNAKE_HDR_WORDS * 4 + NS * 128);
+        return state + n * (uint32_t)shape::fixed_bytes(NS);
     };
-    auto ring_of = [&](int s) -> uint16_t* {
+    auto ring_of = [&](int s) -> uint16_t* {  // shape::sections().ovf + the snake's ring
         uint32_t ee = (uint32_t)e;
         asm volatile("" : "+s"(ee));
         return reinterpret_cast<uint16_t*>(const_cast<uint8_t*>(tmpl_of()) + img_bytes * TMPL_COPIES) + ((size_t)ee * NS + (size_t)s) * (size_t)cap;
@@ -460,14 +464,14 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     lds_layout();
     // adversarial rules keep a growing fruit LIST ([A]:183-185 appends dead bodies to it): entries
     // 0..63 in a VGPR like a body chunk (lane l = entry l), the complete list in HBM behind the rings
-    const int fcap = (NS + NS * (n2 + 2) + 63) & ~63;
+    const int fcap = shape::fruit_cap(NS, n2);
     // (addresses derived at the point of use, like the overflow rings: nothing kept in SGPRs)
-    auto fl0_of = [&]() -> uint16_t* {
+    auto fl0_of = [&]() -> uint16_t* {  // shape::sections().fl0 + the env's chunk
         uint32_t ee = (uint32_t)e;
         asm volatile("" : "+s"(ee));
         return reinterpret_cast<uint16_t*>(const_cast<uint8_t*>(tmpl_of()) + img_bytes * TMPL_COPIES) + (size_t)nenv * NS * cap + (size_t)ee * 64;
     };
-    auto flist_of = [&]() -> uint16_t* {
+    auto flist_of = [&]() -> uint16_t* {  // shape::sections().flist + the env's list
         uint32_t ee = (uint32_t)e;
         asm volatile("" : "+s"(ee));
         return reinterpret_cast<uint16_t*>(const_cast<uint8_t*>(tmpl_of()) + img_bytes * TMPL_COPIES) + (size_t)nenv * NS * cap + (size_t)nenv * 64 +
@@ -621,7 +625,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
         wave_sync();
         auto mark = [&](int, uint32_t cell) {
             // used = c1*dim + c0; out-of-grid heads alias onto other cells or fall outside
-            const int used = ((int)(cell & 255u) - 1) * dim + ((int)(cell >> 8) - 1);
+            const int used = cell_c1(cell) * dim + cell_c0(cell);
             if ((uint32_t)used < (uint32_t)n2) atomicOr(&occw[used >> 5], 1u << (used & 31));
         };
         if (RULES == MSNAKE_RULES_SNAKE_ENV && bf_short) {
@@ -696,7 +700,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
             q = ((uint32_t)x * (p2 >> PK2_DIVM_SHIFT)) >> sh;
         }
         const uint32_t r = (uint32_t)x - q * (uint32_t)dim;
-        return ((r + 1u) << 8) | (q + 1u);
+        return cell_pack((int)r, (int)q);
     };
     auto safe_cell = [&]() -> uint32_t {
         if (RULES == MSNAKE_RULES_ADVERSARIAL && nfree > 0) ensure_draws(1);  // its respawn count is not known up front
@@ -746,7 +750,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const uint32_t c0 = randint((uint32_t)dim), c1 = randint((uint32_t)dim);
-                const uint32_t hd = ((c0 + 1) << 8) | (c1 + 1);
+                const uint32_t hd = cell_pack((int)c0, (int)c1);
                 HV_SET_U(SN_A(s), 1u << 16);   // overflow empty, len 1
                 HV_SET_U(SN_B(s), 3u);         // grow_to 3
                 HV_SET_U(SN_C(s), hd);         // head cell, velocity (0,0), head in ring slot 0
@@ -758,7 +762,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
             build_free();
             for (int f = 0; f < nf; ++f) {
                 const uint32_t c = safe_cell();
-                HV_SET_DYN(FR0 + f, c);
+                HV_SET(FR0 + f, c);
             }
         }
         if (RULES == MSNAKE_RULES_ADVERSARIAL) HV_SET_C(HDR_NLIST, (uint32_t)NS);  // spare_fruits survives ([A]:14)
@@ -854,7 +858,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
         // builtin re-writes M0 per load, and an if / else-if over nk becomes a flag-driven state machine.)
         const uint32_t lds0 = (uint32_t)(uintptr_t)MSNAKE_LP(0);
         // (a compile-time shape knows its number of KiB: no tests in between)
-        constexpr int NK_SPEC = SPEC ? ((DIM + 2) * (DIM + 2) * C + 15 + 1023) >> 10 : 0;
+        constexpr int NK_SPEC = SPEC ? shape::img_bytes(shape::obs_bytes(DIM, C), 1) >> 10 : 0;
         if constexpr (NK_SPEC == 4)
             asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\t"
                          "global_load_lds_dwordx4 %0, off\n\t"
@@ -1082,7 +1086,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
                     build_free();
                     const int f = __builtin_ctz(m1 | (1u << NS));
                     const uint32_t c = pick_cell(randint_parked);
-                    HV_SET_DYN(FR0 + f, c);
+                    HV_SET(FR0 + f, c);
                     const uint32_t bit = (uint32_t)v_nh == c ? (1u << f) : 0u;
                     v_em = (v_moves && lane > s1) ? ((v_em & ~(1u << f)) | bit) : v_em;
                     s_begin = s1 + 1;
@@ -1106,7 +1110,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
                     const int f = __builtin_ffs((int)m) - 1;
                     m &= m - 1;
                     const uint32_t c = safe_cell();
-                    HV_SET_DYN(FR0 + f, c);
+                    HV_SET(FR0 + f, c);
                     const uint32_t bit = (uint32_t)v_nh == c ? (1u << f) : 0u;
                     v_em = (v_moves && lane > s) ? ((v_em & ~(1u << f)) | bit) : v_em;
                 }
@@ -1240,7 +1244,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
                         const int f = __builtin_ffsll((long long)m) - 1;
                         m &= m - 1;
                         const uint32_t c = safe_cell();
-                        HV_SET_DYN(FR0 + f, c);
+                        HV_SET(FR0 + f, c);
                     }
                 }
             }
@@ -1390,7 +1394,7 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
             }
             const uint32_t myhead = row_shl<8>(0u, hv) & 0xFFFFu;
             // (lane masks on purpose: `&&` / `||` here compile to nested exec-mask regions with branches)
-            const uint32_t hr = (myhead >> 8) - 1u, hc = (myhead & 255u) - 1u;  // head row / column in the grid, or >= dim
+            const uint32_t hr = (uint32_t)cell_c0(myhead), hc = (uint32_t)cell_c1(myhead);  // head row / column in the grid, or >= dim
             const uint32_t deadmask = (uint32_t)NSMASK &
                                       ((uint32_t)lanes_where<CMP_ULT>(hv, 1u << 16) | (uint32_t)lanes_where<CMP_UGE>(hr, (uint32_t)dim) |
                                        (uint32_t)lanes_where<CMP_UGE>(hc, (uint32_t)dim) | hitmask);
@@ -1506,9 +1510,6 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
     LANE_FENCE();
     CONFIG_FENCE();
     if (FOLD || obs_t) {
-#ifdef MSNAKE_PRIO_PAINT
-        __builtin_amdgcn_s_setprio(MSNAKE_PRIO_PAINT);
-#endif
         wave_sync();
         uint8_t* px = img + (CAN_ALIGN ? obs_shift_of() : 0u);
         // fruits first ([S]:43-44): red in every view; the background is already black
@@ -1810,9 +1811,6 @@ __global__ __launch_bounds__(MSNAKE_BLOCK_THREADS) void msnake_step_kernel(
         }
         if (RULES == MSNAKE_RULES_ADVERSARIAL && fr_dirty) fl0_of()[lane] = (uint16_t)fr;
     }
-#ifdef MSNAKE_END_WAIT  // experiment: every wave stays until its stores have been acknowledged
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
 #ifdef MSNAKE_HAVE_SPAN
     if (p.dbg_span) {
         SPAN(4);
@@ -1856,207 +1854,9 @@ hipError_t launch_stats(uint32_t* hdr, int nenv, unsigned long long* stats, int 
 }  // namespace msnake
 
 #include "msnake_envread.inc"  // StateView and EnvReader: how the kernels off the step path read an env's state
+#include "msnake_state.inc"    // msnake_get_state / msnake_set_state: the canonical state words <-> the device layout (off the step path)
 
 namespace msnake {
-
-// ------------------------------------------------------------------------------------------------
-// canonical state export / import (msnake_get_state[_all] / msnake_set_state[_all]; checkpoint and
-// test path, off the step path).  Word layout per env: include/msnake.h.  One wave per env.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void msnake_state_sizes_kernel(StateView v, int env0, int count, uint32_t* __restrict__ need) {
-    const int w = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (w >= count) return;
-    const uint32_t* h = v.hdr + (size_t)(env0 + w) * MSNAKE_HDR_WORDS;
-    uint32_t n = 8u + 2u * (uint32_t)fruit_count(v, h[HDR_NLIST]);
-    for (int s = 0; s < v.ns; ++s) n += 6u + 2u * (h[SN_A(s)] >> 16);
-    need[w] = n;
-}
-
-__global__ __launch_bounds__(256) void msnake_state_pack_kernel(StateView v, int env0, int count,
-                                                                const uint64_t* __restrict__ offsets, int32_t* __restrict__ words) {
-    const int lane = (int)(threadIdx.x & 63u);
-    const int w = (int)uni(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-    if (w >= count) return;
-    const EnvReader rd(v, env0 + w, lane);
-    int32_t* out = words + offsets[w];
-    const bool nw = v.rules == MSNAKE_RULES_NEW_WORLD;
-    const int nfr = rd.n_fruits();
-    const uint32_t flags = rd.flags();
-    if (lane == 0) {
-        out[0] = (int32_t)rd.word(HDR_T); out[1] = (int32_t)rd.word(HDR_CTR_LO); out[2] = (int32_t)rd.word(HDR_CTR_HI);
-        out[3] = (int32_t)rd.word(HDR_SPARE); out[4] = (int32_t)rd.word(HDR_EP_LEN); out[5] = (int32_t)rd.word(HDR_EP_RETURN);
-        out[6] = nfr; out[7] = v.ns | ((flags & HDR_FLAG_FINISHED) ? 0x100 : 0);
-    }
-    size_t k = 8;
-    rd.for_each_fruit([&](int f, uint32_t c, bool valid) {
-        if (valid) {
-            out[k + 2 * f] = (int32_t)(c >> 8) - 1;
-            out[k + 2 * f + 1] = (int32_t)(c & 255u) - 1;
-        }
-    });
-    k += 2 * (size_t)nfr;
-#pragma unroll
-    for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
-        if (s >= v.ns) continue;
-        const SnakeRef sn = rd.snake(s);
-        const int len = sn.len, vel = (int)((rd.word(SN_C(s)) >> 16) & 7u);
-        if (lane == 0) {
-            out[k] = len;
-            out[k + 1] = vel == 1 ? 1 : vel == 3 ? -1 : 0;
-            out[k + 2] = vel == 2 ? 1 : vel == 4 ? -1 : 0;
-            out[k + 3] = (int32_t)rd.word(SN_B(s));
-            out[k + 4] = nw ? (int32_t)((flags >> s) & 1u) : 1;
-            out[k + 5] = nw ? (int32_t)((flags >> (4 + s)) & 1u) : 0;
-        }
-        rd.for_each_piece(sn, [&](int i, uint32_t c, bool valid) {
-            if (valid) {
-                out[k + 6 + 2 * (size_t)i] = (int32_t)(c >> 8) - 1;
-                out[k + 6 + 2 * (size_t)i + 1] = (int32_t)(c & 255u) - 1;
-            }
-        });
-        k += 6 + 2 * (size_t)len;
-    }
-}
-
-// status[0]: number of rejected envs, status[1]: min over them of (local index + 1) << 8 | MSNAKE_ST_* reason (ONE
-// atomicMin on ~0u: index and reason of the first rejected env cannot come from two different waves), status[2]: != 0 if
-// an accepted env has a head outside the grid
-#define MSNAKE_ST_SHORT 1      // buffer too short / truncated
-#define MSNAKE_ST_SNAKES 2     // snake count differs from the handle
-#define MSNAKE_ST_FRUITS 3     // fruit count differs from the handle / exceeds the list capacity
-#define MSNAKE_ST_CELL 4       // a cell outside [-1, dim]
-#define MSNAKE_ST_LEN 5        // a body length outside [0, cap - 2]
-#define MSNAKE_ST_SCALAR 6     // a scalar field out of range: t, spare_fruits, ep_len, grow_to, a velocity, alive / in_dead
-__global__ __launch_bounds__(256) void msnake_state_unpack_kernel(StateView v, int env0, int count,
-                                                                  const uint64_t* __restrict__ offsets,
-                                                                  const int32_t* __restrict__ words, uint32_t* __restrict__ status) {
-    const int lane = (int)(threadIdx.x & 63u);
-    const int w = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-    if (w >= count) return;
-    const int e = env0 + w;
-    const int32_t* in = words + offsets[w];
-    const long long n = (long long)(offsets[w + 1] - offsets[w]);
-    const bool adv = v.rules == MSNAKE_RULES_ADVERSARIAL, nw = v.rules == MSNAKE_RULES_NEW_WORLD;
-    auto cell_ok = [&](int c0, int c1) { return c0 >= -1 && c0 <= v.dim && c1 >= -1 && c1 <= v.dim; };
-    // ---- pass 1: validate everything before anything is written
-    int bad = 0;
-    int nfr = 0;
-    bool off_head = false;  // (lane 0) some head lies outside the grid: reported in status[2] if the env is accepted
-    if (n < 8) bad = MSNAKE_ST_SHORT;
-    else if ((in[7] & ~0x100) != v.ns) bad = MSNAKE_ST_SNAKES;  // (bit 8: the episode-finished flag)
-    // counters that play only ever raises from 0; a negative spare_fruits also stops the reference's respawns for good
-    // ([A]:137-141 tests > 0 and == 0).  t has no upper bound: a handle with a lower episode cap may receive any t
-    else if (in[0] < 0 || in[3] < 0 || in[4] < 0) bad = MSNAKE_ST_SCALAR;
-    else {
-        nfr = in[6];
-        if (adv ? (nfr < 0 || nfr > v.fcap) : nfr != v.nf) bad = MSNAKE_ST_FRUITS;
-        else if (n < 8 + 2LL * nfr) bad = MSNAKE_ST_SHORT;
-    }
-    long long k = 8;
-    if (!bad) {
-        bool okc = true;
-        for (int f = lane; f < nfr; f += 64) {
-            const int c0 = in[k + 2 * f], c1 = in[k + 2 * f + 1];
-            // the adversarial fruit list may hold the off-grid head of a dead snake ([A]:183-185); the inline
-            // fruits of the other rule sets are only ever placed inside the grid
-            okc = okc && (adv ? cell_ok(c0, c1) : (c0 >= 0 && c0 < v.dim && c1 >= 0 && c1 < v.dim));
-        }
-        if (__builtin_amdgcn_ballot_w64(!okc) != 0) bad = MSNAKE_ST_CELL;
-        k += 2LL * nfr;
-    }
-    for (int s = 0; s < v.ns && !bad; ++s) {
-        if (n < k + 6) { bad = MSNAKE_ST_SHORT; break; }
-        const int len = in[k];
-        if (len < 0 || len > v.cap - 2) { bad = MSNAKE_ST_LEN; break; }
-        if (n < k + 6 + 2LL * len) { bad = MSNAKE_ST_SHORT; break; }
-        // what the record cannot hold, or holds as something else: a velocity that is not one of the five, a bit that is
-        // not 0 / 1, a negative grow_to (the vector update compares it unsigned); without the new_world bits a snake
-        // is alive and not in dead_snakes, which is what the export says there
-        const int v0 = in[k + 1], v1 = in[k + 2], al = in[k + 4], ind = in[k + 5];
-        const bool vel_ok = (v0 == 0 && (v1 >= -1 && v1 <= 1)) || (v1 == 0 && (v0 == -1 || v0 == 1));
-        const bool bits_ok = nw ? ((al == 0 || al == 1) && (ind == 0 || ind == 1)) : (al == 1 && ind == 0);
-        if (!vel_ok || in[k + 3] < 0 || !bits_ok) { bad = MSNAKE_ST_SCALAR; break; }
-        bool okc = true;
-        for (int i = lane; i < len; i += 64) {
-            const int c0 = in[k + 6 + 2LL * i], c1 = in[k + 6 + 2LL * i + 1];
-            okc = okc && cell_ok(c0, c1);
-            if (i == 0) off_head = off_head || !(c0 >= 0 && c0 < v.dim && c1 >= 0 && c1 < v.dim);
-            // only a head may be one step outside the grid (where a reference snake can be, for one step)
-            if (i > 0) okc = okc && c0 >= 0 && c0 < v.dim && c1 >= 0 && c1 < v.dim;
-        }
-        if (__builtin_amdgcn_ballot_w64(!okc) != 0) { bad = MSNAKE_ST_CELL; break; }
-        k += 6 + 2LL * len;
-    }
-    if (bad) {
-        if (lane == 0) {
-            atomicAdd(&status[0], 1u);
-            atomicMin(&status[1], (((uint32_t)w + 1u) << 8) | (uint32_t)bad);
-        }
-        return;
-    }
-    if (off_head) atomicOr(&status[2], 1u);
-    // ---- pass 2: the record (lane l builds word l; logging totals are not part of the canonical
-    //      state and stay; every other word, the parked Philox draws included, is cleared)
-    uint32_t* h = v.hdr + (size_t)e * MSNAKE_HDR_WORDS;
-    uint32_t hv = (lane >= HDR_ACC_EPISODES && lane <= HDR_ACC_LEN_HI) ? h[lane] : 0u;
-    HV_SET_C(HDR_T, in[0]); HV_SET_C(HDR_CTR_LO, in[1]); HV_SET_C(HDR_CTR_HI, in[2]); HV_SET_C(HDR_SPARE, in[3]);
-    HV_SET_C(HDR_EP_LEN, in[4]); HV_SET_C(HDR_EP_RETURN, in[5]);
-    if (adv) HV_SET_C(HDR_NLIST, nfr);
-    k = 8;
-    const int fr0 = nw ? HDR_FRUIT0_N : HDR_FRUIT0_S;
-    for (int f = lane; f < nfr; f += 64) {
-        const uint32_t c = ((uint32_t)(in[k + 2 * f] + 1) << 8) | (uint32_t)(in[k + 2 * f + 1] + 1);
-        if (adv) {
-            v.flist[(size_t)e * v.fcap + f] = (uint16_t)c;
-            if (f < 64) v.fl0[(size_t)e * 64 + f] = (uint16_t)c;
-        }
-    }
-    if (!adv)
-        for (int f = 0; f < nfr; ++f)
-            HV_SET_DYN(fr0 + f, ((uint32_t)(in[k + 2 * f] + 1) << 8) | (uint32_t)(in[k + 2 * f + 1] + 1));
-    k += 2LL * nfr;
-    uint32_t flags = 0;
-    for (int s = 0; s < v.ns; ++s) {
-        const int len = in[k], v0 = in[k + 1], v1 = in[k + 2];
-        const int vel = (v0 == 1 && v1 == 0) ? 1 : (v0 == 0 && v1 == 1) ? 2 : (v0 == -1 && v1 == 0) ? 3 : (v0 == 0 && v1 == -1) ? 4 : 0;
-        if (in[k + 4]) flags |= 1u << s;
-        if (in[k + 5]) flags |= 16u << s;
-        uint32_t headc = 0;
-        if (len > 0) headc = ((uint32_t)(in[k + 6] + 1) << 8) | (uint32_t)(in[k + 7] + 1);
-        for (int i = lane; i < len; i += 64) {
-            const uint32_t c = ((uint32_t)(in[k + 6 + 2LL * i] + 1) << 8) | (uint32_t)(in[k + 6 + 2LL * i + 1] + 1);
-            if (i < 64) v.body0[((size_t)e * v.ns + s) * 64 + i] = (uint16_t)c;          // head in slot 0
-            else v.ovf[((size_t)e * v.ns + s) * v.cap + (i - 64)] = (uint16_t)c;         // overflow from position 0
-        }
-        HV_SET(SN_A(s), (uint32_t)len << 16);
-        HV_SET(SN_B(s), in[k + 3]);
-        HV_SET(SN_C(s), headc | ((uint32_t)vel << 16));
-        k += 6 + 2LL * len;
-    }
-    if (in[7] & 0x100) flags |= HDR_FLAG_FINISHED;  // restored as exported: the episode is not counted a second time
-    HV_SET_C(HDR_FLAGS, flags);
-    h[lane] = hv;
-}
-
-hipError_t launch_state_sizes(const StepParams& p, int rules, int env0, int count, uint32_t* need_words, hipStream_t stream) {
-    hipLaunchKernelGGL(msnake_state_sizes_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream,
-                       state_view(p, rules), env0, count, need_words);
-    return hipGetLastError();
-}
-
-hipError_t launch_state_pack(const StepParams& p, int rules, int env0, int count, const uint64_t* offsets, int32_t* words,
-                             hipStream_t stream) {
-    hipLaunchKernelGGL(msnake_state_pack_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, stream,
-                       state_view(p, rules), env0, count, offsets, words);
-    return hipGetLastError();
-}
-
-hipError_t launch_state_unpack(const StepParams& p, int rules, int env0, int count, const uint64_t* offsets,
-                               const int32_t* words, uint32_t* status, hipStream_t stream) {
-    hipLaunchKernelGGL(msnake_state_unpack_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, stream,
-                       state_view(p, rules), env0, count, offsets, words, status);
-    return hipGetLastError();
-}
 
 // ------------------------------------------------------------------------------------------------
 // launch glue (called from the C-ABI in msnake_capi.hip)
@@ -2076,10 +1876,10 @@ static constexpr bool has_spec(int rules, int ns, int k, int dim) {
 }
 int spec_dim_of(const StepParams& p, int rules) {
     if (!has_spec(rules, p.n_snakes, p.obs_scale, p.dim)) return 0;
-    const int W = p.dim + 2, n2 = p.dim * p.dim, S = W * W * 9;
+    const int n2 = p.dim * p.dim, S = shape::obs_bytes(p.dim, 9);  // (what unpack() and lds_layout() fold for DIM = p.dim)
     if (p.n_fruits != p.n_snakes || !p.auto_reset || p.short_rec || p.views != 3 || p.C != 9) return 0;
-    if (p.S != S || p.rest.cap != (n2 + 2 + 63) / 64 * 64 || p.img_bytes != ((S + 15 + 1023) & ~1023) ||
-        p.lds_per_wave != p.img_bytes + ((n2 + 15) & ~15))
+    if (p.S != S || p.rest.cap != shape::ring_cap(n2 + 2) || p.img_bytes != shape::img_bytes(S, 1) ||
+        p.lds_per_wave != shape::lds_per_wave(p.img_bytes, n2, false))
         return 0;
     return p.dim;
 }
@@ -2099,9 +1899,9 @@ int call_shape_of(const StepParams& p, int mode) {
                        (uint64_t)p.nenv * (uint64_t)p.S < (1ull << 31);
     return plain ? MSNAKE_CALL_PLAIN : MSNAKE_CALL_SHAPE;
 }
-// (the stage bits that thin out the observation stores, and the A/B build without the aligned copy-out, live in the
-//  variant-0 code only: those builds never launch the plain-call variant)
-#if defined(MSNAKE_DBG_STAGES) || defined(MSNAKE_NO_ALIGN)
+// (the stage bits that thin out the observation stores live in the variant-0 code only: that build never launches the
+//  plain-call variant)
+#ifdef MSNAKE_DBG_STAGES
 static constexpr bool PLAIN_BUILT = false;
 #else
 static constexpr bool PLAIN_BUILT = true;
@@ -2113,8 +1913,8 @@ static hipError_t launch_k(const StepParams& p, int mode, int epb, hipStream_t s
                          ((uint32_t)(p.auto_reset ? 1 : 0) << 15) | ((uint32_t)p.rest.max_steps << 16);
     const uint32_t pk1 = (uint32_t)p.S | ((uint32_t)p.rest.cap << 16);
 
-    size_t lds_wave = (size_t)p.lds_per_wave;
-    if (mode == 3 && K == 1) {  // + the pristine background copy; fewer envs per workgroup if that needs it
+    size_t lds_wave = (size_t)p.lds_per_wave;  // (derive_shape: shape::lds_per_wave without the background copy)
+    if (mode == 3 && K == 1) {  // + the pristine background copy = shape::lds_per_wave(.., true); fewer envs per workgroup if that needs it
         lds_wave += (size_t)p.img_bytes;
         while (epb > 1 && lds_wave * (size_t)epb > 64 * 1024) epb >>= 1;
         if (lds_wave > 64 * 1024) return hipErrorInvalidValue;

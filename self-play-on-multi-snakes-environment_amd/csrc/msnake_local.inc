@@ -52,7 +52,7 @@ __global__ __launch_bounds__(LOCAL_WAVES * 64) void msnake_local_kernel(LocalArg
 
     // a cell inside the grid takes the phase's code; anything else is not stored
     auto paint = [&](uint32_t c, bool valid, uint32_t code) {
-        const int c0 = (int)(c >> 8) - 1, c1 = (int)(c & 255u) - 1;
+        const int c0 = MSNAKE_CELL_C0(c), c1 = MSNAKE_CELL_C1(c);
         if (valid && c0 >= 0 && c0 < dim && c1 >= 0 && c1 < dim) board[c0 * dim + c1] = (uint8_t)code;
     };
 
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(LOCAL_WAVES * 64) void msnake_local_kernel(LocalArg
         int snake;
         const uint32_t p = slot_par(q, snake);
         const int k = a.oriented ? (int)((p >> 20) & 3u) : 0;
-        const int f0 = k == 0 ? 1 : k == 2 ? -1 : 0, f1 = k == 1 ? 1 : k == 3 ? -1 : 0;  // g = (-f1, f0)
+        const int f0 = move_d0(k), f1 = move_d1(k);  // g = (-f1, f0)
         const int c0 = (int)(p & 1023u) - 2 + di * f0 - dj * f1, c1 = (int)((p >> 10) & 1023u) - 2 + di * f1 + dj * f0;
         const bool inside = c0 >= 0 && c0 < dim && c1 >= 0 && c1 < dim;
         const uint32_t b = board[inside ? c0 * dim + c1 : 0];

@@ -76,13 +76,13 @@ __global__ __launch_bounds__(256) void msnake_scripted_kernel(ScriptedArgs a) {
             const int hp0 = (int)((rdlane(hv, SN_C(s)) >> SN_C_HP0_SHIFT) & 63u);
             if (len[s] > 0) {
                 const uint32_t head = rdlane(ring[s], hp0);  // piece 0 sits in ring slot hp0
-                hx[s] = (int)(head >> 8) - 1; hy[s] = (int)(head & 255u) - 1;
+                hx[s] = cell_c0(head); hy[s] = cell_c1(head);
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
-                    const int tx = hx[s] + (m == 0 ? 1 : m == 2 ? -1 : 0), ty = hy[s] + (m == 1 ? 1 : m == 3 ? -1 : 0);
+                    const int tx = hx[s] + move_d0(m), ty = hy[s] + move_d1(m);
                     if (tx >= 0 && tx < dim && ty >= 0 && ty < dim) {
                         onb[s] |= 1u << m;
-                        cand[s][m] = ((uint32_t)(tx + 1) << 8) | (uint32_t)(ty + 1);
+                        cand[s][m] = cell_pack(tx, ty);
                     }
                 }
             }
@@ -140,12 +140,12 @@ __global__ __launch_bounds__(256) void msnake_scripted_kernel(ScriptedArgs a) {
 #pragma unroll
         for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) key[s] = 0xFFFFFFFFu;
         auto fruit = [&](uint32_t c, bool valid) {
-            const int fx = (int)(c >> 8) - 1, fy = (int)(c & 255u) - 1;
+            const int fx = cell_c0(c), fy = cell_c1(c);
 #pragma unroll
             for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s)
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
-                    const int tx = hx[s] + (m == 0 ? 1 : m == 2 ? -1 : 0), ty = hy[s] + (m == 1 ? 1 : m == 3 ? -1 : 0);
+                    const int tx = hx[s] + move_d0(m), ty = hy[s] + move_d1(m);
                     const int dx = fx - tx, dy = fy - ty;
                     const uint32_t k = ((uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy)) << 3) | (uint32_t)(m + 1);
                     if (valid && ((open[s] >> m) & 1u) && k < key[s]) key[s] = k;

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArg
 
     // ---- occupancy: every body cell inside the grid sets its bit
     auto mark = [&](uint32_t c, bool valid) {
-        const int x = (int)(c >> 8) - 1, y = (int)(c & 255u) - 1;
+        const int x = MSNAKE_CELL_C0(c), y = MSNAKE_CELL_C1(c);
         if (valid && x >= 0 && x < dim && y >= 0 && y < dim)
             __hip_atomic_fetch_or(&my[2 * y + (x >> 5)], 1u << (x & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArg
     const int my_len = cs == 0 ? len[0] : cs == 1 ? len[1] : cs == 2 ? len[2] : cs == 3 ? len[3] : 0;
     const int my_hx = cs == 0 ? hx[0] : cs == 1 ? hx[1] : cs == 2 ? hx[2] : hx[3];
     const int my_hy = cs == 0 ? hy[0] : cs == 1 ? hy[1] : cs == 2 ? hy[2] : hy[3];
-    const int tx = my_hx + (cm == 0 ? 1 : cm == 2 ? -1 : 0), ty = my_hy + (cm == 1 ? 1 : cm == 3 ? -1 : 0);
+    const int tx = my_hx + move_d0(cm), ty = my_hy + move_d1(cm);
     const bool onb = lane < 4 * ns && my_len > 0 && tx >= 0 && tx < dim && ty >= 0 && ty < dim;
     const int gx = onb ? tx : 0, gy = onb ? ty : 0;  // what the gathers index with: always inside the wave
     const uint64_t target_row = gather_row(vacant, gy);  // (every lane takes part: the source lanes must be active)
@@ -155,12 +155,12 @@ __global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArg
 #pragma unroll
         for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) key[s] = 0xFFFFFFFFu;
         rd.for_each_fruit([&](int, uint32_t c, bool valid) {
-            const int fx = (int)(c >> 8) - 1, fy = (int)(c & 255u) - 1;
+            const int fx = cell_c0(c), fy = cell_c1(c);
 #pragma unroll
             for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s)
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
-                    const int qx = hx[s] + (m == 0 ? 1 : m == 2 ? -1 : 0), qy = hy[s] + (m == 1 ? 1 : m == 3 ? -1 : 0);
+                    const int qx = hx[s] + move_d0(m), qy = hy[s] + move_d1(m);
                     const int dx = fx - qx, dy = fy - qy;
                     const uint32_t kk = ((uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy)) << 3) | (uint32_t)(m + 1);
                     const uint32_t out = 0u - ((~elig[s] >> m) & 1u);  // all ones where the move is not eligible
