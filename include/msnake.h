@@ -32,6 +32,9 @@
  *   msnake_scripted_actions: no reference counterpart (its opponents are always networks: evaluate_snake.py,
  *                      ppo_multi_agent.py:28-50 MultiModel.multi_step); a fixed, deterministic opponent and the
  *                      safe-move mask, computed on the device from the state the handle already owns.
+ *   msnake_space_actions / msnake_territory_actions: no reference counterpart either; opponents that look ahead -- how
+ *                      much room a move leads into, and how much of it the snake reaches before any other snake can
+ *                      (Voronoi territory) -- with the counts as per-move features.
  *   msnake_copy_envs <- no reference counterpart (a reference env can only be re-created and replayed); the analogue is
  *                      ALE's cloneState / restoreState, batched and on the device: snapshot, fork and restore of envs
  *                      between two handles without the host round trip of msnake_get_state / msnake_set_state.
@@ -292,6 +295,33 @@ int msnake_scripted_actions(msnake_handle h, int32_t policy, uint32_t snake_mask
  * action_stride < n_snakes when snake_mask != 0; nothing to write (snake_mask 0, safe_dev and space_dev NULL). */
 int msnake_space_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride,
                          uint8_t* safe_dev, uint16_t* space_dev, void* stream);
+
+/* Voronoi territory counts and the opponent territory_greedy, in the terms of the two calls above (`used`, moves 1..4,
+ * free, open).  Bodies are static: tails do not recede, and neither the velocity nor the alive bit plays a part (a
+ * new_world snake that kept its body after a self-hit still moves, so it counts like any other).
+ * territory_dev (may be NULL): uint16 [num_envs][n_snakes][4], written for every snake whatever snake_mask is.  For
+ * snake s with a non-empty body and open move m + 1 with target t: O_s = the targets of the open moves of every OTHER
+ * snake with a non-empty body (where they can stand after the same lockstep step); dA(c) = the BFS distance from t to
+ * c through free cells, 4-connected; dB(c) = the BFS distance from the set O_s, infinite when O_s is empty or c cannot
+ * be reached from it.  Entry m = |{ c free : dA(c) < dB(c) }|, the cells s reaches strictly first; ties go to the
+ * others.  So the entry is 0 when the move is not open or the body is empty, and ALSO for an open move whose target
+ * lies in O_s -- a head-on cell, where both snakes die in this env; safe_dev tells the two zero cases apart.  When no
+ * other snake can move, the entry equals space_dev of the call above exactly.  At most 62^2 - 1.  2-byte aligned
+ * (MSNAKE_E_ALIGN otherwise).
+ * safe_dev (may be NULL): exactly what the two calls above write there.
+ * actions_dev: int32 [num_envs][action_stride]; entry s of every row is written for each s with bit s of
+ * snake_mask set, all other entries are left untouched.  The policy territory_greedy is space_greedy with territory
+ * in place of space: the action is 0 if the body is empty or no move is open; otherwise need = min(len, max over the
+ * open moves of territory), with len the canonical state's body length (duplicates counted); the eligible moves are
+ * the open moves with territory >= need -- when every open move has territory 0, all open moves; and the action is
+ * the first eligible move, in the order 1, 2, 3, 4, whose target has the strictly smallest L1 distance to any fruit
+ * of the state's fruit list (adversarial: the complete list; distance 0 when the list is empty).
+ * Like its siblings the call only reads the handle's state, draws no random numbers, allocates nothing, does not
+ * synchronise and adds nothing to env_steps; asynchronous on `stream`, and it can be captured into a HIP graph in
+ * front of the step.  MSNAKE_E_ARG, before any device work: a snake_mask bit >= n_snakes; actions_dev NULL or
+ * action_stride < n_snakes when snake_mask != 0; nothing to write (snake_mask 0, safe_dev and territory_dev NULL). */
+int msnake_territory_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride,
+                             uint8_t* safe_dev, uint16_t* territory_dev, void* stream);
 
 /* Copy env state from `src` into `dst` on the device: destination env e receives the state of source env
  * src_index_dev[e] (int32 [dst.num_envs], a device pointer).  A negative entry leaves destination env e completely

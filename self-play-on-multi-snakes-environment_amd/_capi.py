@@ -21,7 +21,7 @@ SYMBOLS = [
     "msnake_render", "msnake_get_stats", "msnake_kernel_name", "msnake_algorithmic_bytes_per_env_step",
     "msnake_scripted_actions", "msnake_copy_envs", "msnake_kernel_name_for_config",
     "msnake_set_generic_kernels", "msnake_space_actions", "msnake_render_cells", "msnake_render_local",
-    "msnake_call_shape_for_config",
+    "msnake_call_shape_for_config", "msnake_territory_actions",
 ]
 
 
@@ -41,6 +41,7 @@ RECORD_POLICY = {"auto": 0, "full": 1, "short": 2}
 STORE_POLICY = {"auto": 0, "plain": 1, "stream": 2}
 SCRIPTED_POLICY = {None: 0, "safe_greedy": 1, "hamiltonian": 2}  # MSNAKE_POLICY_*
 SPACE_POLICY = "space_greedy"  # no policy id: an entry point of its own (msnake_space_actions)
+TERRITORY_POLICY = "territory_greedy"  # likewise (msnake_territory_actions)
 
 
 class MsnakeBlobInfo(ctypes.Structure):
@@ -88,6 +89,8 @@ def load():
     L.msnake_scripted_actions.argtypes = [vp, i32, ctypes.c_uint32, vp, i32, u8p, vp]
     # h, snake_mask, actions_dev, action_stride, safe_dev, space_dev (uint16 [num_envs][n_snakes][4]), stream
     L.msnake_space_actions.argtypes = [vp, ctypes.c_uint32, vp, i32, u8p, vp, vp]
+    # h, snake_mask, actions_dev, action_stride, safe_dev, territory_dev (uint16 [num_envs][n_snakes][4]), stream
+    L.msnake_territory_actions.argtypes = [vp, ctypes.c_uint32, vp, i32, u8p, vp, vp]
     # h, view_mask, cells_dev (uint8 [num_envs][V][dim][dim]), snakes_dev (int32 [num_envs][n_snakes][8] or NULL), stream
     L.msnake_render_cells.argtypes = [vp, ctypes.c_uint32, u8p, vp, vp]
     # h, radius, snake_mask, oriented, windows_dev (uint8 [num_envs][S][W][W]), heading_dev (uint8 [num_envs][S] or NULL), stream
@@ -116,7 +119,7 @@ def load():
     for name in ("msnake_create", "msnake_destroy", "msnake_obs_shape", "msnake_reset", "msnake_reset_envs", "msnake_render",
                  "msnake_step", "msnake_step_tape", "msnake_rollout_tape", "msnake_get_state", "msnake_set_state", "msnake_set_state_all",
                  "msnake_state_blob_info", "msnake_get_stats", "msnake_scripted_actions", "msnake_copy_envs",
-                 "msnake_space_actions", "msnake_render_cells", "msnake_render_local"):
+                 "msnake_space_actions", "msnake_render_cells", "msnake_render_local", "msnake_territory_actions"):
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L

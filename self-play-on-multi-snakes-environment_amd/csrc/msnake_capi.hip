@@ -480,6 +480,26 @@ int msnake_space_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_
     return MSNAKE_OK;
 }
 
+int msnake_territory_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride, uint8_t* safe_dev,
+                             uint16_t* territory_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    const int ns = h->p.n_snakes;
+    if (snake_mask >> ns)
+        return fail(MSNAKE_E_ARG, "msnake_territory_actions: snake_mask 0x%x has a bit >= n_snakes=%d", snake_mask, ns);
+    if (snake_mask && !actions_dev) return fail(MSNAKE_E_ARG, "msnake_territory_actions: actions_dev is NULL");
+    if (snake_mask && action_stride < ns)
+        return fail(MSNAKE_E_ARG, "msnake_territory_actions: action_stride %d must be >= n_snakes=%d", action_stride, ns);
+    if (!snake_mask && !safe_dev && !territory_dev)
+        return fail(MSNAKE_E_ARG, "msnake_territory_actions: nothing to write (snake_mask 0, safe_dev and territory_dev are NULL)");
+    if (snake_mask && ((uintptr_t)actions_dev & 3)) return fail(MSNAKE_E_ALIGN, "actions_dev must be 4-byte aligned");
+    if ((uintptr_t)territory_dev & 1) return fail(MSNAKE_E_ALIGN, "territory_dev must be 2-byte aligned");
+    DeviceGuard guard(h->cfg.device);
+    hipError_t e = msnake::launch_territory(h->p, h->cfg.rules, snake_mask, actions_dev, action_stride, safe_dev, territory_dev,
+                                            static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return MSNAKE_OK;
+}
+
 int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_index_dev, void* stream) {
     if (int rc = check(dst)) return rc;
     if (int rc = check(src)) return rc;

@@ -24,6 +24,8 @@
 //     open && space >= need, then safe_greedy's choice among the eligible moves (min over (fruit, move) pairs of
 //     distance << 3 | move, fruits lane-distributed).
 //   * lane s stores snake s's action word and mask byte, lane 4 s + m the count of move m + 1.
+// The occupancy build with the candidates (read_board) and the choice by count (greedy_by_count) are functions of their
+// own: msnake_territory.inc, included behind this file, races on the same board and chooses in the same way.
 // No random numbers, no global atomics, no workgroup barrier, no scratch.
 namespace msnake {
 
@@ -68,17 +70,20 @@ __device__ __forceinline__ uint64_t gather_row(uint64_t v, int src) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-// ACT: the space_greedy actions are written (snake_mask != 0); SAFE / SPACE: safe_dev / space_dev are written
-template <bool ACT, bool SAFE, bool SPACE>
-__global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArgs a) {
-    __shared__ uint32_t occ[SPACE_WAVES][128];  // per wave: row y = words 2 y (bits 0..31) and 2 y + 1 (bits 32..63)
-    const int lane = (int)(threadIdx.x & 63u);
-    const int wave = (int)uni(threadIdx.x >> 6);
-    const int e = (int)uni(blockIdx.x * SPACE_WAVES + (threadIdx.x >> 6));
-    if (e >= a.v.nenv) return;  // (no workgroup barrier below)
-    const int ns = a.v.ns, dim = a.v.dim;
-    const EnvReader rd(a.v, e, lane);
-    uint32_t* my = occ[wave];
+// What both count kernels (this file's and msnake_territory.inc's) know of the board before they fill anything: the
+// free cells as row-per-lane masks and the 16 candidates.
+struct Board {
+    uint64_t vacant;   // lane y: bit x <-> cell (x, y) is free; 0 for lanes >= dim
+    int len[MSNAKE_MAX_SNAKES], hx[MSNAKE_MAX_SNAKES], hy[MSNAKE_MAX_SNAKES];
+    int my_len;        // lane 4 s + m: snake s's body length (0 for lanes >= 16)
+    int gx, gy;        // lane 4 s + m: the target of move m + 1 where it lies in the grid, else (0, 0): safe to gather with
+    uint32_t open_all; // bit 4 s + m: move m + 1 of snake s is open
+};
+
+// `my`: the wave's private 128 words of LDS (row y = words 2 y and 2 y + 1).  Every lane of the wave must call this.
+__device__ __forceinline__ Board read_board(const StateView& v, const EnvReader& rd, uint32_t* my, int lane) {
+    Board b;
+    const int ns = v.ns, dim = v.dim;
     my[lane] = 0u;
     my[64 + lane] = 0u;
     wave_sync();
@@ -89,28 +94,91 @@ __global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArg
         if (valid && x >= 0 && x < dim && y >= 0 && y < dim)
             __hip_atomic_fetch_or(&my[2 * y + (x >> 5)], 1u << (x & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
-    int len[MSNAKE_MAX_SNAKES], hx[MSNAKE_MAX_SNAKES], hy[MSNAKE_MAX_SNAKES];
 #pragma unroll
     for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
         const SnakeRef sn = rd.snake(s);
-        len[s] = sn.len; hx[s] = sn.x; hy[s] = sn.y;
+        b.len[s] = sn.len; b.hx[s] = sn.x; b.hy[s] = sn.y;
         rd.for_each_piece(sn, [&](int, uint32_t c, bool valid) { mark(c, valid); });
     }
     wave_sync();
     const uint64_t used = (uint64_t)my[2 * lane] | ((uint64_t)my[2 * lane + 1] << 32);
-    const uint64_t vacant = lane < dim ? ~used & ((1ull << dim) - 1ull) : 0ull;
+    b.vacant = lane < dim ? ~used & ((1ull << dim) - 1ull) : 0ull;
 
     // ---- the candidates: lane 4 s + m <-> move m + 1 of snake s
     const int cs = lane >> 2, cm = lane & 3;
-    const int my_len = cs == 0 ? len[0] : cs == 1 ? len[1] : cs == 2 ? len[2] : cs == 3 ? len[3] : 0;
-    const int my_hx = cs == 0 ? hx[0] : cs == 1 ? hx[1] : cs == 2 ? hx[2] : hx[3];
-    const int my_hy = cs == 0 ? hy[0] : cs == 1 ? hy[1] : cs == 2 ? hy[2] : hy[3];
+    b.my_len = cs == 0 ? b.len[0] : cs == 1 ? b.len[1] : cs == 2 ? b.len[2] : cs == 3 ? b.len[3] : 0;
+    const int my_hx = cs == 0 ? b.hx[0] : cs == 1 ? b.hx[1] : cs == 2 ? b.hx[2] : b.hx[3];
+    const int my_hy = cs == 0 ? b.hy[0] : cs == 1 ? b.hy[1] : cs == 2 ? b.hy[2] : b.hy[3];
     const int tx = my_hx + move_d0(cm), ty = my_hy + move_d1(cm);
-    const bool onb = lane < 4 * ns && my_len > 0 && tx >= 0 && tx < dim && ty >= 0 && ty < dim;
-    const int gx = onb ? tx : 0, gy = onb ? ty : 0;  // what the gathers index with: always inside the wave
-    const uint64_t target_row = gather_row(vacant, gy);  // (every lane takes part: the source lanes must be active)
-    const bool is_open = onb && ((target_row >> gx) & 1ull);
-    const uint32_t open_all = (uint32_t)__ballot(is_open);  // bit 4 s + m: move m + 1 of snake s is open
+    const bool onb = lane < 4 * ns && b.my_len > 0 && tx >= 0 && tx < dim && ty >= 0 && ty < dim;
+    b.gx = onb ? tx : 0, b.gy = onb ? ty : 0;  // what the gathers index with: always inside the wave
+    const uint64_t target_row = gather_row(b.vacant, b.gy);  // (every lane takes part: the source lanes must be active)
+    const bool is_open = onb && ((target_row >> b.gx) & 1ull);
+    b.open_all = (uint32_t)__ballot(is_open);
+    return b;
+}
+
+// The choice space_greedy and territory_greedy share.  `count`: lane 4 s + m holds the count of move m + 1 of snake s
+// (0 where the move is not open).  need = min(len, max over the open moves of count) by two quad-permute DPP steps,
+// eligible = open && count >= need, then safe_greedy's choice among the eligible moves.  act[s] is set for every snake
+// with an eligible move and left alone otherwise.  Every lane of the wave must call this.
+__device__ __forceinline__ void greedy_by_count(const EnvReader& rd, int ns, int lane, uint32_t open_all, uint32_t count, int my_len,
+                                                const int (&hx)[MSNAKE_MAX_SNAKES], const int (&hy)[MSNAKE_MAX_SNAKES],
+                                                uint32_t (&act)[MSNAKE_MAX_SNAKES]) {
+    uint32_t mx = count;
+    uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mx, 0xB1, 0xF, 0xF, true);  // quad_perm:[1,0,3,2]
+    mx = mx > o ? mx : o;
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mx, 0x4E, 0xF, 0xF, true);           // quad_perm:[2,3,0,1]
+    mx = mx > o ? mx : o;
+    const uint32_t need = (uint32_t)my_len < mx ? (uint32_t)my_len : mx;
+    const uint32_t elig_all = (uint32_t)__ballot(lane < 16 && ((open_all >> lane) & 1u) && count >= need);
+    uint32_t elig[MSNAKE_MAX_SNAKES];
+#pragma unroll
+    for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) elig[s] = (elig_all >> (4 * s)) & 15u;
+
+    const int nfr = rd.n_fruits();
+    uint32_t key[MSNAKE_MAX_SNAKES];  // min over this lane's fruits and the eligible moves of distance << 3 | move
+#pragma unroll
+    for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) key[s] = 0xFFFFFFFFu;
+    rd.for_each_fruit([&](int, uint32_t c, bool valid) {
+        const int fx = cell_c0(c), fy = cell_c1(c);
+#pragma unroll
+        for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s)
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const int qx = hx[s] + move_d0(m), qy = hy[s] + move_d1(m);
+                const int dx = fx - qx, dy = fy - qy;
+                const uint32_t kk = ((uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy)) << 3) | (uint32_t)(m + 1);
+                const uint32_t out = 0u - ((~elig[s] >> m) & 1u);  // all ones where the move is not eligible
+                const uint32_t cand = valid ? kk | out : 0xFFFFFFFFu;
+                key[s] = cand < key[s] ? cand : key[s];
+            }
+    });
+#pragma unroll
+    for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
+        if (s >= ns || elig[s] == 0u) continue;
+        if (nfr <= 0) {  // every distance is 0: the first eligible move
+            act[s] = (uint32_t)__builtin_ctz(elig[s]) + 1u;
+        } else {
+            act[s] = wave_reduce(key[s], [](uint32_t x, uint32_t y) { return x < y ? x : y; }) & 7u;
+        }
+    }
+}
+
+// ACT: the space_greedy actions are written (snake_mask != 0); SAFE / SPACE: safe_dev / space_dev are written
+template <bool ACT, bool SAFE, bool SPACE>
+__global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArgs a) {
+    __shared__ uint32_t occ[SPACE_WAVES][128];  // per wave: row y = words 2 y (bits 0..31) and 2 y + 1 (bits 32..63)
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = (int)uni(threadIdx.x >> 6);
+    const int e = (int)uni(blockIdx.x * SPACE_WAVES + (threadIdx.x >> 6));
+    if (e >= a.v.nenv) return;  // (no workgroup barrier below)
+    const int ns = a.v.ns, dim = a.v.dim;
+    const EnvReader rd(a.v, e, lane);
+    const Board b = read_board(a.v, rd, occ[wave], lane);
+    const uint64_t vacant = b.vacant;
+    const int gx = b.gx, gy = b.gy;
+    const uint32_t open_all = b.open_all;
 
     // ---- fills: one per distinct region that holds an open target
     uint32_t space = 0u;
@@ -138,46 +206,7 @@ __global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArg
     uint32_t act[MSNAKE_MAX_SNAKES];
 #pragma unroll
     for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) act[s] = 0u;
-    if (ACT) {
-        uint32_t mx = space;  // (0 where the move is not open)
-        uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mx, 0xB1, 0xF, 0xF, true);  // quad_perm:[1,0,3,2]
-        mx = mx > o ? mx : o;
-        o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mx, 0x4E, 0xF, 0xF, true);           // quad_perm:[2,3,0,1]
-        mx = mx > o ? mx : o;
-        const uint32_t need = (uint32_t)my_len < mx ? (uint32_t)my_len : mx;
-        const uint32_t elig_all = (uint32_t)__ballot(lane < 16 && ((open_all >> lane) & 1u) && space >= need);
-        uint32_t elig[MSNAKE_MAX_SNAKES];
-#pragma unroll
-        for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) elig[s] = (elig_all >> (4 * s)) & 15u;
-
-        const int nfr = rd.n_fruits();
-        uint32_t key[MSNAKE_MAX_SNAKES];  // min over this lane's fruits and the eligible moves of distance << 3 | move
-#pragma unroll
-        for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) key[s] = 0xFFFFFFFFu;
-        rd.for_each_fruit([&](int, uint32_t c, bool valid) {
-            const int fx = cell_c0(c), fy = cell_c1(c);
-#pragma unroll
-            for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s)
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const int qx = hx[s] + move_d0(m), qy = hy[s] + move_d1(m);
-                    const int dx = fx - qx, dy = fy - qy;
-                    const uint32_t kk = ((uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy)) << 3) | (uint32_t)(m + 1);
-                    const uint32_t out = 0u - ((~elig[s] >> m) & 1u);  // all ones where the move is not eligible
-                    const uint32_t cand = valid ? kk | out : 0xFFFFFFFFu;
-                    key[s] = cand < key[s] ? cand : key[s];
-                }
-        });
-#pragma unroll
-        for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
-            if (s >= ns || elig[s] == 0u) continue;
-            if (nfr <= 0) {  // every distance is 0: the first eligible move
-                act[s] = (uint32_t)__builtin_ctz(elig[s]) + 1u;
-            } else {
-                act[s] = wave_reduce(key[s], [](uint32_t x, uint32_t y) { return x < y ? x : y; }) & 7u;
-            }
-        }
-    }
+    if (ACT) greedy_by_count(rd, ns, lane, open_all, space, b.my_len, b.hx, b.hy, act);
 
     // lane s owns snake s's action word and mask byte, lane 4 s + m the count of move m + 1
     if (lane < ns) {

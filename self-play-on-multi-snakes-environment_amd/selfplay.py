@@ -375,7 +375,7 @@ class MonitorCSV:
 
 
 # ----------------------------------------------------------------------------- scripted opponents
-SCRIPTED_POLICIES = ("safe_greedy", "hamiltonian", "space_greedy")
+SCRIPTED_POLICIES = ("safe_greedy", "hamiltonian", "space_greedy", "territory_greedy")
 
 
 class ScriptedColumns:
@@ -409,7 +409,7 @@ class ScriptedColumns:
 
 class ScriptedOpponent:
     """A fixed, deterministic opponent in the place of a CnnPolicy: snake `snake` plays the env's on-device scripted
-    `policy` ("safe_greedy", "hamiltonian" or "space_greedy", MultiSnakeVecEnv.scripted_actions_device).  step(obs) has the shape
+    `policy` (one of SCRIPTED_POLICIES, MultiSnakeVecEnv.scripted_actions_device).  step(obs) has the shape
     Runner.multi_step calls; the observation is ignored, the env's state is asked.  eps > 0: with probability eps
     the action is replaced by randint(0, 5), drawn with torch on the env's device from `generator` (the env's own
     random numbers are never used).  On its own (columns=None) every step() is one env call.  Several opponents of one

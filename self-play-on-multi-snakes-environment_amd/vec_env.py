@@ -394,8 +394,16 @@ class MultiSnakeVecEnv:
                              f"{self.device}")
         return out
 
-    def scripted_actions_device(self, policy, snakes=None, out=None, safe_out=None, space_out=None):
-        """Actions of a scripted policy ("safe_greedy", "hamiltonian", "space_greedy", or None for the mask alone) for the
+    def _territory_out(self, out):
+        torch = self._torch
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint16 or out.device != self.device or
+                tuple(out.shape) != (self.num_envs, self.n_snakes, 4) or not out.is_contiguous()):
+            raise ValueError(f"territory_out must be a contiguous uint16 tensor of shape ({self.num_envs}, {self.n_snakes}, 4) "
+                             f"on {self.device}")
+        return out
+
+    def scripted_actions_device(self, policy, snakes=None, out=None, safe_out=None, space_out=None, territory_out=None):
+        """Actions of a scripted policy ("safe_greedy", "hamiltonian", "space_greedy", "territory_greedy", or None for the mask alone) for the
         snakes in `snakes` (indices; default every snake), computed on the device from the env's current state.  They go to
         columns `snakes` of `out`, an int32 [num_envs, >= n_snakes] device tensor as step_device() takes it; its other
         columns are left as they are (out=None: a cached, zero-initialised [num_envs, n_snakes] tensor of the env).
@@ -404,12 +412,18 @@ class MultiSnakeVecEnv:
         nothing is synchronised.  Draws no random numbers and changes no env state.
         "space_greedy" (msnake_space_actions) flood-fills from every open move's target and refuses moves into a region
         smaller than the body; only with it, `space_out`, a uint16 [num_envs, n_snakes, 4] device tensor, gets the
-        reachable-space counts (see reachable_space_device) and is returned behind the others that were asked for."""
+        reachable-space counts (see reachable_space_device) and is returned behind the others that were asked for.
+        "territory_greedy" (msnake_territory_actions) is space_greedy with the Voronoi territory in place of the space:
+        the cells the snake reaches strictly before any other snake can; only with it, `territory_out`, a uint16
+        [num_envs, n_snakes, 4] device tensor, gets those counts (see territory_device), returned like space_out."""
         torch = self._torch
         space = policy == _capi.SPACE_POLICY
+        territory = policy == _capi.TERRITORY_POLICY
         if space_out is not None and not space:
             raise ValueError(f"space_out is written by policy 'space_greedy' only, got policy {policy!r}")
-        if not space and policy not in _capi.SCRIPTED_POLICY:
+        if territory_out is not None and not territory:
+            raise ValueError(f"territory_out is written by policy 'territory_greedy' only, got policy {policy!r}")
+        if not space and not territory and policy not in _capi.SCRIPTED_POLICY:
             raise ValueError(f"policy must be 'safe_greedy', 'hamiltonian' or None, got {policy!r}")
         if snakes is None:
             bits = (1 << self.n_snakes) - 1
@@ -435,6 +449,14 @@ class MultiSnakeVecEnv:
             if rc < 0:
                 _capi.check(rc, "msnake_space_actions")
             res = (out,) + tuple(t for t in (safe_out, space_out) if t is not None)
+            return res[0] if len(res) == 1 else res
+        if territory:
+            p_terr = self._territory_out(territory_out).data_ptr() if territory_out is not None else None
+            rc = self._L.msnake_territory_actions(self._h, bits, out.data_ptr(), int(out.shape[1]), p_safe, p_terr,
+                                                  self._cur_stream(self.device).cuda_stream)
+            if rc < 0:
+                _capi.check(rc, "msnake_territory_actions")
+            res = (out,) + tuple(t for t in (safe_out, territory_out) if t is not None)
             return res[0] if len(res) == 1 else res
         rc = self._scripted_fn(self._h, _capi.SCRIPTED_POLICY[policy], bits, out.data_ptr(), int(out.shape[1]), p_safe,
                                self._cur_stream(self.device).cuda_stream)
@@ -463,6 +485,21 @@ class MultiSnakeVecEnv:
         rc = self._space_fn(self._h, 0, None, 0, None, self._space_out(out).data_ptr(), self._cur_stream(self.device).cuda_stream)
         if rc < 0:
             _capi.check(rc, "msnake_space_actions")
+        return out
+
+    def territory_device(self, out=None):
+        """uint16 [num_envs, n_snakes, 4]: entry m of a snake is its Voronoi territory behind move m + 1: the number of
+        free cells it reaches from that move's target in strictly fewer steps than any other snake needs from the targets
+        of its own open moves (bodies static, ties to the others); 0 when the move is not open, the body is empty, or
+        another snake can enter the same target.  Equals reachable_space_device() when no other snake can move.  On the
+        device; nothing is synchronised."""
+        if out is None:
+            with self._torch.cuda.device(self.device):
+                out = self._torch.empty((self.num_envs, self.n_snakes, 4), dtype=self._torch.uint16, device=self.device)
+        rc = self._L.msnake_territory_actions(self._h, 0, None, 0, None, self._territory_out(out).data_ptr(),
+                                              self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_territory_actions")
         return out
 
     @property

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Cost of msnake_scripted_actions and msnake_space_actions next to msnake_step on the same handle.  19x19x3 snake_env at
+"""Cost of msnake_scripted_actions, msnake_space_actions and msnake_territory_actions next to msnake_step on the same handle.  19x19x3 snake_env at
 4 096 and 32 768 envs, on a freshly reset batch and 500 steps into safe_greedy play (longer bodies).  The Hamiltonian
 cycle needs an even board: its legs run on a 20x20 handle of the same batch, in the same kind of state.  The "->step"
 legs are one scripted call and one step per call (the self-play loop on the device).  `worst_case_62x62`: the flood
 fill's longest runs, serpentine mazes of a 62x62 board (one corridor of 1 953 cells, along the rows and along the
-columns, nine head positions each), copied over the whole batch.
+columns, nine head positions each), copied over the whole batch; the territory race runs on the same states (the wall
+snake is the opponent), and on `two_ends`, where two snakes enter the corridor from its two ends.
 
 Two figures per leg, both from HIP events after a warm-up, legs alternating in one process:
   graph_us: CALLS back-to-back calls captured into one HIP graph (a linear chain) and replayed: the kernel's cadence,
@@ -13,7 +14,7 @@ Two figures per leg, both from HIP events after a warm-up, legs alternating in o
             Python caller pays when nothing else is queued; mostly the host's submission rate.
 The step leg plays the constant action 1 (with auto reset), so over its CALLS calls the batch leaves the state the run
 is labelled with; the scripted legs read the restored state every time.  The state is restored before every leg.
-    python tools/scripted_cost.py > profiles/scripted_cost.json"""
+    python tools/scripted_cost.py > profiles/territory_cost.json"""
 import argparse
 import json
 import os
@@ -40,6 +41,14 @@ def serpentine_states(dim, transposed):
     return [{"t": 0, "ctr": 0, "spare_fruits": 0, "ep_len": 0, "ep_return": 0.0, "fruits": [[0, 0], [0, 0]],
              "snakes": [[list(path[i])], [list(c) for c in walls]], "vels": [[1, 0]] * 2, "grow_to": [1, len(walls)],
              "alive": [True] * 2, "in_dead": [False] * 2} for i in (0, 1, L // 8, L // 4, L // 3, L // 2, 2 * L // 3, L - 2, L - 1)]
+
+
+def two_ends(states):
+    """The same mazes with the wall stacked under snake 0's head on one end of the corridor and snake 1 on the other: the
+    two fronts meet in the middle after half the corridor's length in rounds."""
+    first, last = states[0]["snakes"][0][0], states[-1]["snakes"][0][0]
+    walls = states[0]["snakes"][1]
+    return [dict(states[0], snakes=[[first] + walls, [last]], grow_to=[len(walls) + 1, 1])]
 
 
 def main():
@@ -75,6 +84,7 @@ def main():
         ones = torch.ones((n, 3), dtype=torch.int32, device=env.device)
         safe = torch.zeros((n, 3), dtype=torch.uint8, device=env.device)
         space = torch.zeros((n, 3, 4), dtype=torch.uint16, device=env.device)
+        terr = torch.zeros((n, 3, 4), dtype=torch.uint16, device=env.device)
         legs = {
             "safe_greedy": lambda: env.scripted_actions_device("safe_greedy", out=acts),
             "safe_greedy+mask": lambda: env.scripted_actions_device("safe_greedy", out=acts, safe_out=safe),
@@ -84,9 +94,14 @@ def main():
             "space_greedy": lambda: env.scripted_actions_device("space_greedy", out=acts),
             "space_greedy+mask+space": lambda: env.scripted_actions_device("space_greedy", out=acts, safe_out=safe, space_out=space),
             "space_only": lambda: env.reachable_space_device(out=space),
+            "territory_greedy": lambda: env.scripted_actions_device("territory_greedy", out=acts),
+            "territory_greedy+mask+territory": lambda: env.scripted_actions_device("territory_greedy", out=acts, safe_out=safe,
+                                                                                   territory_out=terr),
+            "territory_only": lambda: env.territory_device(out=terr),
             "msnake_step": lambda: env.step_device(ones),
             "safe_greedy->step": lambda: env.step_device(env.scripted_actions_device("safe_greedy", out=acts)),
             "space_greedy->step": lambda: env.step_device(env.scripted_actions_device("space_greedy", out=acts)),
+            "territory_greedy->step": lambda: env.step_device(env.scripted_actions_device("territory_greedy", out=acts)),
         }
         out = {}
         for state in ("fresh_reset", f"after_{args.play_steps}_greedy_steps"):
@@ -118,14 +133,18 @@ def main():
                     times[name]["call_us"].append(timed(lambda: [fn() for _ in range(args.calls)]))
             med = lambda v: [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)]
             out[state] = {k: {kind: med(v) for kind, v in t.items()} for k, t in times.items()}
+            print(f"{n} envs, {state}: done", file=sys.stderr, flush=True)
         res["batches"][str(n)] = out
         env.close(), env20.close()
     from oracle.snake_oracle import state_to_flat
     res["worst_case_62x62"] = {}
     for n in args.envs:
         out = {}
-        for name, transposed in (("walls_on_rows", False), ("walls_on_columns", True)):
+        for name, transposed, ends in (("walls_on_rows", False, False), ("walls_on_columns", True, False),
+                                       ("two_ends_rows", False, True), ("two_ends_columns", True, True)):
             states = serpentine_states(62, transposed)
+            if ends:
+                states = two_ends(states)
             src = msnake.MultiSnakeVecEnv(len(states), dim=62, n_snakes=2, rules="snake_env", seed=0)
             env = msnake.MultiSnakeVecEnv(n, dim=62, n_snakes=2, rules="snake_env", seed=0)
             src.reset_device(), env.reset_device()
@@ -134,21 +153,24 @@ def main():
             env.copy_envs_device(src, torch.arange(n, dtype=torch.int32, device=env.device) % len(states))
             acts = torch.ones((n, 2), dtype=torch.int32, device=env.device)
             space = torch.zeros((n, 2, 4), dtype=torch.uint16, device=env.device)
-            fn = lambda: env.scripted_actions_device("space_greedy", out=acts, space_out=space)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                fn(), fn()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                for _ in range(args.calls):
-                    fn()
-            v = [timed(g.replay) for _ in range(args.rounds)]
-            out[name] = {"graph_us": [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)],
-                         "largest_count": int(space.view(torch.int16).max())}
+            out[name] = {}
+            for pol, kw in (("space_greedy", "space_out"), ("territory_greedy", "territory_out")):
+                fn = lambda: env.scripted_actions_device(pol, out=acts, **{kw: space})
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    fn(), fn()
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    for _ in range(args.calls):
+                        fn()
+                v = [timed(g.replay) for _ in range(args.rounds)]
+                out[name][pol] = {"graph_us": [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)],
+                                  "largest_count": int(space.view(torch.int16).max())}
             env.close(), src.close()
+            print(f"{n} envs, worst case {name}: done", file=sys.stderr, flush=True)
         res["worst_case_62x62"][str(n)] = out
     print(json.dumps(res, indent=1))
 
