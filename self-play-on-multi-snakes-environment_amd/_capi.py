@@ -13,18 +13,6 @@ LIB_PATH = os.environ.get("MSNAKE_LIB") or os.path.join(_HERE, "libmsnake.so")
 RULES = {"snake_env": 0, "new_world": 1, "adversarial": 2}
 RULE_NAMES = {v: k for k, v in RULES.items()}
 
-# every extern "C" symbol include/msnake.h declares (tests check the .so exports all of them)
-SYMBOLS = [
-    "msnake_abi_version", "msnake_last_error", "msnake_create", "msnake_destroy", "msnake_obs_shape",
-    "msnake_reset", "msnake_reset_envs", "msnake_step", "msnake_step_tape", "msnake_rollout_tape", "msnake_get_state", "msnake_set_state",
-    "msnake_get_state_all", "msnake_set_state_all", "msnake_state_blob_info",
-    "msnake_render", "msnake_get_stats", "msnake_kernel_name", "msnake_algorithmic_bytes_per_env_step",
-    "msnake_scripted_actions", "msnake_copy_envs", "msnake_kernel_name_for_config",
-    "msnake_set_generic_kernels", "msnake_space_actions", "msnake_render_cells", "msnake_render_local",
-    "msnake_call_shape_for_config", "msnake_territory_actions",
-]
-
-
 class MsnakeConfig(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("device", ctypes.c_int32), ("num_envs", ctypes.c_int32),
                 ("dim", ctypes.c_int32), ("n_snakes", ctypes.c_int32), ("n_fruits", ctypes.c_int32),
@@ -42,6 +30,7 @@ STORE_POLICY = {"auto": 0, "plain": 1, "stream": 2}
 SCRIPTED_POLICY = {None: 0, "safe_greedy": 1, "hamiltonian": 2}  # MSNAKE_POLICY_*
 SPACE_POLICY = "space_greedy"  # no policy id: an entry point of its own (msnake_space_actions)
 TERRITORY_POLICY = "territory_greedy"  # likewise (msnake_territory_actions)
+SCRIPTED_POLICY_NAMES = ("safe_greedy", "hamiltonian", SPACE_POLICY, TERRITORY_POLICY)  # every scripted opponent there is
 
 
 class MsnakeBlobInfo(ctypes.Structure):
@@ -54,6 +43,50 @@ class MsnakeStats(ctypes.Structure):
     _fields_ = [("episodes", ctypes.c_int64), ("ep_len_sum", ctypes.c_int64), ("ep_return_sum", ctypes.c_int64),
                 ("env_steps", ctypes.c_int64), ("errors", ctypes.c_int64), ("reserved", ctypes.c_int64 * 3)]
 
+
+_vp, _i32, _u32, _size = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_size_t
+_int, _cfg = ctypes.c_int, ctypes.POINTER(MsnakeConfig)
+# h, actions_dev, action_stride, n_steps, obs_dev, obs_step_stride, rew_dev, done_dev, info_dev, scalar_step_stride, stream
+_TAPE = [_vp, _vp, _i32, _i32, _vp, _size, _vp, _vp, _vp, _size, _vp]
+# every extern "C" symbol include/msnake.h declares (tests check the .so exports all of them): name -> (restype, argtypes)
+PROTOTYPES = {
+    "msnake_abi_version": (_int, None),
+    "msnake_last_error": (ctypes.c_char_p, None),
+    "msnake_create": (_int, [_cfg, ctypes.POINTER(_vp)]),
+    "msnake_destroy": (_int, [_vp]),
+    "msnake_obs_shape": (_int, [_vp] + [ctypes.POINTER(_i32)] * 3),  # h, H, W, C
+    "msnake_reset": (_int, [_vp, _vp, _vp]),  # h, obs_dev, stream
+    "msnake_reset_envs": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # h, mask_dev, obs_dev, final_obs_dev, truncated_dev, stream
+    # h, actions_dev, action_stride, obs_dev, rew_dev, done_dev, info_dev, stream
+    "msnake_step": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "msnake_step_tape": (_int, _TAPE),
+    "msnake_rollout_tape": (_int, _TAPE),
+    "msnake_get_state": (_int, [_vp, _i32, _vp, _i32]),  # h, env, words, cap_words
+    "msnake_set_state": (_int, [_vp, _i32, _vp, _i32]),  # h, env, words, n
+    "msnake_get_state_all": (ctypes.c_int64, [_vp, _vp, _size]),  # h, buf, cap_bytes
+    "msnake_set_state_all": (_int, [_vp, _vp, _size]),  # h, buf, bytes
+    "msnake_state_blob_info": (_int, [_vp, _size, ctypes.POINTER(MsnakeBlobInfo)]),  # buf, bytes, out
+    "msnake_render": (_int, [_vp, _vp, _vp]),  # h, obs_dev, stream
+    "msnake_get_stats": (_int, [_vp, ctypes.POINTER(MsnakeStats), _i32]),  # h, out, reset
+    "msnake_kernel_name": (ctypes.c_char_p, [_vp]),
+    "msnake_algorithmic_bytes_per_env_step": (ctypes.c_int64, [_vp]),
+    # h, policy, snake_mask, actions_dev, action_stride, safe_dev, stream
+    "msnake_scripted_actions": (_int, [_vp, _i32, _u32, _vp, _i32, _vp, _vp]),
+    "msnake_copy_envs": (_int, [_vp, _vp, _vp, _vp]),  # dst, src, src_index_dev (int32 [dst.num_envs] or NULL), stream
+    "msnake_kernel_name_for_config": (_int, [_cfg, ctypes.c_char_p, _size]),  # cfg, out, n
+    "msnake_set_generic_kernels": (_int, [_i32]),
+    # h, snake_mask, actions_dev, action_stride, safe_dev, space_dev (uint16 [num_envs][n_snakes][4]), stream
+    "msnake_space_actions": (_int, [_vp, _u32, _vp, _i32, _vp, _vp, _vp]),
+    # h, view_mask, cells_dev (uint8 [num_envs][V][dim][dim]), snakes_dev (int32 [num_envs][n_snakes][8] or NULL), stream
+    "msnake_render_cells": (_int, [_vp, _u32, _vp, _vp, _vp]),
+    # h, radius, snake_mask, oriented, windows_dev (uint8 [num_envs][S][W][W]), heading_dev (uint8 [num_envs][S] or NULL), stream
+    "msnake_render_local": (_int, [_vp, _i32, _u32, _i32, _vp, _vp, _vp]),
+    # cfg, action_stride, obs / rew / done / info (addresses, only looked at), out
+    "msnake_call_shape_for_config": (_int, [_cfg, _i32, _vp, _vp, _vp, _vp, ctypes.POINTER(_i32)]),
+    # h, snake_mask, actions_dev, action_stride, safe_dev, territory_dev (uint16 [num_envs][n_snakes][4]), stream
+    "msnake_territory_actions": (_int, [_vp, _u32, _vp, _i32, _vp, _vp, _vp]),
+}
+SYMBOLS = list(PROTOTYPES)
 
 _lib = None
 
@@ -76,51 +109,9 @@ def load():
     # process, and that one finds no device (msnake_create -> MSNAKE_E_NOGPU).
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    vp, i32, u8p = ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p
-    L.msnake_abi_version.restype = ctypes.c_int
-    L.msnake_last_error.restype = ctypes.c_char_p
-    L.msnake_create.argtypes = [ctypes.POINTER(MsnakeConfig), ctypes.POINTER(vp)]
-    L.msnake_destroy.argtypes = [vp]
-    L.msnake_obs_shape.argtypes = [vp] + [ctypes.POINTER(i32)] * 3
-    L.msnake_reset.argtypes = [vp, u8p, vp]
-    L.msnake_render.argtypes = [vp, u8p, vp]
-    L.msnake_reset_envs.argtypes = [vp, u8p, u8p, u8p, u8p, vp]
-    L.msnake_step.argtypes = [vp, vp, i32, u8p, vp, vp, vp, vp]
-    L.msnake_scripted_actions.argtypes = [vp, i32, ctypes.c_uint32, vp, i32, u8p, vp]
-    # h, snake_mask, actions_dev, action_stride, safe_dev, space_dev (uint16 [num_envs][n_snakes][4]), stream
-    L.msnake_space_actions.argtypes = [vp, ctypes.c_uint32, vp, i32, u8p, vp, vp]
-    # h, snake_mask, actions_dev, action_stride, safe_dev, territory_dev (uint16 [num_envs][n_snakes][4]), stream
-    L.msnake_territory_actions.argtypes = [vp, ctypes.c_uint32, vp, i32, u8p, vp, vp]
-    # h, view_mask, cells_dev (uint8 [num_envs][V][dim][dim]), snakes_dev (int32 [num_envs][n_snakes][8] or NULL), stream
-    L.msnake_render_cells.argtypes = [vp, ctypes.c_uint32, u8p, vp, vp]
-    # h, radius, snake_mask, oriented, windows_dev (uint8 [num_envs][S][W][W]), heading_dev (uint8 [num_envs][S] or NULL), stream
-    L.msnake_render_local.argtypes = [vp, i32, ctypes.c_uint32, i32, u8p, u8p, vp]
-    L.msnake_copy_envs.argtypes = [vp, vp, vp, vp]  # dst, src, src_index_dev (int32 [dst.num_envs] or NULL), stream
-    L.msnake_step_tape.argtypes = [vp, vp, i32, i32, u8p, ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, vp]
-    L.msnake_rollout_tape.argtypes = L.msnake_step_tape.argtypes
-    L.msnake_get_state.argtypes = [vp, i32, vp, i32]
-    L.msnake_set_state.argtypes = [vp, i32, vp, i32]
-    L.msnake_get_state_all.argtypes = [vp, vp, ctypes.c_size_t]
-    L.msnake_get_state_all.restype = ctypes.c_int64
-    L.msnake_set_state_all.argtypes = [vp, vp, ctypes.c_size_t]
-    L.msnake_state_blob_info.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(MsnakeBlobInfo)]
-    L.msnake_get_stats.argtypes = [vp, ctypes.POINTER(MsnakeStats), i32]
-    L.msnake_kernel_name.argtypes = [vp]
-    L.msnake_kernel_name.restype = ctypes.c_char_p
-    L.msnake_kernel_name_for_config.argtypes = [ctypes.POINTER(MsnakeConfig), ctypes.c_char_p, ctypes.c_size_t]
-    L.msnake_kernel_name_for_config.restype = ctypes.c_int
-    L.msnake_set_generic_kernels.argtypes = [i32]
-    # cfg, action_stride, obs / rew / done / info (addresses, only looked at), out
-    L.msnake_call_shape_for_config.argtypes = [ctypes.POINTER(MsnakeConfig), i32, vp, vp, vp, vp, ctypes.POINTER(i32)]
-    L.msnake_call_shape_for_config.restype = ctypes.c_int
-    L.msnake_set_generic_kernels.restype = ctypes.c_int
-    L.msnake_algorithmic_bytes_per_env_step.argtypes = [vp]
-    L.msnake_algorithmic_bytes_per_env_step.restype = ctypes.c_int64
-    for name in ("msnake_create", "msnake_destroy", "msnake_obs_shape", "msnake_reset", "msnake_reset_envs", "msnake_render",
-                 "msnake_step", "msnake_step_tape", "msnake_rollout_tape", "msnake_get_state", "msnake_set_state", "msnake_set_state_all",
-                 "msnake_state_blob_info", "msnake_get_stats", "msnake_scripted_actions", "msnake_copy_envs",
-                 "msnake_space_actions", "msnake_render_cells", "msnake_render_local", "msnake_territory_actions"):
-        getattr(L, name).restype = ctypes.c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

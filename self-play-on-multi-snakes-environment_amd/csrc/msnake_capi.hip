@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "msnake_internal.h"
@@ -72,6 +73,53 @@ namespace {
 
 int check(msnake_handle h) {
     if (!h || h->magic != kMagic) return fail(MSNAKE_E_HANDLE, "invalid or destroyed msnake handle");
+    return MSNAKE_OK;
+}
+
+// a launch's hipError_t -> the return code and the message
+int launched(hipError_t e) {
+    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return MSNAKE_OK;
+}
+
+// every device allocation of a handle, complete or partly built, and the handle itself (on the handle's device)
+struct ReleaseHandle {
+    void operator()(msnake_env* h) const {
+        (void)hipFree(h->d_state); (void)hipFree(h->d_stats);
+        if (h->d_scratch) (void)hipFree(h->d_scratch);
+        h->magic = 0; free(h);
+    }
+};
+
+// msnake_step's action_stride (msnake_call_shape_for_config checks nothing else)
+int check_action_stride(int32_t action_stride, int ns) {
+    if (action_stride < ns || action_stride > 7)
+        return fail(MSNAKE_E_ARG, "action_stride %d must be in [n_snakes=%d, 7]", action_stride, ns);
+    return MSNAKE_OK;
+}
+
+// the arguments of a step (msnake_step, msnake_rollout_tape); `fn` names the entry point in the message
+int check_step_args(const char* fn, int ns, const int32_t* actions, int32_t action_stride, const float* rew, const uint8_t* done, const msnake_info* info) {
+    if (!actions || !rew || !done) return fail(MSNAKE_E_ARG, "%s: actions/rew/done must not be NULL", fn);
+    if (int rc = check_action_stride(action_stride, ns)) return rc;
+    if (((uintptr_t)actions & 3) || ((uintptr_t)rew & 3) || ((uintptr_t)info & 15))
+        return fail(MSNAKE_E_ALIGN, "actions/rew must be 4-byte and info 16-byte aligned");
+    return MSNAKE_OK;
+}
+
+// the per-call fields of a copy of the handle's StepParams
+void fill_call(msnake::StepParams& p, const int32_t* actions, int32_t action_stride, uint8_t* obs, float* rew, uint8_t* done, msnake_info* info) {
+    p.actions = actions; p.action_stride = action_stride;
+    p.obs = obs; p.rest.rew = rew; p.rest.done = done; p.rest.info = info;
+}
+
+// the arguments of a call that may write actions (msnake_scripted_ / _space_ / _territory_actions); the last two count only if it does
+int check_action_writer(const char* fn, int ns, bool writes_actions, uint32_t snake_mask, const int32_t* actions_dev, int32_t action_stride) {
+    if (snake_mask >> ns) return fail(MSNAKE_E_ARG, "%s: snake_mask 0x%x has a bit >= n_snakes=%d", fn, snake_mask, ns);
+    if (!writes_actions) return MSNAKE_OK;
+    if (!actions_dev) return fail(MSNAKE_E_ARG, "%s: actions_dev is NULL", fn);
+    if (action_stride < ns) return fail(MSNAKE_E_ARG, "%s: action_stride %d must be >= n_snakes=%d", fn, action_stride, ns);
+    if ((uintptr_t)actions_dev & 3) return fail(MSNAKE_E_ALIGN, "actions_dev must be 4-byte aligned");
     return MSNAKE_OK;
 }
 
@@ -210,6 +258,15 @@ int pick_spec_dim(const msnake::StepParams& p, int rules) {
     return msnake::spec_dim_of(p, rules);
 }
 
+// what a handle created from *cfg_in right now would step with, without a GPU: the *_for_config calls
+int shape_for_config(const msnake_config* cfg_in, msnake_config* cfg, msnake::StepParams& p) {
+    if (int rc = validate_config(cfg_in, cfg)) return rc;
+    memset(&p, 0, sizeof(p));
+    if (int rc = derive_shape(cfg, p)) return rc;
+    p.spec_dim = pick_spec_dim(p, cfg->rules);
+    return MSNAKE_OK;
+}
+
 }  // namespace
 
 int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
@@ -226,14 +283,13 @@ int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
         return fail(MSNAKE_E_ARG, "device %d out of range (have %d)", cfg->device, ndev);
     DeviceGuard guard(cfg->device);
 
-    msnake_env* h = static_cast<msnake_env*>(calloc(1, sizeof(msnake_env)));
+    // (released on every return but the last one)
+    std::unique_ptr<msnake_env, ReleaseHandle> owner(static_cast<msnake_env*>(calloc(1, sizeof(msnake_env))));
+    msnake_env* h = owner.get();
     if (!h) return fail(MSNAKE_E_ARG, "out of host memory");
     h->cfg = *cfg;
     msnake::StepParams& p = h->p;
-    if (int rc = derive_shape(cfg, p)) {
-        free(h);
-        return rc;
-    }
+    if (int rc = derive_shape(cfg, p)) return rc;
     const int dim = cfg->dim, W = dim + 2, n2 = dim * dim;
     const int K = cfg->obs_scale;
     p.rest.seed_lo = (uint32_t)cfg->seed;
@@ -252,11 +308,8 @@ int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
     const size_t state_bytes = sec.total;
     hipError_t e;
     if ((e = hipMalloc(&h->d_state, state_bytes)) != hipSuccess || (e = hipMalloc(&h->d_stats, 64)) != hipSuccess ||
-        (e = hipMemset(h->d_state, 0, state_bytes)) != hipSuccess || (e = hipMemset(h->d_stats, 0, 64)) != hipSuccess) {
-        (void)hipFree(h->d_state); (void)hipFree(h->d_stats);
-        free(h);
+        (e = hipMemset(h->d_state, 0, state_bytes)) != hipSuccess || (e = hipMemset(h->d_stats, 0, 64)) != hipSuccess)
         return fail(MSNAKE_E_HIP, "allocating %zu bytes of env state failed: %s", state_bytes, hipGetErrorString(e));
-    }
     p.state = static_cast<uint8_t*>(h->d_state);
     p.hdr = reinterpret_cast<uint32_t*>(p.state + sec.hdr);
     p.body0 = reinterpret_cast<uint16_t*>(p.state + sec.body0);
@@ -272,11 +325,8 @@ int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
             for (int c = 0; c < W; ++c)
                 if (r == 0 || r == W - 1 || c == 0 || c == W - 1)
                     memset(&tmpl[(size_t)copy * p.img_bytes + copy + ((size_t)r * W + c) * p.C * K], 255, (size_t)p.C * K);
-    if ((e = hipMemcpy(const_cast<uint8_t*>(p.tmpl), tmpl.data(), tmpl_bytes, hipMemcpyHostToDevice)) != hipSuccess) {
-        (void)hipFree(h->d_state); (void)hipFree(h->d_stats);
-        free(h);
+    if ((e = hipMemcpy(const_cast<uint8_t*>(p.tmpl), tmpl.data(), tmpl_bytes, hipMemcpyHostToDevice)) != hipSuccess)
         return fail(MSNAKE_E_HIP, "uploading the background image failed: %s", hipGetErrorString(e));
-    }
     if (cfg->envs_per_block > 0 && cfg->envs_per_block < h->epb) h->epb = cfg->envs_per_block;  // (never above what LDS allows)
     // obs_store_policy: should the observation stores carry the nt (streaming) hint?  Measured on
     // MI355X with the native 16-byte-per-lane copy-out (tools/kbench.py --store-policy plain/stream), per launch:
@@ -306,7 +356,7 @@ int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
     p.spec_dim = pick_spec_dim(p, cfg->rules);
     msnake::step_kernel_name(cfg->rules, cfg->n_snakes, cfg->obs_scale, p.spec_dim, h->kname, sizeof(h->kname));
     h->magic = kMagic;
-    *out = h;
+    *out = owner.release();
     return MSNAKE_OK;
 }
 
@@ -314,10 +364,7 @@ int msnake_destroy(msnake_handle h) {
     if (int rc = check(h)) return rc;
     DeviceGuard guard(h->cfg.device);
     (void)hipDeviceSynchronize();
-    (void)hipFree(h->d_state); (void)hipFree(h->d_stats);
-    if (h->d_scratch) (void)hipFree(h->d_scratch);
-    h->magic = 0;
-    free(h);
+    ReleaseHandle()(h);
     return MSNAKE_OK;
 }
 
@@ -333,20 +380,16 @@ static int launch(msnake_handle h, int mode, const int32_t* actions, int32_t act
                   uint8_t* done, msnake_info* info, void* stream, const uint8_t* env_mask = nullptr,
                   uint8_t* truncated = nullptr) {
     msnake::StepParams p = h->p;
-    p.actions = actions; p.action_stride = action_stride;
-    p.obs = obs; p.rest.rew = rew; p.rest.done = done; p.rest.info = info;
+    fill_call(p, actions, action_stride, obs, rew, done, info);
     p.rest.env_mask = env_mask; p.rest.truncated = truncated;  // (MODE 1 / 2 only; msnake_reset_envs)
     DeviceGuard guard(h->cfg.device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (obs && p.obs_scale > 1 && ((uintptr_t)obs & 3))  // the fused x4 / x7 copy-out stores dwords
         return fail(MSNAKE_E_ALIGN, "obs_dev must be 4-byte aligned when obs_scale > 1");
 #if defined(MSNAKE_DBG_STAGES) || defined(MSNAKE_SPAN_LIGHT)
     if (h->dbg_span && mode == 0)  // every msnake_step launch stamps into its own slot (they wrap)
         p.rest.dbg_span = h->dbg_span + (size_t)(h->dbg_launch++ % h->dbg_span_slots) * (size_t)p.nenv * 8;
 #endif
-    hipError_t e = msnake::launch_step(p, h->cfg.rules, mode, h->epb, s);
-    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return MSNAKE_OK;
+    return launched(msnake::launch_step(p, h->cfg.rules, mode, h->epb, static_cast<hipStream_t>(stream)));
 }
 
 int msnake_reset(msnake_handle h, uint8_t* obs_dev, void* stream) {
@@ -376,11 +419,7 @@ int msnake_render(msnake_handle h, uint8_t* obs_dev, void* stream) {
 int msnake_step(msnake_handle h, const int32_t* actions_dev, int32_t action_stride, uint8_t* obs_dev, float* rew_dev,
                 uint8_t* done_dev, msnake_info* info_dev, void* stream) {
     if (int rc = check(h)) return rc;
-    if (!actions_dev || !rew_dev || !done_dev) return fail(MSNAKE_E_ARG, "msnake_step: actions/rew/done must not be NULL");
-    if (action_stride < h->p.n_snakes || action_stride > 7)
-        return fail(MSNAKE_E_ARG, "action_stride %d must be in [n_snakes=%d, 7]", action_stride, h->p.n_snakes);
-    if (((uintptr_t)actions_dev & 3) || ((uintptr_t)rew_dev & 3) || ((uintptr_t)info_dev & 15))
-        return fail(MSNAKE_E_ALIGN, "actions/rew must be 4-byte and info 16-byte aligned");
+    if (int rc = check_step_args("msnake_step", h->p.n_snakes, actions_dev, action_stride, rew_dev, done_dev, info_dev)) return rc;
     int rc = launch(h, 0, actions_dev, action_stride, obs_dev, rew_dev, done_dev, info_dev, stream);
     if (rc == MSNAKE_OK) h->env_steps += h->p.nenv;
     return rc;
@@ -407,14 +446,9 @@ int msnake_rollout_tape(msnake_handle h, const int32_t* actions_dev, int32_t act
                         size_t scalar_step_stride, void* stream) {
     if (int rc = check(h)) return rc;
     if (n_steps < 1) return fail(MSNAKE_E_ARG, "n_steps must be >= 1");
-    if (!actions_dev || !rew_dev || !done_dev) return fail(MSNAKE_E_ARG, "msnake_rollout_tape: actions/rew/done must not be NULL");
-    if (action_stride < h->p.n_snakes || action_stride > 7)
-        return fail(MSNAKE_E_ARG, "action_stride %d must be in [n_snakes=%d, 7]", action_stride, h->p.n_snakes);
-    if (((uintptr_t)actions_dev & 3) || ((uintptr_t)rew_dev & 3) || ((uintptr_t)info_dev & 15))
-        return fail(MSNAKE_E_ALIGN, "actions/rew must be 4-byte and info 16-byte aligned");
+    if (int rc = check_step_args("msnake_rollout_tape", h->p.n_snakes, actions_dev, action_stride, rew_dev, done_dev, info_dev)) return rc;
     msnake::StepParams p = h->p;
-    p.actions = actions_dev; p.action_stride = action_stride;
-    p.obs = obs_dev; p.rest.rew = rew_dev; p.rest.done = done_dev; p.rest.info = info_dev;
+    fill_call(p, actions_dev, action_stride, obs_dev, rew_dev, done_dev, info_dev);
     p.rest.n_steps = n_steps;
     // tape_store_policy: a tape whose steps keep one alignment (step stride a multiple of 16 bytes: the aligned copy-out)
     // and whose observations go to per-step slices of >= 192 MiB in all streams (4 096 envs x 256 steps = 4.2 GB: 3.8 us per
@@ -430,11 +464,9 @@ int msnake_rollout_tape(msnake_handle h, const int32_t* actions_dev, int32_t act
     if (obs_dev && p.obs_scale > 1 && (((uintptr_t)obs_dev | obs_step_stride) & 3))
         return fail(MSNAKE_E_ALIGN, "obs_dev and obs_step_stride must be multiples of 4 when obs_scale > 1");
     DeviceGuard guard(h->cfg.device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = msnake::launch_step(p, h->cfg.rules, 3, h->epb, s);
-    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    h->env_steps += (int64_t)h->p.nenv * n_steps;
-    return MSNAKE_OK;
+    int rc = launched(msnake::launch_step(p, h->cfg.rules, 3, h->epb, static_cast<hipStream_t>(stream)));
+    if (rc == MSNAKE_OK) h->env_steps += (int64_t)h->p.nenv * n_steps;
+    return rc;
 }
 
 int msnake_scripted_actions(msnake_handle h, int32_t policy, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride,
@@ -443,61 +475,41 @@ int msnake_scripted_actions(msnake_handle h, int32_t policy, uint32_t snake_mask
     const int ns = h->p.n_snakes;
     if (policy != MSNAKE_POLICY_NONE && policy != MSNAKE_POLICY_SAFE_GREEDY && policy != MSNAKE_POLICY_HAMILTONIAN)
         return fail(MSNAKE_E_ARG, "msnake_scripted_actions: policy %d is not one of MSNAKE_POLICY_*", policy);
-    if (snake_mask >> ns) return fail(MSNAKE_E_ARG, "msnake_scripted_actions: snake_mask 0x%x has a bit >= n_snakes=%d", snake_mask, ns);
-    if (policy == MSNAKE_POLICY_HAMILTONIAN && (h->p.dim & 1))
+    // (a snake_mask bit >= n_snakes is reported first: the parity check waits for a good mask)
+    if (policy == MSNAKE_POLICY_HAMILTONIAN && (h->p.dim & 1) && !(snake_mask >> ns))
         return fail(MSNAKE_E_ARG, "msnake_scripted_actions: policy HAMILTONIAN needs an even dim (the cycle), got dim %d", h->p.dim);
     const bool writes_actions = policy != MSNAKE_POLICY_NONE && snake_mask != 0;
+    if (int rc = check_action_writer("msnake_scripted_actions", ns, writes_actions, snake_mask, actions_dev, action_stride)) return rc;
     if (!writes_actions && !safe_dev)
         return fail(MSNAKE_E_ARG, "msnake_scripted_actions: nothing to write (policy NONE or snake_mask 0, and safe_dev is NULL)");
-    if (writes_actions && !actions_dev) return fail(MSNAKE_E_ARG, "msnake_scripted_actions: actions_dev is NULL");
-    if (writes_actions && action_stride < ns)
-        return fail(MSNAKE_E_ARG, "msnake_scripted_actions: action_stride %d must be >= n_snakes=%d", action_stride, ns);
-    if (writes_actions && ((uintptr_t)actions_dev & 3)) return fail(MSNAKE_E_ALIGN, "actions_dev must be 4-byte aligned");
     DeviceGuard guard(h->cfg.device);
     // without actions to write the kernel only fills safe_dev: POLICY_NONE
-    hipError_t e = msnake::launch_scripted(h->p, h->cfg.rules, writes_actions ? policy : MSNAKE_POLICY_NONE, snake_mask, actions_dev,
-                                           action_stride, safe_dev, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return MSNAKE_OK;
+    return launched(msnake::launch_scripted(h->p, h->cfg.rules, writes_actions ? policy : MSNAKE_POLICY_NONE, snake_mask, actions_dev,
+                                            action_stride, safe_dev, static_cast<hipStream_t>(stream)));
 }
 
 int msnake_space_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride, uint8_t* safe_dev,
                          uint16_t* space_dev, void* stream) {
     if (int rc = check(h)) return rc;
-    const int ns = h->p.n_snakes;
-    if (snake_mask >> ns) return fail(MSNAKE_E_ARG, "msnake_space_actions: snake_mask 0x%x has a bit >= n_snakes=%d", snake_mask, ns);
+    if (int rc = check_action_writer("msnake_space_actions", h->p.n_snakes, snake_mask != 0, snake_mask, actions_dev, action_stride)) return rc;
     if (!snake_mask && !safe_dev && !space_dev)
         return fail(MSNAKE_E_ARG, "msnake_space_actions: nothing to write (snake_mask 0, safe_dev and space_dev are NULL)");
-    if (snake_mask && !actions_dev) return fail(MSNAKE_E_ARG, "msnake_space_actions: actions_dev is NULL");
-    if (snake_mask && action_stride < ns)
-        return fail(MSNAKE_E_ARG, "msnake_space_actions: action_stride %d must be >= n_snakes=%d", action_stride, ns);
-    if (snake_mask && ((uintptr_t)actions_dev & 3)) return fail(MSNAKE_E_ALIGN, "actions_dev must be 4-byte aligned");
     if ((uintptr_t)space_dev & 1) return fail(MSNAKE_E_ALIGN, "space_dev must be 2-byte aligned");
     DeviceGuard guard(h->cfg.device);
-    hipError_t e = msnake::launch_space(h->p, h->cfg.rules, snake_mask, actions_dev, action_stride, safe_dev, space_dev,
-                                        static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return MSNAKE_OK;
+    return launched(msnake::launch_space(h->p, h->cfg.rules, snake_mask, actions_dev, action_stride, safe_dev, space_dev,
+                                         static_cast<hipStream_t>(stream)));
 }
 
 int msnake_territory_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride, uint8_t* safe_dev,
                              uint16_t* territory_dev, void* stream) {
     if (int rc = check(h)) return rc;
-    const int ns = h->p.n_snakes;
-    if (snake_mask >> ns)
-        return fail(MSNAKE_E_ARG, "msnake_territory_actions: snake_mask 0x%x has a bit >= n_snakes=%d", snake_mask, ns);
-    if (snake_mask && !actions_dev) return fail(MSNAKE_E_ARG, "msnake_territory_actions: actions_dev is NULL");
-    if (snake_mask && action_stride < ns)
-        return fail(MSNAKE_E_ARG, "msnake_territory_actions: action_stride %d must be >= n_snakes=%d", action_stride, ns);
+    if (int rc = check_action_writer("msnake_territory_actions", h->p.n_snakes, snake_mask != 0, snake_mask, actions_dev, action_stride)) return rc;
     if (!snake_mask && !safe_dev && !territory_dev)
         return fail(MSNAKE_E_ARG, "msnake_territory_actions: nothing to write (snake_mask 0, safe_dev and territory_dev are NULL)");
-    if (snake_mask && ((uintptr_t)actions_dev & 3)) return fail(MSNAKE_E_ALIGN, "actions_dev must be 4-byte aligned");
     if ((uintptr_t)territory_dev & 1) return fail(MSNAKE_E_ALIGN, "territory_dev must be 2-byte aligned");
     DeviceGuard guard(h->cfg.device);
-    hipError_t e = msnake::launch_territory(h->p, h->cfg.rules, snake_mask, actions_dev, action_stride, safe_dev, territory_dev,
-                                            static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return MSNAKE_OK;
+    return launched(msnake::launch_territory(h->p, h->cfg.rules, snake_mask, actions_dev, action_stride, safe_dev, territory_dev,
+                                             static_cast<hipStream_t>(stream)));
 }
 
 int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_index_dev, void* stream) {
@@ -521,9 +533,7 @@ int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_in
     if ((uintptr_t)src_index_dev & 3) return fail(MSNAKE_E_ALIGN, "src_index_dev must be 4-byte aligned");
     DeviceGuard guard(d.device);
     if (src->offgrid_head) note_offgrid_head(dst);
-    hipError_t e = msnake::launch_copy_envs(dst->p, src->p, d.rules, src_index_dev, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return MSNAKE_OK;
+    return launched(msnake::launch_copy_envs(dst->p, src->p, d.rules, src_index_dev, static_cast<hipStream_t>(stream)));
 }
 
 int msnake_render_cells(msnake_handle h, uint32_t view_mask, uint8_t* cells_dev, int32_t* snakes_dev, void* stream) {
@@ -536,9 +546,7 @@ int msnake_render_cells(msnake_handle h, uint32_t view_mask, uint8_t* cells_dev,
         return fail(MSNAKE_E_ARG, "msnake_render_cells: nothing to write (view_mask 0 and snakes_dev is NULL)");
     if ((uintptr_t)snakes_dev & 3) return fail(MSNAKE_E_ALIGN, "snakes_dev must be 4-byte aligned");
     DeviceGuard guard(h->cfg.device);
-    hipError_t e = msnake::launch_cells(h->p, h->cfg.rules, view_mask, cells_dev, snakes_dev, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return MSNAKE_OK;
+    return launched(msnake::launch_cells(h->p, h->cfg.rules, view_mask, cells_dev, snakes_dev, static_cast<hipStream_t>(stream)));
 }
 
 int msnake_render_local(msnake_handle h, int32_t radius, uint32_t snake_mask, int32_t oriented, uint8_t* windows_dev,
@@ -552,10 +560,8 @@ int msnake_render_local(msnake_handle h, int32_t radius, uint32_t snake_mask, in
     if (oriented != 0 && oriented != 1) return fail(MSNAKE_E_ARG, "msnake_render_local: oriented must be 0 or 1, got %d", oriented);
     if (!windows_dev) return fail(MSNAKE_E_ARG, "msnake_render_local: windows_dev is NULL");
     DeviceGuard guard(h->cfg.device);
-    hipError_t e = msnake::launch_local(h->p, h->cfg.rules, radius, snake_mask, oriented, windows_dev, heading_dev,
-                                        static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(MSNAKE_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return MSNAKE_OK;
+    return launched(msnake::launch_local(h->p, h->cfg.rules, radius, snake_mask, oriented, windows_dev, heading_dev,
+                                         static_cast<hipStream_t>(stream)));
 }
 
 // ---- canonical state import / export.  The device packs / unpacks (msnake_state_*_kernel); the host
@@ -736,11 +742,9 @@ const char* msnake_kernel_name(msnake_handle h) {
 int msnake_kernel_name_for_config(const msnake_config* cfg_in, char* out, size_t n) {
     if (!cfg_in || !out || n == 0) return fail(MSNAKE_E_ARG, "msnake_kernel_name_for_config: NULL argument");
     msnake_config cfg;
-    if (int rc = validate_config(cfg_in, &cfg)) return rc;
     msnake::StepParams p;
-    memset(&p, 0, sizeof(p));
-    if (int rc = derive_shape(&cfg, p)) return rc;
-    msnake::step_kernel_name(cfg.rules, cfg.n_snakes, cfg.obs_scale, pick_spec_dim(p, cfg.rules), out, n);
+    if (int rc = shape_for_config(cfg_in, &cfg, p)) return rc;
+    msnake::step_kernel_name(cfg.rules, cfg.n_snakes, cfg.obs_scale, p.spec_dim, out, n);
     return MSNAKE_OK;
 }
 
@@ -748,18 +752,11 @@ int msnake_call_shape_for_config(const msnake_config* cfg_in, int32_t action_str
                                  const void* done_dev, const void* info_dev, int32_t* out) {
     if (!cfg_in || !out) return fail(MSNAKE_E_ARG, "msnake_call_shape_for_config: NULL argument");
     msnake_config cfg;
-    if (int rc = validate_config(cfg_in, &cfg)) return rc;
     msnake::StepParams p;
-    memset(&p, 0, sizeof(p));
-    if (int rc = derive_shape(&cfg, p)) return rc;
-    if (action_stride < p.n_snakes || action_stride > 7)
-        return fail(MSNAKE_E_ARG, "action_stride %d must be in [n_snakes=%d, 7]", action_stride, p.n_snakes);
-    p.spec_dim = pick_spec_dim(p, cfg.rules);
-    p.action_stride = action_stride;
-    p.obs = static_cast<uint8_t*>(const_cast<void*>(obs_dev));
-    p.rest.rew = static_cast<float*>(const_cast<void*>(rew_dev));
-    p.rest.done = static_cast<uint8_t*>(const_cast<void*>(done_dev));
-    p.rest.info = static_cast<msnake_info*>(const_cast<void*>(info_dev));
+    if (int rc = shape_for_config(cfg_in, &cfg, p)) return rc;
+    if (int rc = check_action_stride(action_stride, p.n_snakes)) return rc;
+    fill_call(p, nullptr, action_stride, static_cast<uint8_t*>(const_cast<void*>(obs_dev)), static_cast<float*>(const_cast<void*>(rew_dev)),
+              static_cast<uint8_t*>(const_cast<void*>(done_dev)), static_cast<msnake_info*>(const_cast<void*>(info_dev)));
     *out = msnake::call_shape_of(p, 0);
     return MSNAKE_OK;
 }

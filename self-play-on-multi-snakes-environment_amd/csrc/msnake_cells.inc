@@ -151,16 +151,9 @@ hipError_t launch_cells(const StepParams& p, int rules, uint32_t view_mask, uint
                       p.fcap, rules, nplanes, views4, slice_words};
     const size_t lds = (size_t)CELLS_WAVES * slice_words * 4;  // <= 4 x 15 384 bytes
     const dim3 grid((unsigned)((p.nenv + CELLS_WAVES - 1) / CELLS_WAVES)), block(CELLS_WAVES * 64);
-    const int which = (nplanes ? 2 : 0) | (snakes ? 1 : 0);
-#define MSNAKE_CELLS(C, T) hipLaunchKernelGGL((msnake_cells_kernel<C, T>), grid, block, lds, stream, a)
-    switch (which) {
-        case 1: MSNAKE_CELLS(false, true); break;
-        case 2: MSNAKE_CELLS(true, false); break;
-        case 3: MSNAKE_CELLS(true, true); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef MSNAKE_CELLS
-    return hipGetLastError();
+    return launch_by_flags<2>((nplanes ? 2 : 0) | (snakes ? 1 : 0), [&](auto planes, auto table) {
+        hipLaunchKernelGGL((msnake_cells_kernel<planes.value, table.value>), grid, block, lds, stream, a);
+    });
 }
 
 }  // namespace msnake

@@ -1997,6 +1997,22 @@ void step_kernel_name(int rules, int n_snakes, int obs_scale, int spec_dim, char
     else snprintf(out, n, "msnake_step_kernel<%d, %d, 0, %d>", rules, n_snakes, obs_scale);
 }
 
+// Run-time flags -> bool template arguments, for the launchers of the off-step kernels: bit N - 1 - i of `flags` becomes
+// argument i of f(std::bool_constant<..>...), which launches.  Host code only.  No flag set (nothing to write) is
+// hipErrorInvalidValue, and f is never instantiated for it: no kernel exists for that combination.
+template <int N, bool... B, typename F>
+static hipError_t launch_by_flags(int flags, const F& f) {
+    if constexpr (N > 0) {
+        // (the clear bit first: the kernels are emitted in ascending order of `flags`, and `make isa` listings compare by position)
+        return !((flags >> (N - 1)) & 1) ? launch_by_flags<N - 1, B..., false>(flags, f) : launch_by_flags<N - 1, B..., true>(flags, f);
+    } else if constexpr ((B || ...)) {
+        f(std::bool_constant<B>{}...);
+        return hipGetLastError();
+    } else {
+        return hipErrorInvalidValue;
+    }
+}
+
 }  // namespace msnake
 
 #include "msnake_scripted.inc"  // msnake_scripted_actions: scripted opponents and safe-move masks (off the step path)

@@ -221,20 +221,9 @@ hipError_t launch_space(const StepParams& p, int rules, uint32_t snake_mask, int
                         uint16_t* space, hipStream_t stream) {
     const SpaceArgs a{state_view(p, rules), actions, safe, space, action_stride, snake_mask};
     const dim3 grid((unsigned)((p.nenv + SPACE_WAVES - 1) / SPACE_WAVES)), block(SPACE_WAVES * 64);
-    const int which = (snake_mask != 0u ? 4 : 0) | (safe ? 2 : 0) | (space ? 1 : 0);
-#define MSNAKE_SPACE(A, S, C) hipLaunchKernelGGL((msnake_space_kernel<A, S, C>), grid, block, 0, stream, a)
-    switch (which) {
-        case 1: MSNAKE_SPACE(false, false, true); break;
-        case 2: MSNAKE_SPACE(false, true, false); break;
-        case 3: MSNAKE_SPACE(false, true, true); break;
-        case 4: MSNAKE_SPACE(true, false, false); break;
-        case 5: MSNAKE_SPACE(true, false, true); break;
-        case 6: MSNAKE_SPACE(true, true, false); break;
-        case 7: MSNAKE_SPACE(true, true, true); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef MSNAKE_SPACE
-    return hipGetLastError();
+    return launch_by_flags<3>((snake_mask != 0u ? 4 : 0) | (safe ? 2 : 0) | (space ? 1 : 0), [&](auto act, auto sf, auto sp) {
+        hipLaunchKernelGGL((msnake_space_kernel<act.value, sf.value, sp.value>), grid, block, 0, stream, a);
+    });
 }
 
 }  // namespace msnake

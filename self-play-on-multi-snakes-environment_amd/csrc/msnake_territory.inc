@@ -109,20 +109,9 @@ hipError_t launch_territory(const StepParams& p, int rules, uint32_t snake_mask,
                             uint8_t* safe, uint16_t* territory, hipStream_t stream) {
     const TerritoryArgs a{state_view(p, rules), actions, safe, territory, action_stride, snake_mask};
     const dim3 grid((unsigned)((p.nenv + SPACE_WAVES - 1) / SPACE_WAVES)), block(SPACE_WAVES * 64);
-    const int which = (snake_mask != 0u ? 4 : 0) | (safe ? 2 : 0) | (territory ? 1 : 0);
-#define MSNAKE_TERRITORY(A, S, C) hipLaunchKernelGGL((msnake_territory_kernel<A, S, C>), grid, block, 0, stream, a)
-    switch (which) {
-        case 1: MSNAKE_TERRITORY(false, false, true); break;
-        case 2: MSNAKE_TERRITORY(false, true, false); break;
-        case 3: MSNAKE_TERRITORY(false, true, true); break;
-        case 4: MSNAKE_TERRITORY(true, false, false); break;
-        case 5: MSNAKE_TERRITORY(true, false, true); break;
-        case 6: MSNAKE_TERRITORY(true, true, false); break;
-        case 7: MSNAKE_TERRITORY(true, true, true); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef MSNAKE_TERRITORY
-    return hipGetLastError();
+    return launch_by_flags<3>((snake_mask != 0u ? 4 : 0) | (safe ? 2 : 0) | (territory ? 1 : 0), [&](auto act, auto sf, auto terr) {
+        hipLaunchKernelGGL((msnake_territory_kernel<act.value, sf.value, terr.value>), grid, block, 0, stream, a);
+    });
 }
 
 }  // namespace msnake

@@ -31,6 +31,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ._capi import SCRIPTED_POLICY_NAMES as SCRIPTED_POLICIES
 from .vec_env import check_radius, relative_to_absolute
 
 
@@ -375,9 +376,6 @@ class MonitorCSV:
 
 
 # ----------------------------------------------------------------------------- scripted opponents
-SCRIPTED_POLICIES = ("safe_greedy", "hamiltonian", "space_greedy", "territory_greedy")
-
-
 class ScriptedColumns:
     """The scripted action columns of a team of ScriptedOpponents of one env, in a buffer of its own: refresh() fills the
     columns of every member with ONE env call per policy, each member's step() then reads its own.  Whoever drives the

@@ -155,6 +155,11 @@ def relative_to_absolute(rel, heading):
     return torch.where(rel > 0, (rel - 1 + k) % 4 + 1, torch.zeros_like(rel))
 
 
+# the scripted policies that are an entry point of their own with a count output ([num_envs, n_snakes, 4] uint16):
+# name -> (the env's bound C function, its name, the keyword of the count output)
+COUNT_POLICIES = {_capi.SPACE_POLICY: ("_space_fn", "msnake_space_actions", "space_out"),
+                  _capi.TERRITORY_POLICY: ("_territory_fn", "msnake_territory_actions", "territory_out")}
+
 # constructor arguments that may differ between the two handles of a device-side copy (include/msnake.h,
 # msnake_copy_envs): what MultiSnakeVecEnv.clone() lets a caller override
 CLONE_OVERRIDES = ("record_policy", "envs_per_block", "obs_scale", "auto_reset", "max_steps", "seed", "env_id_base")
@@ -296,6 +301,7 @@ class MultiSnakeVecEnv:
         self._scripted_fn = self._L.msnake_scripted_actions
         self._scripted_out = None  # scripted_actions_device(out=None): allocated on first use
         self._space_fn = self._L.msnake_space_actions
+        self._territory_fn = self._L.msnake_territory_actions
         self._cells_fn = self._L.msnake_render_cells
         self._local_fn = self._L.msnake_render_local
 
@@ -303,17 +309,16 @@ class MultiSnakeVecEnv:
     def _stream(self):
         return ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _checked(self, t, name, dtype, want):
+        """The kernels write through raw pointers: a caller-supplied tensor must be exactly `dtype` and shape `want`,
+        contiguous, on this device.  Returns it."""
+        if (not isinstance(t, self._torch.Tensor) or t.dtype != dtype or t.device != self.device or
+                tuple(t.shape) != want or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {want} on {self.device}")
+        return t
+
     def _out(self, out):
-        """The kernel writes num_envs*H*W*C bytes through a raw pointer: a caller-supplied buffer must
-        be exactly that, on this device."""
-        if out is None:
-            return self._obs
-        torch = self._torch
-        want = (self.num_envs,) + self.obs_shape
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device or
-                tuple(out.shape) != want or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous uint8 tensor of shape {want} on {self.device}")
-        return out
+        return self._obs if out is None else self._checked(out, "out", self._torch.uint8, (self.num_envs,) + self.obs_shape)
 
     def _mask(self, mask):
         """mask -> contiguous uint8 [num_envs] tensor on this device (a tensor that already is one is used as it is)."""
@@ -326,13 +331,6 @@ class MultiSnakeVecEnv:
                 return mask
             return mask.to(device=self.device, dtype=torch.uint8).contiguous()
         return torch.from_numpy(normalize_mask(mask, self.num_envs)).to(self.device)
-
-    def _flags_out(self, out):
-        torch = self._torch
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device or
-                tuple(out.shape) != (self.num_envs,) or not out.is_contiguous()):
-            raise ValueError(f"truncated_out must be a contiguous uint8 tensor of shape ({self.num_envs},) on {self.device}")
-        return out
 
     def reset_device(self, mask=None, out=None, final_out=None, truncated_out=None):
         """mask=None: reset every env.  Otherwise reset only the envs `mask` selects (a bool / uint8 tensor or NumPy
@@ -347,7 +345,9 @@ class MultiSnakeVecEnv:
             return obs
         m = self._mask(mask)
         p_final = self._out(final_out).data_ptr() if final_out is not None else None
-        p_trunc = self._flags_out(truncated_out).data_ptr() if truncated_out is not None else None
+        p_trunc = None
+        if truncated_out is not None:
+            p_trunc = self._checked(truncated_out, "truncated_out", self._torch.uint8, (self.num_envs,)).data_ptr()
         _capi.check(self._reset_envs_fn(self._h, m.data_ptr(), obs.data_ptr(), p_final, p_trunc, self._stream()),
                     "msnake_reset_envs")
         return obs
@@ -378,30 +378,6 @@ class MultiSnakeVecEnv:
                 _capi.check(rc, "msnake_reset_envs")
         return obs, self._rew, self._done, self._info
 
-    def _safe_out(self, out):
-        torch = self._torch
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device or
-                tuple(out.shape) != (self.num_envs, self.n_snakes) or not out.is_contiguous()):
-            raise ValueError(f"safe_out must be a contiguous uint8 tensor of shape ({self.num_envs}, {self.n_snakes}) on "
-                             f"{self.device}")
-        return out
-
-    def _space_out(self, out):
-        torch = self._torch
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint16 or out.device != self.device or
-                tuple(out.shape) != (self.num_envs, self.n_snakes, 4) or not out.is_contiguous()):
-            raise ValueError(f"space_out must be a contiguous uint16 tensor of shape ({self.num_envs}, {self.n_snakes}, 4) on "
-                             f"{self.device}")
-        return out
-
-    def _territory_out(self, out):
-        torch = self._torch
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint16 or out.device != self.device or
-                tuple(out.shape) != (self.num_envs, self.n_snakes, 4) or not out.is_contiguous()):
-            raise ValueError(f"territory_out must be a contiguous uint16 tensor of shape ({self.num_envs}, {self.n_snakes}, 4) "
-                             f"on {self.device}")
-        return out
-
     def scripted_actions_device(self, policy, snakes=None, out=None, safe_out=None, space_out=None, territory_out=None):
         """Actions of a scripted policy ("safe_greedy", "hamiltonian", "space_greedy", "territory_greedy", or None for the mask alone) for the
         snakes in `snakes` (indices; default every snake), computed on the device from the env's current state.  They go to
@@ -417,13 +393,12 @@ class MultiSnakeVecEnv:
         the cells the snake reaches strictly before any other snake can; only with it, `territory_out`, a uint16
         [num_envs, n_snakes, 4] device tensor, gets those counts (see territory_device), returned like space_out."""
         torch = self._torch
-        space = policy == _capi.SPACE_POLICY
-        territory = policy == _capi.TERRITORY_POLICY
-        if space_out is not None and not space:
+        if space_out is not None and policy != _capi.SPACE_POLICY:
             raise ValueError(f"space_out is written by policy 'space_greedy' only, got policy {policy!r}")
-        if territory_out is not None and not territory:
+        if territory_out is not None and policy != _capi.TERRITORY_POLICY:
             raise ValueError(f"territory_out is written by policy 'territory_greedy' only, got policy {policy!r}")
-        if not space and not territory and policy not in _capi.SCRIPTED_POLICY:
+        count = COUNT_POLICIES.get(policy)
+        if count is None and policy not in _capi.SCRIPTED_POLICY:
             raise ValueError(f"policy must be 'safe_greedy', 'hamiltonian' or None, got {policy!r}")
         if snakes is None:
             bits = (1 << self.n_snakes) - 1
@@ -441,22 +416,20 @@ class MultiSnakeVecEnv:
         elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.device != self.device or out.dim() != 2 or
               out.shape[0] != self.num_envs or out.shape[1] < self.n_snakes or not out.is_contiguous()):
             raise ValueError(f"out must be a contiguous int32 tensor of shape ({self.num_envs}, >= {self.n_snakes}) on {self.device}")
-        p_safe = self._safe_out(safe_out).data_ptr() if safe_out is not None else None
-        if space:
-            p_space = self._space_out(space_out).data_ptr() if space_out is not None else None
-            rc = self._space_fn(self._h, bits, out.data_ptr(), int(out.shape[1]), p_safe, p_space,
-                                self._cur_stream(self.device).cuda_stream)
+        p_safe = None
+        if safe_out is not None:
+            p_safe = self._checked(safe_out, "safe_out", torch.uint8, (self.num_envs, self.n_snakes)).data_ptr()
+        if count is not None:
+            fn, c_name, kw = count
+            count_out = space_out if kw == "space_out" else territory_out
+            p_count = None
+            if count_out is not None:
+                p_count = self._checked(count_out, kw, torch.uint16, (self.num_envs, self.n_snakes, 4)).data_ptr()
+            rc = getattr(self, fn)(self._h, bits, out.data_ptr(), int(out.shape[1]), p_safe, p_count,
+                                   self._cur_stream(self.device).cuda_stream)
             if rc < 0:
-                _capi.check(rc, "msnake_space_actions")
-            res = (out,) + tuple(t for t in (safe_out, space_out) if t is not None)
-            return res[0] if len(res) == 1 else res
-        if territory:
-            p_terr = self._territory_out(territory_out).data_ptr() if territory_out is not None else None
-            rc = self._L.msnake_territory_actions(self._h, bits, out.data_ptr(), int(out.shape[1]), p_safe, p_terr,
-                                                  self._cur_stream(self.device).cuda_stream)
-            if rc < 0:
-                _capi.check(rc, "msnake_territory_actions")
-            res = (out,) + tuple(t for t in (safe_out, territory_out) if t is not None)
+                _capi.check(rc, c_name)
+            res = (out,) + tuple(t for t in (safe_out, count_out) if t is not None)
             return res[0] if len(res) == 1 else res
         rc = self._scripted_fn(self._h, _capi.SCRIPTED_POLICY[policy], bits, out.data_ptr(), int(out.shape[1]), p_safe,
                                self._cur_stream(self.device).cuda_stream)
@@ -470,22 +443,29 @@ class MultiSnakeVecEnv:
         if out is None:
             with self._torch.cuda.device(self.device):
                 out = self._torch.empty((self.num_envs, self.n_snakes), dtype=self._torch.uint8, device=self.device)
-        rc = self._scripted_fn(self._h, 0, 0, None, 0, self._safe_out(out).data_ptr(), self._cur_stream(self.device).cuda_stream)
+        self._checked(out, "safe_out", self._torch.uint8, (self.num_envs, self.n_snakes))
+        rc = self._scripted_fn(self._h, 0, 0, None, 0, out.data_ptr(), self._cur_stream(self.device).cuda_stream)
         if rc < 0:
             _capi.check(rc, "msnake_scripted_actions")
+        return out
+
+    def _counts_device(self, policy, out):
+        """The counts of a COUNT_POLICIES entry point alone: no action and no mask is written."""
+        fn, c_name, kw = COUNT_POLICIES[policy]
+        if out is None:
+            with self._torch.cuda.device(self.device):
+                out = self._torch.empty((self.num_envs, self.n_snakes, 4), dtype=self._torch.uint16, device=self.device)
+        self._checked(out, kw, self._torch.uint16, (self.num_envs, self.n_snakes, 4))
+        rc = getattr(self, fn)(self._h, 0, None, 0, None, out.data_ptr(), self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, c_name)
         return out
 
     def reachable_space_device(self, out=None):
         """uint16 [num_envs, n_snakes, 4]: entry m of a snake is the number of free cells 4-connected to the target of
         its move m + 1 through free cells, the target included; 0 when that move is not open (off the board or into a
         body) or the body is empty.  One flood fill per distinct region, on the device; nothing is synchronised."""
-        if out is None:
-            with self._torch.cuda.device(self.device):
-                out = self._torch.empty((self.num_envs, self.n_snakes, 4), dtype=self._torch.uint16, device=self.device)
-        rc = self._space_fn(self._h, 0, None, 0, None, self._space_out(out).data_ptr(), self._cur_stream(self.device).cuda_stream)
-        if rc < 0:
-            _capi.check(rc, "msnake_space_actions")
-        return out
+        return self._counts_device(_capi.SPACE_POLICY, out)
 
     def territory_device(self, out=None):
         """uint16 [num_envs, n_snakes, 4]: entry m of a snake is its Voronoi territory behind move m + 1: the number of
@@ -493,14 +473,7 @@ class MultiSnakeVecEnv:
         of its own open moves (bodies static, ties to the others); 0 when the move is not open, the body is empty, or
         another snake can enter the same target.  Equals reachable_space_device() when no other snake can move.  On the
         device; nothing is synchronised."""
-        if out is None:
-            with self._torch.cuda.device(self.device):
-                out = self._torch.empty((self.num_envs, self.n_snakes, 4), dtype=self._torch.uint16, device=self.device)
-        rc = self._L.msnake_territory_actions(self._h, 0, None, 0, None, self._territory_out(out).data_ptr(),
-                                              self._cur_stream(self.device).cuda_stream)
-        if rc < 0:
-            _capi.check(rc, "msnake_territory_actions")
-        return out
+        return self._counts_device(_capi.TERRITORY_POLICY, out)
 
     @property
     def cells_shape(self):
@@ -524,10 +497,7 @@ class MultiSnakeVecEnv:
             with torch.cuda.device(self.device):
                 snakes_out = torch.empty((self.num_envs, self.n_snakes, 8), dtype=torch.int32, device=self.device)
         elif snakes_out is not None:
-            want = (self.num_envs, self.n_snakes, 8)
-            if (not isinstance(snakes_out, torch.Tensor) or snakes_out.dtype != torch.int32 or snakes_out.device != self.device or
-                    tuple(snakes_out.shape) != want or not snakes_out.is_contiguous()):
-                raise ValueError(f"snakes_out must be a contiguous int32 tensor of shape {want} on {self.device}")
+            self._checked(snakes_out, "snakes_out", torch.int32, (self.num_envs, self.n_snakes, 8))
         want = (self.num_envs, len(sel), dim, dim)
         if not sel:
             if out is not None:
@@ -537,9 +507,8 @@ class MultiSnakeVecEnv:
         elif out is None:
             with torch.cuda.device(self.device):
                 out = torch.empty(want, dtype=torch.uint8, device=self.device)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device or
-              tuple(out.shape) != want or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous uint8 tensor of shape {want} on {self.device}")
+        else:
+            self._checked(out, "out", torch.uint8, want)
         rc = self._cells_fn(self._h, mask, out.data_ptr() if sel else None,
                             snakes_out.data_ptr() if snakes_out is not None else None, self._cur_stream(self.device).cuda_stream)
         if rc < 0:
@@ -576,17 +545,14 @@ class MultiSnakeVecEnv:
         if out is None:
             with torch.cuda.device(self.device):
                 out = torch.empty(want, dtype=torch.uint8, device=self.device)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device or
-              tuple(out.shape) != want or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous uint8 tensor of shape {want} on {self.device}")
+        else:
+            self._checked(out, "out", torch.uint8, want)
         want = (self.num_envs, len(sel))
         if heading_out is None and heading:
             with torch.cuda.device(self.device):
                 heading_out = torch.empty(want, dtype=torch.uint8, device=self.device)
         elif heading_out is not None:
-            if (not isinstance(heading_out, torch.Tensor) or heading_out.dtype != torch.uint8 or heading_out.device != self.device or
-                    tuple(heading_out.shape) != want or not heading_out.is_contiguous()):
-                raise ValueError(f"heading_out must be a contiguous uint8 tensor of shape {want} on {self.device}")
+            self._checked(heading_out, "heading_out", torch.uint8, want)
         rc = self._local_fn(self._h, radius, mask, oriented, out.data_ptr(),
                             heading_out.data_ptr() if heading_out is not None else None, self._cur_stream(self.device).cuda_stream)
         if rc < 0:

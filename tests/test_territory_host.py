@@ -304,13 +304,14 @@ class _FakeLib:
 
 
 def _bare_env(n=5, ns=3):
-    """A MultiSnakeVecEnv with only what the scripted calls touch, on the CPU (as test_space_host.py builds it: no
-    attribute for the new entry point, which is looked up in the library when the policy is asked for)."""
+    """A MultiSnakeVecEnv with only what the scripted calls touch, on the CPU (as test_space_host.py builds it, plus the
+    bound entry point of territory_greedy)."""
     env = object.__new__(msnake.MultiSnakeVecEnv)
     lib = _FakeLib()
     env._torch, env._L, env._h = torch, lib, 1234
     env.num_envs, env.n_snakes, env.device = n, ns, torch.device("cpu")
     env._scripted_fn, env._space_fn = lib.msnake_scripted_actions, lib.msnake_space_actions
+    env._territory_fn = lib.msnake_territory_actions
     env._scripted_out = torch.zeros((n, ns), dtype=torch.int32)
     env._cur_stream = lambda dev: type("S", (), {"cuda_stream": 77})()
     return env, lib

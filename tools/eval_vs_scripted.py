@@ -15,10 +15,11 @@ os.environ.setdefault("MIOPEN_FIND_MODE", "FAST")
 
 
 def main():
+    import msnake  # (no GPU is touched before an env is made)
     ap = argparse.ArgumentParser()
     ap.add_argument("--weights", default=None, help="weights file written by selfplay.save_weights")
     ap.add_argument("--random", action="store_true", help="a freshly initialised policy instead of --weights")
-    ap.add_argument("--opponent", choices=("safe_greedy", "hamiltonian", "space_greedy", "territory_greedy"), default="safe_greedy")
+    ap.add_argument("--opponent", choices=msnake._capi.SCRIPTED_POLICY_NAMES, default="safe_greedy")
     ap.add_argument("--eps", type=float, default=0.0, help="share of opponent actions replaced by a random one")
     ap.add_argument("--episodes", type=int, default=1000)
     ap.add_argument("--envs", type=int, default=1024)
@@ -32,7 +33,6 @@ def main():
     if (args.weights is None) == (not args.random):
         ap.error("give exactly one of --weights FILE and --random")
     import torch
-    import msnake
     from msnake import selfplay
 
     torch.manual_seed(args.seed)
