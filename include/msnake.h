@@ -42,6 +42,8 @@
  *                      step, the colour table: which of six things each cell shows, per view, plus the per-snake facts.
  *   msnake_render_local: no reference counterpart; the head-centred, heading-aligned window of those cell codes that
  *                      snake policies outside the reference are trained on, cut on the device.
+ *   msnake_render_rays: no reference counterpart; the eight-direction distance vector of snake agents (wall, fruit, own
+ *                      body, another snake), read off the same cell codes on the device.
  *   msnake_get_stats <- the epinfobuf aggregation in ppo_multi_agent.py:288,331,366-390
  *
  * RNG contract (shared with oracle/ and tests/golden): draw i of global env g is word (i & 3) of
@@ -406,6 +408,43 @@ int msnake_render_cells(msnake_handle h, uint32_t view_mask, uint8_t* cells_dev,
 #define MSNAKE_CELL_OUTSIDE 6 /* a window entry that lies outside the grid */
 int msnake_render_local(msnake_handle h, int32_t radius, uint32_t snake_mask, int32_t oriented, uint8_t* windows_dev,
                         uint8_t* heading_dev, void* stream);
+
+/* Eight-direction ray observations, one set per selected snake, computed on the device from the current state of every
+ * env: from the head, look along eight directions and report per direction how far the wall is and how far the first
+ * fruit, the first piece of the snake's own body and the first piece of another snake are.  32 bytes per snake: the
+ * classic vector observation of snake agents, the input of a policy without convolutions.
+ * Shapes: S = popcount(snake_mask).  rays_dev: uint8 [num_envs][S][MSNAKE_RAY_DIRS][MSNAKE_RAY_CHANNELS], the selected
+ * snakes in ascending order; it must be 4-byte aligned (MSNAKE_E_ALIGN otherwise): one (snake, direction) entry is
+ * exactly one dword.  heading_dev (may be NULL): uint8 [num_envs][S], no alignment; it receives exactly what
+ * msnake_render_local writes there, whatever `oriented` is.
+ * Directions: heading k of snake s and the unit steps f and g are those of msnake_render_local; with oriented == 0, k is
+ * taken as 0 for the rays, so f = (1,0) and g = (0,1).  Direction j for j = 0, 2, 4, 6 is f, g, -f, -g; for j = 1, 3, 5,
+ * 7 it is f + g, g - f, -f - g, f - g.  A diagonal step counts as one step.  Relative action r in 1..4 (see
+ * msnake_render_local) looks along direction 2 (r - 1).
+ * The walk: the ray of snake s in direction d visits head + t * d for t = 1, 2, ..., where head is piece 0.  Channel
+ * MSNAKE_RAY_WALL is the smallest t >= 1 whose cell lies outside [0, dim)^2: at least 1 and at most 63 (a head at -1
+ * looking across a board of 62).  The other three channels look only at the cells with t < wall, and there at the byte
+ * the plane of view s of msnake_render_cells holds: the same paint order (a later paint wins, a dead new_world snake
+ * paints nothing, duplicates are included, a fruit under a body is hidden).  MSNAKE_RAY_FRUIT is the smallest t with
+ * code 1, MSNAKE_RAY_OWN the smallest t with code 2 or 3, MSNAKE_RAY_OTHER the smallest t with code 4 or 5; each is 0
+ * when there is none.  Rays see through everything: the four channels are independent of each other.  The head's own
+ * cell (t = 0) is not looked at.  A snake with an empty body gets 32 zeros and heading 0.
+ * Identities: the oriented rays of a snake of heading k are its unoriented ones turned, rays_or[j] = rays_un[(j + 2 k)
+ * mod 8].  For dim <= 30 every entry can be read off the radius-31 window of msnake_render_local with the same
+ * `oriented`: walk from the centre [31][31] by (1,0), (1,1), (0,1), (-1,1), (-1,0), (-1,-1), (0,-1), (1,-1) for j = 0..7;
+ * the first MSNAKE_CELL_OUTSIDE on the walk is the wall.
+ * Like msnake_render_local the call only reads the handle's state (no random numbers are drawn, the Philox counter
+ * stays), allocates nothing, does not synchronise and adds nothing to env_steps; asynchronous on `stream`, and it can be
+ * captured into a HIP graph behind a step.  MSNAKE_E_ARG, before any device work: snake_mask 0 or with a bit >=
+ * n_snakes; oriented not 0 or 1; rays_dev NULL.  MSNAKE_E_HANDLE for a NULL handle. */
+#define MSNAKE_RAY_DIRS 8
+#define MSNAKE_RAY_CHANNELS 4
+#define MSNAKE_RAY_WALL 0
+#define MSNAKE_RAY_FRUIT 1
+#define MSNAKE_RAY_OWN 2
+#define MSNAKE_RAY_OTHER 3
+int msnake_render_rays(msnake_handle h, uint32_t snake_mask, int32_t oriented, uint8_t* rays_dev, uint8_t* heading_dev,
+                       void* stream);
 
 /* Copy the aggregate statistics to the host.  Blocking: waits for the device (every step issued so
  * far, on any stream) before it sums the per-env totals.  episodes / ep_len_sum / ep_return_sum /

@@ -85,6 +85,8 @@ PROTOTYPES = {
     "msnake_call_shape_for_config": (_int, [_cfg, _i32, _vp, _vp, _vp, _vp, ctypes.POINTER(_i32)]),
     # h, snake_mask, actions_dev, action_stride, safe_dev, territory_dev (uint16 [num_envs][n_snakes][4]), stream
     "msnake_territory_actions": (_int, [_vp, _u32, _vp, _i32, _vp, _vp, _vp]),
+    # h, snake_mask, oriented, rays_dev (uint8 [num_envs][S][8][4], 4-byte aligned), heading_dev (uint8 [num_envs][S] or NULL), stream
+    "msnake_render_rays": (_int, [_vp, _u32, _i32, _vp, _vp, _vp]),
 }
 SYMBOLS = list(PROTOTYPES)
 

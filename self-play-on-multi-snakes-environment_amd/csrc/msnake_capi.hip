@@ -123,6 +123,15 @@ int check_action_writer(const char* fn, int ns, bool writes_actions, uint32_t sn
     return MSNAKE_OK;
 }
 
+// the snake selection and the `oriented` flag of a per-snake observation (msnake_render_local, msnake_render_rays);
+// `what` names one snake's share of the output in the message
+int check_snake_view(const char* fn, const char* what, int ns, uint32_t snake_mask, int32_t oriented) {
+    if (!snake_mask) return fail(MSNAKE_E_ARG, "%s: snake_mask is 0 (no %s to write)", fn, what);
+    if (snake_mask >> ns) return fail(MSNAKE_E_ARG, "%s: snake_mask 0x%x has a bit >= n_snakes=%d", fn, snake_mask, ns);
+    if (oriented != 0 && oriented != 1) return fail(MSNAKE_E_ARG, "%s: oriented must be 0 or 1, got %d", fn, oriented);
+    return MSNAKE_OK;
+}
+
 int ensure_scratch(msnake_env* h, size_t bytes) {
     if (bytes <= h->scratch_bytes) return MSNAKE_OK;
     if (h->d_scratch) (void)hipFree(h->d_scratch);
@@ -552,16 +561,22 @@ int msnake_render_cells(msnake_handle h, uint32_t view_mask, uint8_t* cells_dev,
 int msnake_render_local(msnake_handle h, int32_t radius, uint32_t snake_mask, int32_t oriented, uint8_t* windows_dev,
                         uint8_t* heading_dev, void* stream) {
     if (int rc = check(h)) return rc;
-    const int ns = h->p.n_snakes;
     if (radius < 1 || radius > MSNAKE_LOCAL_MAX_RADIUS)
         return fail(MSNAKE_E_ARG, "msnake_render_local: radius %d must lie in [1, %d]", radius, MSNAKE_LOCAL_MAX_RADIUS);
-    if (!snake_mask) return fail(MSNAKE_E_ARG, "msnake_render_local: snake_mask is 0 (no window to write)");
-    if (snake_mask >> ns) return fail(MSNAKE_E_ARG, "msnake_render_local: snake_mask 0x%x has a bit >= n_snakes=%d", snake_mask, ns);
-    if (oriented != 0 && oriented != 1) return fail(MSNAKE_E_ARG, "msnake_render_local: oriented must be 0 or 1, got %d", oriented);
+    if (int rc = check_snake_view("msnake_render_local", "window", h->p.n_snakes, snake_mask, oriented)) return rc;
     if (!windows_dev) return fail(MSNAKE_E_ARG, "msnake_render_local: windows_dev is NULL");
     DeviceGuard guard(h->cfg.device);
     return launched(msnake::launch_local(h->p, h->cfg.rules, radius, snake_mask, oriented, windows_dev, heading_dev,
                                          static_cast<hipStream_t>(stream)));
+}
+
+int msnake_render_rays(msnake_handle h, uint32_t snake_mask, int32_t oriented, uint8_t* rays_dev, uint8_t* heading_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    if (int rc = check_snake_view("msnake_render_rays", "rays", h->p.n_snakes, snake_mask, oriented)) return rc;
+    if (!rays_dev) return fail(MSNAKE_E_ARG, "msnake_render_rays: rays_dev is NULL");
+    if ((uintptr_t)rays_dev & 3) return fail(MSNAKE_E_ALIGN, "rays_dev must be 4-byte aligned");
+    DeviceGuard guard(h->cfg.device);
+    return launched(msnake::launch_rays(h->p, h->cfg.rules, snake_mask, oriented, rays_dev, heading_dev, static_cast<hipStream_t>(stream)));
 }
 
 // ---- canonical state import / export.  The device packs / unpacks (msnake_state_*_kernel); the host

@@ -223,6 +223,9 @@ hipError_t launch_cells(const StepParams& p, int rules, uint32_t view_mask, uint
 // head-centred cell-code windows of the snakes in snake_mask (msnake_local.inc); heading NULL = not written
 hipError_t launch_local(const StepParams& p, int rules, int radius, uint32_t snake_mask, int oriented, uint8_t* windows,
                         uint8_t* heading, hipStream_t stream);
+// eight-direction ray observations of the snakes in snake_mask (msnake_rays.inc); rays 4-byte aligned, heading NULL = not written
+hipError_t launch_rays(const StepParams& p, int rules, uint32_t snake_mask, int oriented, uint8_t* rays, uint8_t* heading,
+                       hipStream_t stream);
 // the DIM of the compile-time-shape instantiation that fits the configuration in `p` in every folded field, or 0 (host only)
 int spec_dim_of(const StepParams& p, int rules);
 // which kernel one launch gets: MSNAKE_CALL_GENERIC / _SHAPE / _PLAIN of include/msnake.h (host only, no HIP call)

@@ -5,7 +5,8 @@
 // One wavefront per env; the wave only READS the handle's state, through EnvReader (msnake_envread.inc).
 //   * Board: ONE plane of dim^2 bytes in the wave's own slice of dynamic LDS (4 waves x dim^2 bytes in whole dwords: 1.4 KB
 //     per workgroup at 19x19, 15.0 KB at 62x62, whatever the radius and the selection), with snake-indexed codes:
-//     0 empty, 1 fruit, 2 + 2 i body of snake i, 3 + 2 i head of snake i.  Painted in the phases of msnake_cells_kernel
+//     0 empty, 1 fruit, 2 + 2 i body of snake i, 3 + 2 i head of snake i.  Painted by paint_snake_board (which
+//     msnake_rays_kernel of msnake_rays.inc calls too) in the phases of msnake_cells_kernel
 //     -- the fruits, then per snake its body cells, then its head -- as byte stores; all stores of a phase that meet in
 //     a byte carry the same value, DS operations of one wave execute in program order, so a later phase wins and
 //     wave_sync() (a compiler fence) between the phases is all the ordering this needs.  No workgroup barrier.  The last
@@ -35,19 +36,17 @@ struct LocalArgs {
 
 constexpr int LOCAL_WAVES = 4;  // waves (envs) per workgroup
 
-__global__ __launch_bounds__(LOCAL_WAVES * 64) void msnake_local_kernel(LocalArgs a) {
-    extern __shared__ uint32_t local_lds[];  // LOCAL_WAVES slices of a.slice_words dwords
-    const int lane = (int)(threadIdx.x & 63u);
-    const int wave = (int)uni(threadIdx.x >> 6);
-    const int e = (int)uni(blockIdx.x * LOCAL_WAVES + (threadIdx.x >> 6));
-    if (e >= a.v.nenv) return;  // (no workgroup barrier below)
-    const int dim = a.v.dim;
-    const bool nw = a.v.rules == MSNAKE_RULES_NEW_WORLD;
-    const EnvReader rd(a.v, e, lane);
+// The snake-indexed board of the env `rd` reads, painted into the wave's slice board32[0 .. slice_words) of LDS; every
+// lane of the wave calls it.  Shared by msnake_local_kernel and msnake_rays_kernel (msnake_rays.inc).  par[s] <- what the
+// callers need of snake s: head c0 + 2 in bits 0..9, head c1 + 2 in bits 10..19, the heading in 20..21, bit 22 = the body
+// is not empty (0 for an empty body and for s >= n_snakes).
+__device__ __forceinline__ void paint_snake_board(const StateView& v, const EnvReader& rd, int lane, uint32_t* board32,
+                                                  int slice_words, uint32_t (&par)[MSNAKE_MAX_SNAKES]) {
+    const int dim = v.dim;
+    const bool nw = v.rules == MSNAKE_RULES_NEW_WORLD;
     const uint32_t flags = rd.flags();
-    uint32_t* board32 = local_lds + wave * a.slice_words;
     uint8_t* board = reinterpret_cast<uint8_t*>(board32);
-    for (int i = lane; i < a.slice_words; i += 64) board32[i] = 0u;
+    for (int i = lane; i < slice_words; i += 64) board32[i] = 0u;
     wave_sync();
 
     // a cell inside the grid takes the phase's code; anything else is not stored
@@ -60,14 +59,11 @@ __global__ __launch_bounds__(LOCAL_WAVES * 64) void msnake_local_kernel(LocalArg
     rd.for_each_fruit([&](int, uint32_t c, bool valid) { paint(c, valid, 1u); });
     wave_sync();
 
-    // ---- per snake: its body cells (duplicates and piece 0 included), then piece 0 as the head.  par[s]: what the gather
-    // needs of snake s: head c0 + 2 in bits 0..9, head c1 + 2 in bits 10..19, the heading in 20..21, bit 22 = the body is
-    // not empty
-    uint32_t par[MSNAKE_MAX_SNAKES];
+    // ---- per snake: its body cells (duplicates and piece 0 included), then piece 0 as the head
 #pragma unroll
     for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
         par[s] = 0u;
-        if (s >= a.v.ns) continue;
+        if (s >= v.ns) continue;
         const SnakeRef sn = rd.snake(s);
         if (sn.len == 0) continue;  // an empty body: nothing painted, a window of zeros, heading 0
         const uint32_t vel = (rd.word(SN_C(s)) >> 16) & 7u;  // 0 = at rest, 1..4 = the move that keeps the direction
@@ -78,6 +74,20 @@ __global__ __launch_bounds__(LOCAL_WAVES * 64) void msnake_local_kernel(LocalArg
         paint(sn.head, lane == 0, 3u + 2u * s);
         wave_sync();
     }
+}
+
+__global__ __launch_bounds__(LOCAL_WAVES * 64) void msnake_local_kernel(LocalArgs a) {
+    extern __shared__ uint32_t local_lds[];  // LOCAL_WAVES slices of a.slice_words dwords
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = (int)uni(threadIdx.x >> 6);
+    const int e = (int)uni(blockIdx.x * LOCAL_WAVES + (threadIdx.x >> 6));
+    if (e >= a.v.nenv) return;  // (no workgroup barrier below)
+    const int dim = a.v.dim;
+    const EnvReader rd(a.v, e, lane);
+    uint32_t* board32 = local_lds + wave * a.slice_words;
+    const uint8_t* board = reinterpret_cast<const uint8_t*>(board32);
+    uint32_t par[MSNAKE_MAX_SNAKES];
+    paint_snake_board(a.v, rd, lane, board32, a.slice_words, par);
 
     // ---- heading: lane q <-> the q-th selected snake
     const auto slot_par = [&](int q, int& snake) {

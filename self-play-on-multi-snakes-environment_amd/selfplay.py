@@ -130,22 +130,73 @@ class WindowPolicy(CnnPolicy):
         return logits.float(), v.float()
 
 
+class RayPolicy(nn.Module):
+    """An MLP over one snake's eight-direction rays (MultiSnakeVecEnv.render_rays_device): the input is uint8 [B, 8, 4],
+    steps to the wall, the first fruit, the first piece of the own body and the first piece of another snake per
+    direction.  Features are 1 / d where d > 0, else 0 (near things are large, absent things vanish), flattened to 32;
+    two hidden layers of 64, five logits and a value, initialised like CnnPolicy's layers and heads.  No convolution.
+    It has CnnPolicy's step / value surface; under oriented rays its actions are relative to the heading
+    (relative_to_absolute), and one set of weights can play any column of the action buffer.  The orientation flag the
+    weights were trained under travels with them as the buffer `ray_input` (load_weights refuses another kind)."""
+
+    N_IN = 8 * 4
+    HIDDEN = 64
+
+    def __init__(self, n_actions=5, amp_dtype=None, oriented=True):
+        super().__init__()
+        self.amp_dtype, self.oriented = amp_dtype, bool(oriented)
+        g = float(np.sqrt(2))
+        self.fc1 = _ortho(nn.Linear(self.N_IN, self.HIDDEN), g)
+        self.fc2 = _ortho(nn.Linear(self.HIDDEN, self.HIDDEN), g)
+        self.pi = _ortho(nn.Linear(self.HIDDEN, n_actions), 0.01)
+        self.v = _ortho(nn.Linear(self.HIDDEN, 1), 1.0)
+        self.register_buffer("ray_input", torch.tensor([int(self.oriented)], dtype=torch.int64))
+
+    @staticmethod
+    def features(rays_u8):
+        """uint8 [B, 8, 4] -> float32 [B, 32]: 1 / d where d > 0, else 0."""
+        d = rays_u8.flatten(1).float()
+        return torch.where(d > 0, 1.0 / d.clamp(min=1.0), torch.zeros_like(d))
+
+    def forward(self, rays_u8):
+        """rays_u8: uint8 [B, 8, 4] -> logits [B, A], value [B]."""
+        if rays_u8.dim() != 3 or tuple(rays_u8.shape[1:]) != (8, 4) or rays_u8.dtype != torch.uint8:
+            raise ValueError(f"expected uint8 rays of shape [B, 8, 4], got {rays_u8.dtype} {tuple(rays_u8.shape)}")
+        with torch.autocast(rays_u8.device.type, dtype=self.amp_dtype or torch.bfloat16, enabled=self.amp_dtype is not None):
+            x = F.relu(self.fc2(F.relu(self.fc1(self.features(rays_u8)))))
+            logits, v = self.pi(x), self.v(x)[:, 0]
+        return logits.float(), v.float()
+
+    step, value = CnnPolicy.step, CnnPolicy.value
+
+
 def window_kind(state_dict):
-    """What a weights file was trained on: None for full frames, (radius, oriented) for windows."""
+    """What a weights file was trained on, as far as windows go: None for anything else, (radius, oriented) for windows."""
     t = state_dict.get("local_window")
     return None if t is None else (int(t[0]), bool(int(t[1])))
 
 
+def ray_kind(state_dict):
+    """Likewise for rays: None for anything else, (oriented,) for rays."""
+    t = state_dict.get("ray_input")
+    return None if t is None else (bool(int(t[0])),)
+
+
 def _kind_text(kind):
-    return "full frames" if kind is None else f"windows of radius {kind[0]}, {'oriented' if kind[1] else 'not oriented'}"
+    """kind: None for full frames, (radius, oriented) for windows, (oriented,) for rays."""
+    if kind is None:
+        return "full frames"
+    what = f"windows of radius {kind[0]}" if len(kind) == 2 else "rays"
+    return f"{what}, {'oriented' if kind[-1] else 'not oriented'}"
 
 
 def check_kind(model, state_dict, path):
-    want = (model.radius, model.oriented) if isinstance(model, WindowPolicy) else None
-    got = window_kind(state_dict)
+    want = ((model.radius, model.oriented) if isinstance(model, WindowPolicy) else
+            (model.oriented,) if isinstance(model, RayPolicy) else None)
+    got = window_kind(state_dict) or ray_kind(state_dict)
     if got != want:
         raise RuntimeError(f"{path} holds a policy trained on {_kind_text(got)}; this run trains on {_kind_text(want)} "
-                           "(local_radius / oriented): the weights cannot be loaded")
+                           "(local_radius / rays / oriented): the weights cannot be loaded")
 
 
 def neglogp(logits, actions):
@@ -448,16 +499,19 @@ def refresh_scripted(opponents):
 class Runner:
     """ppo_multi_agent.py:145-216 with everything on the device."""
 
-    def __init__(self, env, model, opponents, nsteps, gamma, lam, local_radius=None, oriented=True):
+    def __init__(self, env, model, opponents, nsteps, gamma, lam, local_radius=None, oriented=True, rays=False):
+        if rays and local_radius is not None:
+            raise ValueError("rays=True and local_radius are mutually exclusive: a run trains on rays or on windows")
         self.env, self.model, self.opponents = env, model, opponents
         self.nsteps, self.gamma, self.lam = nsteps, gamma, lam
-        self.local_radius, self.oriented = local_radius, bool(oriented)
+        self.local_radius, self.oriented, self.rays = local_radius, bool(oriented), bool(rays)
+        self.per_snake = self.rays or local_radius is not None   # windows or rays instead of the frame
         self.obs = env.reset_device()
-        if local_radius is not None:
-            # the learner and every network opponent see their own snake's window: one env call for all of them
+        if self.per_snake:
+            # the learner and every network opponent see their own snake's window / rays: one env call for all of them
             self.win_snakes = [0] + [i + 1 for i, opp in enumerate(opponents) if isinstance(opp, nn.Module)]
             self.slot = {s: q for q, s in enumerate(self.win_snakes)}
-            shape = (env.num_envs,) + env.local_shape(local_radius, self.win_snakes)
+            shape = (env.num_envs,) + (env.rays_shape(self.win_snakes) if self.rays else env.local_shape(local_radius, self.win_snakes))
             self.win = torch.empty(shape, dtype=torch.uint8, device=self.obs.device)
             self.heading = torch.empty(shape[:2], dtype=torch.uint8, device=self.obs.device)
             self.observe_local()
@@ -465,14 +519,17 @@ class Runner:
         self.tstart = time.time()
 
     def observe_local(self):
-        self.env.render_local_device(self.local_radius, snakes=self.win_snakes, oriented=self.oriented, out=self.win,
-                                     heading_out=self.heading)
+        if self.rays:
+            self.env.render_rays_device(snakes=self.win_snakes, oriented=self.oriented, out=self.win, heading_out=self.heading)
+        else:
+            self.env.render_local_device(self.local_radius, snakes=self.win_snakes, oriented=self.oriented, out=self.win,
+                                         heading_out=self.heading)
 
     def learner_obs(self):
-        return self.obs[..., 0:3] if self.local_radius is None else self.win[:, 0]
+        return self.win[:, 0] if self.per_snake else self.obs[..., 0:3]
 
     def absolute(self, a, snake):
-        """A window policy's sampled action as the step takes it: relative to the heading under oriented windows."""
+        """A window / ray policy's sampled action as the step takes it: relative to the heading under `oriented`."""
         return relative_to_absolute(a, self.heading[:, self.slot[snake]]) if self.oriented else a
 
     def multi_step_local(self):
@@ -489,7 +546,7 @@ class Runner:
         return a, v, nlp, torch.stack(acts, dim=1).to(torch.int32)
 
     def multi_step(self):
-        if self.local_radius is not None:
+        if self.per_snake:
             return self.multi_step_local()
         a, v, nlp = self.model.step(self.obs[..., 0:3])
         acts = [a]
@@ -514,7 +571,7 @@ class Runner:
             mb_obs[t] = self.learner_obs()
             mb_act[t], mb_val[t], mb_nlp[t], mb_done[t] = a, v, nlp, self.dones
             self.obs, rew, done, info = self.env.step_device(full)
-            if self.local_radius is not None:
+            if self.per_snake:
                 self.observe_local()
             mb_rew[t] = rew
             self.dones = done.float()
@@ -536,7 +593,7 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
           cliprange=lambda f: f * 0.1, opponent_save_interval=50, max_saved_opponents=1000, csv_path=None,
           monitor_path=None, seed=0, log_fn=print, amp_dtype=None, json_path=None, tb_dir=None,
           save_dir=None, save_interval=0, load_path=None, resume=False, scripted_opponents=None, local_radius=None,
-          oriented=True):
+          oriented=True, rays=False):
     """ppo_multi_agent.py:231-404 (hyper-parameters of test/ppo1_single_test.py:42-47 as defaults).
 
     Checkpoints (ppo_multi_agent.py:112-133, 296-306, 349-364, 392-404), weights only, under `save_dir`
@@ -552,12 +609,19 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
     `local_radius`: the learner and its network opponents are WindowPolicies over their own snake's head-centred window
     of that radius (render_local_device) instead of CnnPolicies over the frame; under `oriented` the windows are turned
     along the heading and the sampled actions are relative to it (relative_to_absolute).  Weights and trainer states
-    carry the radius and the flag: loading the other kind is refused."""
+    carry the radius and the flag: loading the other kind is refused.
+    `rays=True`: the learner and its network opponents are RayPolicies over their own snake's eight-direction rays
+    (render_rays_device, one env call per step for all of them), an MLP on 32 bytes per snake; `oriented` means the same
+    as for windows.  Mutually exclusive with `local_radius`; weights and trainer states carry the kind here too."""
+    if rays and local_radius is not None:
+        raise ValueError("rays=True and local_radius are mutually exclusive: a run trains on rays or on windows")
     torch.manual_seed(seed); random.seed(seed)
     dev = env.device
     n_snakes = env.n_snakes
     H, W, _ = env.obs_shape
-    if local_radius is None:
+    if rays:
+        make_policy = lambda: RayPolicy(amp_dtype=amp_dtype, oriented=oriented).to(dev)
+    elif local_radius is None:
         make_policy = lambda: CnnPolicy((H, W, 3), amp_dtype=amp_dtype).to(dev)
     else:
         make_policy = lambda: WindowPolicy(local_radius, amp_dtype=amp_dtype, oriented=oriented).to(dev)
@@ -611,7 +675,7 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
             pool.save(model)
         if save_dir:  # from the first pool file on there is a state a resume can start from
             save_trainer_state(0)
-    runner = Runner(env, model, opponents, nsteps, gamma, lam, local_radius=local_radius, oriented=oriented)
+    runner = Runner(env, model, opponents, nsteps, gamma, lam, local_radius=local_radius, oriented=oriented, rays=rays)
     nbatch = env.num_envs * nsteps
     nbatch_train = nbatch // nminibatches
     assert nbatch % nminibatches == 0

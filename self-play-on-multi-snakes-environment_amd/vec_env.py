@@ -112,6 +112,8 @@ def normalize_views(views, n_views):
 
 LOCAL_MAX_RADIUS = 31  # MSNAKE_LOCAL_MAX_RADIUS
 CELL_OUTSIDE = 6       # MSNAKE_CELL_OUTSIDE: a window entry of render_local_device() that lies outside the grid
+RAY_DIRS, RAY_CHANNELS = 8, 4                          # MSNAKE_RAY_DIRS, MSNAKE_RAY_CHANNELS: render_rays_device()
+RAY_WALL, RAY_FRUIT, RAY_OWN, RAY_OTHER = 0, 1, 2, 3   # MSNAKE_RAY_*: the channels
 
 
 def normalize_snakes(snakes, n_snakes):
@@ -304,6 +306,7 @@ class MultiSnakeVecEnv:
         self._territory_fn = self._L.msnake_territory_actions
         self._cells_fn = self._L.msnake_render_cells
         self._local_fn = self._L.msnake_render_local
+        self._rays_fn = self._L.msnake_render_rays
 
     # ------------------------------------------------------------------ device-side API
     def _stream(self):
@@ -557,6 +560,47 @@ class MultiSnakeVecEnv:
                             heading_out.data_ptr() if heading_out is not None else None, self._cur_stream(self.device).cuda_stream)
         if rc < 0:
             _capi.check(rc, "msnake_render_local")
+        return out if heading_out is None else (out, heading_out)
+
+    def rays_shape(self, snakes=None):
+        """(S, 8, 4): one env's rays of render_rays_device(snakes)."""
+        return (len(normalize_snakes(snakes, self.n_snakes)[1]), RAY_DIRS, RAY_CHANNELS)
+
+    def render_rays_device(self, snakes=None, oriented=True, out=None, heading_out=None, heading=False):
+        """Eight-direction ray observations (msnake_render_rays): uint8 [num_envs, S, 8, 4], one set per selected snake in
+        ascending snake order.  Entry [j, c] of snake s looks from the head along direction j -- f, f + g, g, g - f, -f,
+        -f - g, -g, f - g with f and g as in render_local_device(), a diagonal step counting as one -- and gives in
+        channel c = 0 the number of steps to the first cell outside the grid (1..63) and in c = 1, 2, 3 the steps to the
+        first fruit, the first piece of the snake's own body and the first piece of another snake in front of that wall,
+        0 when there is none; the cells are read in the codes of view s of render_cells_device().  oriented: direction 0
+        is the snake's direction of travel, and relative action r looks along direction 2 (r - 1); otherwise f = (1, 0),
+        g = (0, 1).  `snakes`: None = every snake, an int, or a strictly ascending sequence.  `heading_out`, a uint8
+        [num_envs, S] device tensor (heading=True: a fresh one), gets every selected snake's heading 0..3
+        (relative_to_absolute() takes it).  `out` must be a contiguous uint8 tensor of the shape above on this device
+        whose storage starts at a multiple of 4 bytes.  Returns the rays, or (rays, heading) when the heading was asked
+        for; nothing is synchronised.  Draws no random numbers and changes no env state."""
+        torch = self._torch
+        mask, sel = normalize_snakes(snakes, self.n_snakes)
+        if isinstance(oriented, (int, np.integer)) and oriented in (0, 1):
+            oriented = int(oriented)
+        else:
+            raise ValueError(f"oriented must be True or False, got {oriented!r}")
+        want = (self.num_envs, len(sel), RAY_DIRS, RAY_CHANNELS)
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.empty(want, dtype=torch.uint8, device=self.device)
+        elif self._checked(out, "out", torch.uint8, want).data_ptr() % 4:
+            raise ValueError("out must start at a multiple of 4 bytes (one direction's four channels are stored as one dword)")
+        want = (self.num_envs, len(sel))
+        if heading_out is None and heading:
+            with torch.cuda.device(self.device):
+                heading_out = torch.empty(want, dtype=torch.uint8, device=self.device)
+        elif heading_out is not None:
+            self._checked(heading_out, "heading_out", torch.uint8, want)
+        rc = self._rays_fn(self._h, mask, oriented, out.data_ptr(), heading_out.data_ptr() if heading_out is not None else None,
+                           self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_render_rays")
         return out if heading_out is None else (out, heading_out)
 
     def rollout_device(self, tape, persistent=True, keep_obs=True):

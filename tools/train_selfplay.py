@@ -33,10 +33,14 @@ def main():
     ap.add_argument("--local-radius", type=int, default=None, metavar="R",
                     help="train window policies on each snake's head-centred (2R+1)x(2R+1) cell-code window instead of the frame")
     ap.add_argument("--no-orient", action="store_true",
-                    help="with --local-radius: windows in board orientation and absolute actions (default: turned along the heading)")
+                    help="with --local-radius / --rays: windows / rays in board orientation and absolute actions (default: turned along the heading)")
+    ap.add_argument("--rays", action="store_true",
+                    help="train ray policies (an MLP) on each snake's eight-direction rays, 32 bytes per snake, instead of the frame")
     args = ap.parse_args()
-    if args.no_orient and args.local_radius is None:
-        ap.error("--no-orient needs --local-radius")
+    if args.rays and args.local_radius is not None:
+        ap.error("--rays and --local-radius are mutually exclusive")
+    if args.no_orient and args.local_radius is None and not args.rays:
+        ap.error("--no-orient needs --local-radius or --rays")
     import torch
     from msnake import selfplay
 
@@ -45,7 +49,7 @@ def main():
     selfplay.learn(env, nsteps=args.nsteps, total_timesteps=args.timesteps, csv_path=args.csv,
                    monitor_path=args.monitor, json_path=args.json, tb_dir=args.tensorboard,
                    amp_dtype=torch.bfloat16 if args.bf16 else None, save_dir=args.save, save_interval=args.save_interval,
-                   load_path=args.load, resume=args.resume, local_radius=args.local_radius, oriented=not args.no_orient,
+                   load_path=args.load, resume=args.resume, local_radius=args.local_radius, oriented=not args.no_orient, rays=args.rays,
                    scripted_opponents=None if args.opponent == "pool" else {s: args.opponent for s in range(1, args.snakes)})
     print(env.stats())
     env.close()
