@@ -35,6 +35,8 @@
  *   msnake_space_actions / msnake_territory_actions: no reference counterpart either; opponents that look ahead -- how
  *                      much room a move leads into, and how much of it the snake reaches before any other snake can
  *                      (Voronoi territory) -- with the counts as per-move features.
+ *   msnake_path_actions: no reference counterpart either; the BFS distance to the nearest fruit around the bodies, per
+ *                      move and as a whole field, and the opponent that forages by it.
  *   msnake_copy_envs <- no reference counterpart (a reference env can only be re-created and replayed); the analogue is
  *                      ALE's cloneState / restoreState, batched and on the device: snapshot, fork and restore of envs
  *                      between two handles without the host round trip of msnake_get_state / msnake_set_state.
@@ -324,6 +326,37 @@ int msnake_space_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_
  * action_stride < n_snakes when snake_mask != 0; nothing to write (snake_mask 0, safe_dev and territory_dev NULL). */
 int msnake_territory_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride,
                              uint8_t* safe_dev, uint16_t* territory_dev, void* stream);
+
+/* Shortest-path distances to the fruits, the whole distance field, and the opponent path_greedy, in the terms of the
+ * three calls above (`used`, moves 1..4, free, open).  Bodies are static: tails do not recede, and neither the velocity
+ * nor the alive bit plays a part.
+ * Sources: the entries of the state's fruit list (adversarial: the complete list) that lie in [0,dim)^2 and are free.  An
+ * entry at -1 or dim is no source, neither is a fruit under a body (or under a head at reset); duplicates count once.
+ * The field F(c): for a free cell c, the length of the shortest 4-connected path through free cells from c to a
+ * source, 0 on a source; MSNAKE_PATH_NONE for a cell in `used`, for a free cell whose region holds no source, and
+ * everywhere when there is no source.  A finite value is at most dim^2 - 2.
+ * field_dev (may be NULL): uint16 [num_envs][dim][dim], entry [c0][c1] = F((c0, c1)), the indexing of the
+ * msnake_render_cells planes.  2-byte aligned (MSNAKE_E_ALIGN otherwise).
+ * path_dev (may be NULL): uint16 [num_envs][n_snakes][4], written for every snake whatever snake_mask is: entry m =
+ * F(target of move m + 1) when that move is open, MSNAKE_PATH_NONE when it is not or the body is empty.  0 means the
+ * move eats; 1 + the minimum over m is the snake's own distance (its head lies in `used`, so the field holds NONE
+ * there).  2-byte aligned (MSNAKE_E_ALIGN otherwise).
+ * safe_dev (may be NULL): exactly what the three calls above write there.
+ * actions_dev: int32 [num_envs][action_stride]; entry s of every row is written for each s with bit s of
+ * snake_mask set, all other entries are left untouched.  The policy path_greedy: the action is 0 if the body is empty
+ * or no move is open; otherwise the eligible moves are exactly space_greedy's (with space as msnake_space_actions
+ * defines it, need = min(len, max over the open moves of space), eligible = open and space >= need), and the action is
+ * the eligible move with the smallest path entry, the first in the order 1, 2, 3, 4 on a tie.  If every eligible
+ * move's entry is MSNAKE_PATH_NONE the action is space_greedy's own, so path_greedy equals space_greedy wherever no
+ * source can be reached.
+ * Like its siblings the call only reads the handle's state, draws no random numbers, allocates nothing, does not
+ * synchronise and adds nothing to env_steps; asynchronous on `stream`, and it can be captured into a HIP graph in
+ * front of the step.  MSNAKE_E_ARG, before any device work: a snake_mask bit >= n_snakes; actions_dev NULL or
+ * action_stride < n_snakes when snake_mask != 0; nothing to write (snake_mask 0, safe_dev, path_dev and field_dev
+ * NULL). */
+#define MSNAKE_PATH_NONE 0xFFFFu
+int msnake_path_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride,
+                        uint8_t* safe_dev, uint16_t* path_dev, uint16_t* field_dev, void* stream);
 
 /* Copy env state from `src` into `dst` on the device: destination env e receives the state of source env
  * src_index_dev[e] (int32 [dst.num_envs], a device pointer).  A negative entry leaves destination env e completely

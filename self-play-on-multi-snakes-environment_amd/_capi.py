@@ -30,7 +30,9 @@ STORE_POLICY = {"auto": 0, "plain": 1, "stream": 2}
 SCRIPTED_POLICY = {None: 0, "safe_greedy": 1, "hamiltonian": 2}  # MSNAKE_POLICY_*
 SPACE_POLICY = "space_greedy"  # no policy id: an entry point of its own (msnake_space_actions)
 TERRITORY_POLICY = "territory_greedy"  # likewise (msnake_territory_actions)
-SCRIPTED_POLICY_NAMES = ("safe_greedy", "hamiltonian", SPACE_POLICY, TERRITORY_POLICY)  # every scripted opponent there is
+PATH_POLICY = "path_greedy"  # likewise (msnake_path_actions)
+SCRIPTED_POLICY_NAMES = ("safe_greedy", "hamiltonian", SPACE_POLICY, TERRITORY_POLICY)  # the opponents selfplay.SCRIPTED_POLICIES names
+SCRIPTED_OPPONENT_NAMES = SCRIPTED_POLICY_NAMES + (PATH_POLICY,)  # every scripted opponent there is
 
 
 class MsnakeBlobInfo(ctypes.Structure):
@@ -87,6 +89,9 @@ PROTOTYPES = {
     "msnake_territory_actions": (_int, [_vp, _u32, _vp, _i32, _vp, _vp, _vp]),
     # h, snake_mask, oriented, rays_dev (uint8 [num_envs][S][8][4], 4-byte aligned), heading_dev (uint8 [num_envs][S] or NULL), stream
     "msnake_render_rays": (_int, [_vp, _u32, _i32, _vp, _vp, _vp]),
+    # h, snake_mask, actions_dev, action_stride, safe_dev, path_dev (uint16 [num_envs][n_snakes][4]),
+    # field_dev (uint16 [num_envs][dim][dim]), stream
+    "msnake_path_actions": (_int, [_vp, _u32, _vp, _i32, _vp, _vp, _vp, _vp]),
 }
 SYMBOLS = list(PROTOTYPES)
 

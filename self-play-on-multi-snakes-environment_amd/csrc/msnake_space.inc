@@ -24,8 +24,10 @@
 //     open && space >= need, then safe_greedy's choice among the eligible moves (min over (fruit, move) pairs of
 //     distance << 3 | move, fruits lane-distributed).
 //   * lane s stores snake s's action word and mask byte, lane 4 s + m the count of move m + 1.
-// The occupancy build with the candidates (read_board) and the choice by count (greedy_by_count) are functions of their
-// own: msnake_territory.inc, included behind this file, races on the same board and chooses in the same way.
+// The occupancy build with the candidates (read_board), the fills (region_sizes) and the choice by count (greedy_by_count
+// = eligible_moves, then greedy_among) are functions of their own: msnake_territory.inc, included behind this file, races
+// on the same board and chooses in the same way, and msnake_path.inc takes the eligible moves from here and chooses among
+// them by its own distance.
 // No random numbers, no global atomics, no workgroup barrier, no scratch.
 namespace msnake {
 
@@ -118,20 +120,54 @@ __device__ __forceinline__ Board read_board(const StateView& v, const EnvReader&
     return b;
 }
 
-// The choice space_greedy and territory_greedy share.  `count`: lane 4 s + m holds the count of move m + 1 of snake s
-// (0 where the move is not open).  need = min(len, max over the open moves of count) by two quad-permute DPP steps,
-// eligible = open && count >= need, then safe_greedy's choice among the eligible moves.  act[s] is set for every snake
-// with an eligible move and left alone otherwise.  Every lane of the wave must call this.
-__device__ __forceinline__ void greedy_by_count(const EnvReader& rd, int ns, int lane, uint32_t open_all, uint32_t count, int my_len,
-                                                const int (&hx)[MSNAKE_MAX_SNAKES], const int (&hy)[MSNAKE_MAX_SNAKES],
-                                                uint32_t (&act)[MSNAKE_MAX_SNAKES]) {
+// The space of every candidate: one fill per distinct region that holds an open target.  Lane 4 s + m receives the
+// number of free cells connected to the target of move m + 1 of snake s, 0 where the move is not open.  Every lane of
+// the wave must call this.
+__device__ __forceinline__ uint32_t region_sizes(const Board& b, int dim, int lane) {
+    const uint64_t vacant = b.vacant;
+    const int gx = b.gx, gy = b.gy;
+    uint32_t space = 0u;
+    uint32_t pending = b.open_all;
+    const int max_sweeps = dim * dim;
+    for (int guard = 0; pending != 0u && guard < 16; ++guard) {
+        const int k = __builtin_ctz(pending);
+        const int sx = (int)rdlane((uint32_t)gx, k), sy = (int)rdlane((uint32_t)gy, k);
+        uint64_t r = lane == sy ? 1ull << sx : 0ull;
+        for (int sweeps = 0; sweeps < max_sweeps; sweeps += 4) {
+            const uint64_t before = r;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) r |= ((r << 1) | (r >> 1) | row_above(r) | row_below(r)) & vacant;
+            if (__ballot(r != before) == 0ull) break;
+        }
+        const uint32_t cells = wave_sum((uint32_t)__popcll(r));
+        const uint64_t filled_row = gather_row(r, gy);
+        const bool inside = lane < 16 && ((pending >> lane) & 1u) && ((filled_row >> gx) & 1ull);
+        const uint32_t got = (uint32_t)__ballot(inside) | (1u << k);
+        if (lane < 16 && ((got >> lane) & 1u)) space = cells;
+        pending &= ~got;
+    }
+    return space;
+}
+
+// The moves a count leaves to choose from.  `count`: lane 4 s + m holds the count of move m + 1 of snake s (0 where the
+// move is not open).  need = min(len, max over the open moves of count) by two quad-permute DPP steps, eligible = open
+// && count >= need; bit 4 s + m of the result.  Every lane of the wave must call this.
+__device__ __forceinline__ uint32_t eligible_moves(int lane, uint32_t open_all, uint32_t count, int my_len) {
     uint32_t mx = count;
     uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mx, 0xB1, 0xF, 0xF, true);  // quad_perm:[1,0,3,2]
     mx = mx > o ? mx : o;
     o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mx, 0x4E, 0xF, 0xF, true);           // quad_perm:[2,3,0,1]
     mx = mx > o ? mx : o;
     const uint32_t need = (uint32_t)my_len < mx ? (uint32_t)my_len : mx;
-    const uint32_t elig_all = (uint32_t)__ballot(lane < 16 && ((open_all >> lane) & 1u) && count >= need);
+    return (uint32_t)__ballot(lane < 16 && ((open_all >> lane) & 1u) && count >= need);
+}
+
+// safe_greedy's choice among the moves in `elig_all` (bit 4 s + m): the first, in the order 1, 2, 3, 4, whose target has
+// the strictly smallest L1 distance to any fruit.  act[s] is set for every snake with an eligible move and left alone
+// otherwise.  Every lane of the wave must call this.
+__device__ __forceinline__ void greedy_among(const EnvReader& rd, int ns, int lane, uint32_t elig_all,
+                                             const int (&hx)[MSNAKE_MAX_SNAKES], const int (&hy)[MSNAKE_MAX_SNAKES],
+                                             uint32_t (&act)[MSNAKE_MAX_SNAKES]) {
     uint32_t elig[MSNAKE_MAX_SNAKES];
 #pragma unroll
     for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) elig[s] = (elig_all >> (4 * s)) & 15u;
@@ -165,6 +201,13 @@ __device__ __forceinline__ void greedy_by_count(const EnvReader& rd, int ns, int
     }
 }
 
+// The choice space_greedy and territory_greedy share: safe_greedy's among the moves their count leaves eligible.
+__device__ __forceinline__ void greedy_by_count(const EnvReader& rd, int ns, int lane, uint32_t open_all, uint32_t count, int my_len,
+                                                const int (&hx)[MSNAKE_MAX_SNAKES], const int (&hy)[MSNAKE_MAX_SNAKES],
+                                                uint32_t (&act)[MSNAKE_MAX_SNAKES]) {
+    greedy_among(rd, ns, lane, eligible_moves(lane, open_all, count, my_len), hx, hy, act);
+}
+
 // ACT: the space_greedy actions are written (snake_mask != 0); SAFE / SPACE: safe_dev / space_dev are written
 template <bool ACT, bool SAFE, bool SPACE>
 __global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArgs a) {
@@ -176,31 +219,10 @@ __global__ __launch_bounds__(SPACE_WAVES * 64) void msnake_space_kernel(SpaceArg
     const int ns = a.v.ns, dim = a.v.dim;
     const EnvReader rd(a.v, e, lane);
     const Board b = read_board(a.v, rd, occ[wave], lane);
-    const uint64_t vacant = b.vacant;
-    const int gx = b.gx, gy = b.gy;
     const uint32_t open_all = b.open_all;
 
     // ---- fills: one per distinct region that holds an open target
-    uint32_t space = 0u;
-    uint32_t pending = open_all;
-    const int max_sweeps = dim * dim;
-    for (int guard = 0; pending != 0u && guard < 16; ++guard) {
-        const int k = __builtin_ctz(pending);
-        const int sx = (int)rdlane((uint32_t)gx, k), sy = (int)rdlane((uint32_t)gy, k);
-        uint64_t r = lane == sy ? 1ull << sx : 0ull;
-        for (int sweeps = 0; sweeps < max_sweeps; sweeps += 4) {
-            const uint64_t before = r;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) r |= ((r << 1) | (r >> 1) | row_above(r) | row_below(r)) & vacant;
-            if (__ballot(r != before) == 0ull) break;
-        }
-        const uint32_t cells = wave_sum((uint32_t)__popcll(r));
-        const uint64_t filled_row = gather_row(r, gy);
-        const bool inside = lane < 16 && ((pending >> lane) & 1u) && ((filled_row >> gx) & 1ull);
-        const uint32_t got = (uint32_t)__ballot(inside) | (1u << k);
-        if (lane < 16 && ((got >> lane) & 1u)) space = cells;
-        pending &= ~got;
-    }
+    const uint32_t space = region_sizes(b, dim, lane);
 
     // ---- space_greedy: the eligible moves, then safe_greedy's choice among them
     uint32_t act[MSNAKE_MAX_SNAKES];

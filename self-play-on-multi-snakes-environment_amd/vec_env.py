@@ -157,10 +157,13 @@ def relative_to_absolute(rel, heading):
     return torch.where(rel > 0, (rel - 1 + k) % 4 + 1, torch.zeros_like(rel))
 
 
-# the scripted policies that are an entry point of their own with a count output ([num_envs, n_snakes, 4] uint16):
-# name -> (the env's bound C function, its name, the keyword of the count output)
-COUNT_POLICIES = {_capi.SPACE_POLICY: ("_space_fn", "msnake_space_actions", "space_out"),
-                  _capi.TERRITORY_POLICY: ("_territory_fn", "msnake_territory_actions", "territory_out")}
+# the scripted policies that are an entry point of their own with uint16 outputs behind safe_dev:
+# name -> (the env's bound C function, its name, the keywords of those outputs in the order of the C arguments)
+COUNT_POLICIES = {_capi.SPACE_POLICY: ("_space_fn", "msnake_space_actions", ("space_out",)),
+                  _capi.TERRITORY_POLICY: ("_territory_fn", "msnake_territory_actions", ("territory_out",)),
+                  _capi.PATH_POLICY: ("_path_fn", "msnake_path_actions", ("path_out", "field_out"))}
+# output keyword -> the policy that writes it; every one is [num_envs, n_snakes, 4] but the field, [num_envs, dim, dim]
+COUNT_OUTPUTS = {kw: name for name, (_, _, kws) in COUNT_POLICIES.items() for kw in kws}
 
 # constructor arguments that may differ between the two handles of a device-side copy (include/msnake.h,
 # msnake_copy_envs): what MultiSnakeVecEnv.clone() lets a caller override
@@ -304,6 +307,7 @@ class MultiSnakeVecEnv:
         self._scripted_out = None  # scripted_actions_device(out=None): allocated on first use
         self._space_fn = self._L.msnake_space_actions
         self._territory_fn = self._L.msnake_territory_actions
+        self._path_fn = self._L.msnake_path_actions
         self._cells_fn = self._L.msnake_render_cells
         self._local_fn = self._L.msnake_render_local
         self._rays_fn = self._L.msnake_render_rays
@@ -381,8 +385,14 @@ class MultiSnakeVecEnv:
                 _capi.check(rc, "msnake_reset_envs")
         return obs, self._rew, self._done, self._info
 
-    def scripted_actions_device(self, policy, snakes=None, out=None, safe_out=None, space_out=None, territory_out=None):
-        """Actions of a scripted policy ("safe_greedy", "hamiltonian", "space_greedy", "territory_greedy", or None for the mask alone) for the
+    def _count_shape(self, kw):
+        if kw == "field_out":
+            return (self.num_envs, int(self.cfg.dim), int(self.cfg.dim))
+        return (self.num_envs, self.n_snakes, 4)
+
+    def scripted_actions_device(self, policy, snakes=None, out=None, safe_out=None, space_out=None, territory_out=None,
+                                path_out=None, field_out=None):
+        """Actions of a scripted policy ("safe_greedy", "hamiltonian", "space_greedy", "territory_greedy", "path_greedy", or None for the mask alone) for the
         snakes in `snakes` (indices; default every snake), computed on the device from the env's current state.  They go to
         columns `snakes` of `out`, an int32 [num_envs, >= n_snakes] device tensor as step_device() takes it; its other
         columns are left as they are (out=None: a cached, zero-initialised [num_envs, n_snakes] tensor of the env).
@@ -394,12 +404,17 @@ class MultiSnakeVecEnv:
         reachable-space counts (see reachable_space_device) and is returned behind the others that were asked for.
         "territory_greedy" (msnake_territory_actions) is space_greedy with the Voronoi territory in place of the space:
         the cells the snake reaches strictly before any other snake can; only with it, `territory_out`, a uint16
-        [num_envs, n_snakes, 4] device tensor, gets those counts (see territory_device), returned like space_out."""
+        [num_envs, n_snakes, 4] device tensor, gets those counts (see territory_device), returned like space_out.
+        "path_greedy" (msnake_path_actions) chooses among space_greedy's eligible moves by the shortest path to a fruit
+        around the bodies instead of the L1 distance, and plays space_greedy's move when no fruit can be reached; only
+        with it, `path_out`, a uint16 [num_envs, n_snakes, 4] device tensor, gets the path lengths (see path_device)
+        and `field_out`, a uint16 [num_envs, dim, dim] device tensor, the whole distance field (see
+        fruit_field_device).  The return order is actions, safe, path, field for those asked for."""
         torch = self._torch
-        if space_out is not None and policy != _capi.SPACE_POLICY:
-            raise ValueError(f"space_out is written by policy 'space_greedy' only, got policy {policy!r}")
-        if territory_out is not None and policy != _capi.TERRITORY_POLICY:
-            raise ValueError(f"territory_out is written by policy 'territory_greedy' only, got policy {policy!r}")
+        given = {"space_out": space_out, "territory_out": territory_out, "path_out": path_out, "field_out": field_out}
+        for kw, t in given.items():
+            if t is not None and policy != COUNT_OUTPUTS[kw]:
+                raise ValueError(f"{kw} is written by policy {COUNT_OUTPUTS[kw]!r} only, got policy {policy!r}")
         count = COUNT_POLICIES.get(policy)
         if count is None and policy not in _capi.SCRIPTED_POLICY:
             raise ValueError(f"policy must be 'safe_greedy', 'hamiltonian' or None, got {policy!r}")
@@ -423,16 +438,14 @@ class MultiSnakeVecEnv:
         if safe_out is not None:
             p_safe = self._checked(safe_out, "safe_out", torch.uint8, (self.num_envs, self.n_snakes)).data_ptr()
         if count is not None:
-            fn, c_name, kw = count
-            count_out = space_out if kw == "space_out" else territory_out
-            p_count = None
-            if count_out is not None:
-                p_count = self._checked(count_out, kw, torch.uint16, (self.num_envs, self.n_snakes, 4)).data_ptr()
-            rc = getattr(self, fn)(self._h, bits, out.data_ptr(), int(out.shape[1]), p_safe, p_count,
+            fn, c_name, kws = count
+            p_counts = [None if given[kw] is None else
+                        self._checked(given[kw], kw, torch.uint16, self._count_shape(kw)).data_ptr() for kw in kws]
+            rc = getattr(self, fn)(self._h, bits, out.data_ptr(), int(out.shape[1]), p_safe, *p_counts,
                                    self._cur_stream(self.device).cuda_stream)
             if rc < 0:
                 _capi.check(rc, c_name)
-            res = (out,) + tuple(t for t in (safe_out, count_out) if t is not None)
+            res = (out,) + tuple(t for t in [safe_out] + [given[kw] for kw in kws] if t is not None)
             return res[0] if len(res) == 1 else res
         rc = self._scripted_fn(self._h, _capi.SCRIPTED_POLICY[policy], bits, out.data_ptr(), int(out.shape[1]), p_safe,
                                self._cur_stream(self.device).cuda_stream)
@@ -452,14 +465,15 @@ class MultiSnakeVecEnv:
             _capi.check(rc, "msnake_scripted_actions")
         return out
 
-    def _counts_device(self, policy, out):
-        """The counts of a COUNT_POLICIES entry point alone: no action and no mask is written."""
-        fn, c_name, kw = COUNT_POLICIES[policy]
+    def _counts_device(self, kw, out):
+        """One uint16 output of a COUNT_POLICIES entry point alone: no action, no mask and no other output is written."""
+        fn, c_name, kws = COUNT_POLICIES[COUNT_OUTPUTS[kw]]
         if out is None:
             with self._torch.cuda.device(self.device):
-                out = self._torch.empty((self.num_envs, self.n_snakes, 4), dtype=self._torch.uint16, device=self.device)
-        self._checked(out, kw, self._torch.uint16, (self.num_envs, self.n_snakes, 4))
-        rc = getattr(self, fn)(self._h, 0, None, 0, None, out.data_ptr(), self._cur_stream(self.device).cuda_stream)
+                out = self._torch.empty(self._count_shape(kw), dtype=self._torch.uint16, device=self.device)
+        self._checked(out, kw, self._torch.uint16, self._count_shape(kw))
+        rc = getattr(self, fn)(self._h, 0, None, 0, None, *[out.data_ptr() if k == kw else None for k in kws],
+                               self._cur_stream(self.device).cuda_stream)
         if rc < 0:
             _capi.check(rc, c_name)
         return out
@@ -468,7 +482,7 @@ class MultiSnakeVecEnv:
         """uint16 [num_envs, n_snakes, 4]: entry m of a snake is the number of free cells 4-connected to the target of
         its move m + 1 through free cells, the target included; 0 when that move is not open (off the board or into a
         body) or the body is empty.  One flood fill per distinct region, on the device; nothing is synchronised."""
-        return self._counts_device(_capi.SPACE_POLICY, out)
+        return self._counts_device("space_out", out)
 
     def territory_device(self, out=None):
         """uint16 [num_envs, n_snakes, 4]: entry m of a snake is its Voronoi territory behind move m + 1: the number of
@@ -476,7 +490,22 @@ class MultiSnakeVecEnv:
         of its own open moves (bodies static, ties to the others); 0 when the move is not open, the body is empty, or
         another snake can enter the same target.  Equals reachable_space_device() when no other snake can move.  On the
         device; nothing is synchronised."""
-        return self._counts_device(_capi.TERRITORY_POLICY, out)
+        return self._counts_device("territory_out", out)
+
+    def path_device(self, out=None):
+        """uint16 [num_envs, n_snakes, 4]: entry m of a snake is the length of the shortest 4-connected path through free
+        cells from the target of its move m + 1 to a fruit that no body covers (0: the move eats); 0xFFFF
+        (msnake_path_actions: MSNAKE_PATH_NONE) when the move is not open, the body is empty or no such fruit can be
+        reached.  1 + the minimum over m is the snake's distance to food, the potential of reward shaping.  One BFS per
+        env on the device; nothing is synchronised."""
+        return self._counts_device("path_out", out)
+
+    def fruit_field_device(self, out=None):
+        """uint16 [num_envs, dim, dim]: entry [c0, c1] is the length of the shortest 4-connected path through free cells
+        from cell (c0, c1) to a fruit that no body covers, the indexing of render_cells_device(); 0xFFFF for a cell
+        under a body and for a free cell from which no such fruit can be reached.  On the device; nothing is
+        synchronised."""
+        return self._counts_device("field_out", out)
 
     @property
     def cells_shape(self):

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Cost of msnake_scripted_actions, msnake_space_actions and msnake_territory_actions next to msnake_step on the same handle.  19x19x3 snake_env at
+"""Cost of msnake_scripted_actions, msnake_space_actions, msnake_territory_actions and msnake_path_actions next to msnake_step on the same handle.  19x19x3 snake_env at
 4 096 and 32 768 envs, on a freshly reset batch and 500 steps into safe_greedy play (longer bodies).  The Hamiltonian
 cycle needs an even board: its legs run on a 20x20 handle of the same batch, in the same kind of state.  The "->step"
 legs are one scripted call and one step per call (the self-play loop on the device).  `worst_case_62x62`: the flood
 fill's longest runs, serpentine mazes of a 62x62 board (one corridor of 1 953 cells, along the rows and along the
 columns, nine head positions each), copied over the whole batch; the territory race runs on the same states (the wall
-snake is the opponent), and on `two_ends`, where two snakes enter the corridor from its two ends.
+snake is the opponent), and on `two_ends`, where two snakes enter the corridor from its two ends.  The fruits of these
+states lie on the corridor's first cell, so the BFS of msnake_path_actions walks the corridor from that end up to the
+head: with the field it runs to the end (up to 1 951 levels), without it it stops at the head's open target.
 
 Two figures per leg, both from HIP events after a warm-up, legs alternating in one process:
   graph_us: CALLS back-to-back calls captured into one HIP graph (a linear chain) and replayed: the kernel's cadence,
@@ -14,7 +16,7 @@ Two figures per leg, both from HIP events after a warm-up, legs alternating in o
             Python caller pays when nothing else is queued; mostly the host's submission rate.
 The step leg plays the constant action 1 (with auto reset), so over its CALLS calls the batch leaves the state the run
 is labelled with; the scripted legs read the restored state every time.  The state is restored before every leg.
-    python tools/scripted_cost.py > profiles/territory_cost.json"""
+    python tools/scripted_cost.py > profiles/path_cost.json"""
 import argparse
 import json
 import os
@@ -85,6 +87,8 @@ def main():
         safe = torch.zeros((n, 3), dtype=torch.uint8, device=env.device)
         space = torch.zeros((n, 3, 4), dtype=torch.uint16, device=env.device)
         terr = torch.zeros((n, 3, 4), dtype=torch.uint16, device=env.device)
+        path = torch.zeros((n, 3, 4), dtype=torch.uint16, device=env.device)
+        field = torch.zeros((n, 19, 19), dtype=torch.uint16, device=env.device)
         legs = {
             "safe_greedy": lambda: env.scripted_actions_device("safe_greedy", out=acts),
             "safe_greedy+mask": lambda: env.scripted_actions_device("safe_greedy", out=acts, safe_out=safe),
@@ -98,10 +102,16 @@ def main():
             "territory_greedy+mask+territory": lambda: env.scripted_actions_device("territory_greedy", out=acts, safe_out=safe,
                                                                                    territory_out=terr),
             "territory_only": lambda: env.territory_device(out=terr),
+            "path_greedy": lambda: env.scripted_actions_device("path_greedy", out=acts),
+            "path_greedy+mask+path+field": lambda: env.scripted_actions_device("path_greedy", out=acts, safe_out=safe, path_out=path,
+                                                                               field_out=field),
+            "path_only": lambda: env.path_device(out=path),
+            "field_only": lambda: env.fruit_field_device(out=field),
             "msnake_step": lambda: env.step_device(ones),
             "safe_greedy->step": lambda: env.step_device(env.scripted_actions_device("safe_greedy", out=acts)),
             "space_greedy->step": lambda: env.step_device(env.scripted_actions_device("space_greedy", out=acts)),
             "territory_greedy->step": lambda: env.step_device(env.scripted_actions_device("territory_greedy", out=acts)),
+            "path_greedy->step": lambda: env.step_device(env.scripted_actions_device("path_greedy", out=acts)),
         }
         out = {}
         for state in ("fresh_reset", f"after_{args.play_steps}_greedy_steps"):
@@ -153,9 +163,13 @@ def main():
             env.copy_envs_device(src, torch.arange(n, dtype=torch.int32, device=env.device) % len(states))
             acts = torch.ones((n, 2), dtype=torch.int32, device=env.device)
             space = torch.zeros((n, 2, 4), dtype=torch.uint16, device=env.device)
+            field = torch.zeros((n, 62, 62), dtype=torch.uint16, device=env.device)
             out[name] = {}
-            for pol, kw in (("space_greedy", "space_out"), ("territory_greedy", "territory_out")):
-                fn = lambda: env.scripted_actions_device(pol, out=acts, **{kw: space})
+            for leg, pol, kw in (("space_greedy", "space_greedy", {"space_out": space}),
+                                 ("territory_greedy", "territory_greedy", {"territory_out": space}),
+                                 ("path_greedy", "path_greedy", {"path_out": space}),
+                                 ("path_greedy+field", "path_greedy", {"path_out": space, "field_out": field})):
+                fn = lambda: env.scripted_actions_device(pol, out=acts, **kw)
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
@@ -167,8 +181,11 @@ def main():
                     for _ in range(args.calls):
                         fn()
                 v = [timed(g.replay) for _ in range(args.rounds)]
-                out[name][pol] = {"graph_us": [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)],
-                                  "largest_count": int(space.view(torch.int16).max())}
+                count = space.view(torch.int16).to(torch.int32) & 0xFFFF
+                if pol == "path_greedy":  # the longest finite path (MSNAKE_PATH_NONE is no count)
+                    count = torch.where(count == 0xFFFF, torch.zeros_like(count), count)
+                out[name][leg] = {"graph_us": [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)],
+                                  "largest_count": int(count.max())}
             env.close(), src.close()
             print(f"{n} envs, worst case {name}: done", file=sys.stderr, flush=True)
         res["worst_case_62x62"][str(n)] = out
