@@ -46,6 +46,9 @@
  *                      snake policies outside the reference are trained on, cut on the device.
  *   msnake_render_rays: no reference counterpart; the eight-direction distance vector of snake agents (wall, fruit, own
  *                      body, another snake), read off the same cell codes on the device.
+ *   msnake_agent_outcomes <- the per-snake rewards that update_snake computes and SnakeEnv.step drops for every snake
+ *                      but the main one (snake_multiple_test.py:97-145,166-197), plus which snake died and each snake's episode
+ *                      totals, which the reference never forms: what self-play needs to learn from every column.
  *   msnake_get_stats <- the epinfobuf aggregation in ppo_multi_agent.py:288,331,366-390
  *
  * RNG contract (shared with oracle/ and tests/golden): draw i of global env g is word (i & 3) of
@@ -478,6 +481,56 @@ int msnake_render_local(msnake_handle h, int32_t radius, uint32_t snake_mask, in
 #define MSNAKE_RAY_OTHER 3
 int msnake_render_rays(msnake_handle h, uint32_t snake_mask, int32_t oriented, uint8_t* rays_dev, uint8_t* heading_dev,
                        void* stream);
+
+/* Per-snake outcomes of a step: which snake ate, which died, what every snake's reward was, and each snake's running
+ * totals of the env's current episode.  msnake_step reports snake 0 only; this call, issued behind it, derives every
+ * snake's outcome from two consecutive canonical states: the "before" facts are kept in a tracker that the caller owns,
+ * the "after" facts are read from the handle's state.  S = n_snakes in every shape below.
+ * Terms: grow_to(s) is snake s's grow_to word of the canonical state; alive(s) is len > 0 under snake_env and
+ * adversarial and the alive word (the new_world alive bit) under new_world.  Under new_world a snake that hits itself
+ * keeps its body and its alive bit is set again by the next step that finds it clear, so there a snake can "die" more
+ * than once in one episode and come alive again.
+ * The tracker: track_dev is int32 [num_envs][S][8], 4-byte aligned, owned by the caller; row [env][s] holds
+ *   [0] grow_to  [1] alive  [2] ep_fruit  [3] ep_alive_steps  [4] first_death  [5] ep_steps  [6] ep_return (f32 bits)  [7] 0
+ * words 0 and 1 being the facts of the state the row was last brought up to, words 2..6 the totals of the env's current
+ * episode so far (see info_dev).
+ * Arming, flags = MSNAKE_AGENT_ARM: every row is written from the current state, the five episode words and word 7
+ * zero.  No outcome is produced: done_dev and the four outputs must be NULL.  A tracker needs arming before its first
+ * use and after msnake_reset, msnake_set_state / msnake_set_state_all, msnake_copy_envs into the handle, a
+ * msnake_reset_envs of an env that was not done, and any step that was not followed by an outcomes call.
+ * Outcomes, flags = 0, issued behind each msnake_step on the same stream; done_dev is that step's done output (uint8
+ * [num_envs], required).  For every env and snake s, with `before` = the tracker row and `after` = the state:
+ *   ate   = max(0, grow_to after - grow_to before) >> 1     (every fruit eaten raises grow_to by 2)
+ *   was   = row word 1 != 0,  now = alive(s) after,  died = was && !now,  ended = was && (died || done[env])
+ * rew_dev (may be NULL): float32 [num_envs][S], 4-byte aligned: the rule set's own reward formula applied to snake s:
+ *   snake_env and adversarial: died ? -1 : ate;  new_world: now ? -1 : ate (the reference's done = snake.alive, kept).
+ *   On a step taken from an unfinished episode, column 0 equals that step's rew_dev bit for bit under all three rule sets.
+ * ate_dev (may be NULL): uint8 [num_envs][S]: min(ate, 255); rew_dev and the totals are not clamped.
+ * flags_dev (may be NULL): uint8 [num_envs][S]: MSNAKE_AGENT_ALIVE (now) | MSNAKE_AGENT_WAS_ALIVE (was) |
+ *   MSNAKE_AGENT_DIED | MSNAKE_AGENT_ENDED.  WAS_ALIVE marks the (env, snake) samples a learner can use, ENDED the last
+ *   one of a snake's life or episode.
+ * info_dev (may be NULL): int32 [num_envs][S][4], 4-byte aligned: the totals of the env's current episode after this step,
+ *   ep_fruit (sum of ate), ep_alive_steps (steps at whose end the snake was alive), first_death (1-based episode step
+ *   of the snake's first death, 0 = none), ep_return (sum of rew, f32 bits).  On a done step: the episode's totals.
+ * At least one of the four outputs must be given.  The tracker is then brought up to date: a row of an env with
+ * done[env] == 0 receives the after-facts and the totals just reported; a row of an env with done[env] != 0 receives
+ * what arming writes after a reset (grow_to 3, alive 1, totals 0), because the caller is expected to reset that env
+ * before its next step -- msnake_reset_envs(h, done_dev, ...) on the same stream -- and the next call then needs no
+ * arming.  The result is defined for any tracker contents and meaningful only for an armed one.
+ * Like its siblings the call only reads the handle's state, draws no random numbers, allocates nothing, does not
+ * synchronise and adds nothing to env_steps; asynchronous on `stream`, and [msnake_step, msnake_agent_outcomes,
+ * msnake_reset_envs] can be captured into one HIP graph.  MSNAKE_E_ARG, before any device work: unknown flag bits;
+ * track_dev NULL; arming with done_dev or an output non-NULL; outcomes with done_dev NULL or without any output; a
+ * handle created with auto_reset = 1 (there the step has already replaced the after-state of a done env by a fresh
+ * episode, so the terminal outcomes of snakes >= 1 cannot be known).  MSNAKE_E_ALIGN: track_dev, rew_dev or info_dev not
+ * 4-byte aligned.  MSNAKE_E_HANDLE for a NULL handle. */
+#define MSNAKE_AGENT_ARM 1        /* flags: write the tracker from the current state, produce no outcome */
+#define MSNAKE_AGENT_ALIVE 1      /* flags_dev bits */
+#define MSNAKE_AGENT_WAS_ALIVE 2
+#define MSNAKE_AGENT_DIED 4
+#define MSNAKE_AGENT_ENDED 8
+int msnake_agent_outcomes(msnake_handle h, int32_t flags, int32_t* track_dev, const uint8_t* done_dev, float* rew_dev,
+                          uint8_t* ate_dev, uint8_t* flags_dev, int32_t* info_dev, void* stream);
 
 /* Copy the aggregate statistics to the host.  Blocking: waits for the device (every step issued so
  * far, on any stream) before it sums the per-env totals.  episodes / ep_len_sum / ep_return_sum /

@@ -592,6 +592,26 @@ int msnake_render_rays(msnake_handle h, uint32_t snake_mask, int32_t oriented, u
     return launched(msnake::launch_rays(h->p, h->cfg.rules, snake_mask, oriented, rays_dev, heading_dev, static_cast<hipStream_t>(stream)));
 }
 
+int msnake_agent_outcomes(msnake_handle h, int32_t flags, int32_t* track_dev, const uint8_t* done_dev, float* rew_dev,
+                          uint8_t* ate_dev, uint8_t* flags_dev, int32_t* info_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    if (flags & ~MSNAKE_AGENT_ARM) return fail(MSNAKE_E_ARG, "msnake_agent_outcomes: flags 0x%x has bits other than MSNAKE_AGENT_ARM", flags);
+    if (!track_dev) return fail(MSNAKE_E_ARG, "msnake_agent_outcomes: track_dev is NULL");
+    const bool arm = (flags & MSNAKE_AGENT_ARM) != 0, any_out = rew_dev || ate_dev || flags_dev || info_dev;
+    if (arm && (done_dev || any_out))
+        return fail(MSNAKE_E_ARG, "msnake_agent_outcomes: arming produces no outcome (done_dev and the four outputs must be NULL)");
+    if (!arm && !done_dev) return fail(MSNAKE_E_ARG, "msnake_agent_outcomes: done_dev is NULL (the step's done output)");
+    if (!arm && !any_out) return fail(MSNAKE_E_ARG, "msnake_agent_outcomes: nothing to write (rew_dev, ate_dev, flags_dev and info_dev are NULL)");
+    if (h->p.auto_reset)
+        return fail(MSNAKE_E_ARG, "msnake_agent_outcomes: the handle resets done envs inside the step (auto_reset = 1), so their "
+                                  "terminal state is gone; create it with auto_reset = 0 and follow the step with msnake_reset_envs");
+    if (((uintptr_t)track_dev | (uintptr_t)rew_dev | (uintptr_t)info_dev) & 3)
+        return fail(MSNAKE_E_ALIGN, "track_dev, rew_dev and info_dev must be 4-byte aligned");
+    DeviceGuard guard(h->cfg.device);
+    return launched(msnake::launch_agents(h->p, h->cfg.rules, arm, track_dev, done_dev, rew_dev, ate_dev, flags_dev, info_dev,
+                                          static_cast<hipStream_t>(stream)));
+}
+
 // ---- canonical state import / export.  The device packs / unpacks (msnake_state_*_kernel); the host
 //      only sizes buffers and copies.  Blocking: every call starts with a device synchronise. ----
 namespace {

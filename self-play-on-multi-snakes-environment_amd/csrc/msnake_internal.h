@@ -229,6 +229,10 @@ hipError_t launch_local(const StepParams& p, int rules, int radius, uint32_t sna
 // eight-direction ray observations of the snakes in snake_mask (msnake_rays.inc); rays 4-byte aligned, heading NULL = not written
 hipError_t launch_rays(const StepParams& p, int rules, uint32_t snake_mask, int oriented, uint8_t* rays, uint8_t* heading,
                        hipStream_t stream);
+// per-snake outcomes of the last step against the caller's tracker, or (arm) the tracker from the state (msnake_agents.inc);
+// any of rew / ate / flags / info may be NULL.  Reads the handle's state only
+hipError_t launch_agents(const StepParams& p, int rules, bool arm, int32_t* track, const uint8_t* done, float* rew, uint8_t* ate,
+                         uint8_t* flags, int32_t* info, hipStream_t stream);
 // the DIM of the compile-time-shape instantiation that fits the configuration in `p` in every folded field, or 0 (host only)
 int spec_dim_of(const StepParams& p, int rules);
 // which kernel one launch gets: MSNAKE_CALL_GENERIC / _SHAPE / _PLAIN of include/msnake.h (host only, no HIP call)

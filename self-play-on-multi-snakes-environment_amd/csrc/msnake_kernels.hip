@@ -2023,3 +2023,4 @@ static hipError_t launch_by_flags(int flags, const F& f) {
 #include "msnake_cells.inc"     // msnake_render_cells: the observation as cell codes and the per-snake table (off the step path)
 #include "msnake_local.inc"     // msnake_render_local: head-centred cell-code windows per snake (off the step path)
 #include "msnake_rays.inc"      // msnake_render_rays: eight-direction ray observations per snake (off the step path)
+#include "msnake_agents.inc"    // msnake_agent_outcomes: per-snake rewards, deaths and episode totals behind a step (off the step path)

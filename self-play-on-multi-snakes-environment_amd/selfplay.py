@@ -33,6 +33,7 @@ import torch.nn.functional as F
 
 from ._capi import SCRIPTED_POLICY_NAMES as SCRIPTED_POLICIES
 from ._capi import SCRIPTED_OPPONENT_NAMES as SCRIPTED_OPPONENTS  # SCRIPTED_POLICIES and path_greedy: what a ScriptedOpponent may play
+from ._capi import AGENT_ENDED, AGENT_WAS_ALIVE
 from .vec_env import check_radius, relative_to_absolute
 
 
@@ -226,6 +227,29 @@ def gae(rewards, values, dones, last_values, last_dones, gamma=0.99, lam=0.95):
         delta = rewards[t] + gamma * nextvalues * nextnonterminal - values[t]
         advs[t] = lastgaelam = delta + gamma * lam * nextnonterminal * lastgaelam
     return advs + values, advs
+
+
+def agent_targets(rew, val, flags, last_val, gamma=0.99, lam=0.95):
+    """GAE targets for every snake of every env from the outputs of MultiSnakeVecEnv.agent_outcomes_device.  rew, val:
+    float [T, N, S]; flags: uint8 [T, N, S] (AGENT_* bits); last_val: float [N, S], the values behind the last step.
+    Returns (returns float [T, N, S], valid bool [T, N, S]).  A sample is valid iff WAS_ALIVE (the snake acted in that
+    step) and terminal iff ENDED (it died, or the env's episode ended).  An invalid sample contributes nothing -- its
+    return is 0 -- and cuts the recursion, and a run of valid samples that stops in front of an invalid one without
+    ENDED is closed like a terminal one: there is no value to bootstrap from.  So on each agent's maximal runs of valid
+    samples the result equals gae() run on that run alone."""
+    valid, ended = (flags & AGENT_WAS_ALIVE) != 0, (flags & AGENT_ENDED) != 0
+    T = rew.shape[0]
+    advs = torch.zeros_like(rew)
+    lastgaelam = torch.zeros_like(last_val)
+    zero = torch.zeros_like(last_val)
+    for t in reversed(range(T)):
+        goes_on = ~ended[t] if t == T - 1 else ~ended[t] & valid[t + 1]
+        nextnonterminal = goes_on.to(rew.dtype)
+        nextvalues = torch.where(goes_on, last_val if t == T - 1 else val[t + 1], zero)
+        delta = rew[t] + gamma * nextvalues * nextnonterminal - val[t]
+        lastgaelam = torch.where(valid[t], delta + gamma * lam * nextnonterminal * lastgaelam, zero)
+        advs[t] = lastgaelam
+    return torch.where(valid, advs + val, torch.zeros_like(val)), valid
 
 
 def ppo_loss(logits, vpred, actions, returns, old_values, old_neglogp, cliprange, ent_coef=0.01, vf_coef=0.5):
@@ -500,9 +524,22 @@ def refresh_scripted(opponents):
 class Runner:
     """ppo_multi_agent.py:145-216 with everything on the device."""
 
-    def __init__(self, env, model, opponents, nsteps, gamma, lam, local_radius=None, oriented=True, rays=False):
+    def __init__(self, env, model, opponents, nsteps, gamma, lam, local_radius=None, oriented=True, rays=False, all_snakes=False):
+        """all_snakes=True: every snake of every env is played by `model` on its own window or rays, and run() returns the
+        samples of all of them (agent_targets over env.step_agents_device).  Needs rays=True or local_radius, no
+        opponents, and an env created with auto_reset=False."""
         if rays and local_radius is not None:
             raise ValueError("rays=True and local_radius are mutually exclusive: a run trains on rays or on windows")
+        self.all_snakes = bool(all_snakes)
+        if self.all_snakes:
+            if not rays and local_radius is None:
+                raise ValueError("all_snakes=True needs rays=True or local_radius: one set of weights can play every column "
+                                 "only on per-snake observations")
+            if opponents:
+                raise ValueError("all_snakes=True plays every snake with the learner's weights: there is no opponent to give")
+            if getattr(env, "_ctor", {}).get("auto_reset", True):
+                raise ValueError("all_snakes=True needs an env created with auto_reset=False (step_agents_device)")
+            opponents = []
         self.env, self.model, self.opponents = env, model, opponents
         self.nsteps, self.gamma, self.lam = nsteps, gamma, lam
         self.local_radius, self.oriented, self.rays = local_radius, bool(oriented), bool(rays)
@@ -511,6 +548,8 @@ class Runner:
         if self.per_snake:
             # the learner and every network opponent see their own snake's window / rays: one env call for all of them
             self.win_snakes = [0] + [i + 1 for i, opp in enumerate(opponents) if isinstance(opp, nn.Module)]
+            if self.all_snakes:
+                self.win_snakes = list(range(env.n_snakes))
             self.slot = {s: q for q, s in enumerate(self.win_snakes)}
             shape = (env.num_envs,) + (env.rays_shape(self.win_snakes) if self.rays else env.local_shape(local_radius, self.win_snakes))
             self.win = torch.empty(shape, dtype=torch.uint8, device=self.obs.device)
@@ -559,7 +598,41 @@ class Runner:
                 acts.append(opp.step(self.obs[..., 3 * (i + 1):3 * (i + 2)])[0])
         return a, v, nlp, torch.stack(acts, dim=1).to(torch.int32)
 
+    def run_all_snakes(self):
+        """run() for all_snakes=True: the batch is the valid (t, env, snake) samples, those in which the snake acted."""
+        T, N, S = self.nsteps, self.env.num_envs, self.env.n_snakes
+        dev = self.obs.device
+        mb_obs = torch.empty((T,) + tuple(self.win.shape), dtype=torch.uint8, device=dev)
+        mb_rew = torch.empty((T, N, S), device=dev); mb_val = torch.empty((T, N, S), device=dev)
+        mb_nlp = torch.empty((T, N, S), device=dev); mb_flags = torch.empty((T, N, S), dtype=torch.uint8, device=dev)
+        mb_act = torch.empty((T, N, S), dtype=torch.long, device=dev)
+        ep_r, ep_l = [], []
+        for t in range(T):
+            a, v, nlp = self.model.step(self.win.flatten(0, 1))
+            mb_obs[t] = self.win
+            mb_act[t], mb_val[t], mb_nlp[t] = a.view(N, S), v.view(N, S), nlp.view(N, S)
+            full = relative_to_absolute(a.view(N, S), self.heading) if self.oriented else a.view(N, S)
+            self.obs, rew, done, info, agents = self.env.step_agents_device(full.to(torch.int32))
+            self.observe_local()
+            mb_rew[t], mb_flags[t] = agents.rew, agents.flags  # (copies: the next step overwrites the env's tensors)
+            self.dones = done.float()
+            ep_r.append(torch.where(done.bool(), info[:, 0].view(torch.float32), torch.full_like(rew, float("nan"))))
+            ep_l.append(info[:, 1].clone())  # `info` is the env's buffer: the next step overwrites it
+        last_values = self.model.value(self.win.flatten(0, 1)).view(N, S)
+        returns, valid = agent_targets(mb_rew, mb_val, mb_flags, last_values, self.gamma, self.lam)
+        self.last_flags = mb_flags  # (tests: the batch is exactly the WAS_ALIVE samples)
+        r = torch.stack(ep_r).flatten(); l = torch.stack(ep_l).flatten()
+        keep = ~torch.isnan(r)
+        t_el = round(time.time() - self.tstart, 6)
+        epinfos = [{"r": round(float(x), 6), "l": int(y), "t": t_el} for x, y in zip(r[keep].tolist(), l[keep].tolist())]
+        idx = valid.flatten().nonzero()[:, 0]
+        pick = lambda x: x.flatten(0, 2)[idx]
+        ended = ((mb_flags & AGENT_ENDED) != 0).float()
+        return pick(mb_obs), pick(returns), pick(ended), pick(mb_act), pick(mb_val), pick(mb_nlp), epinfos
+
     def run(self):
+        if self.all_snakes:
+            return self.run_all_snakes()
         T, N = self.nsteps, self.env.num_envs
         dev = self.obs.device
         mb_obs = torch.empty((T, N) + tuple(self.learner_obs().shape[1:]), dtype=torch.uint8, device=dev)
@@ -594,7 +667,7 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
           cliprange=lambda f: f * 0.1, opponent_save_interval=50, max_saved_opponents=1000, csv_path=None,
           monitor_path=None, seed=0, log_fn=print, amp_dtype=None, json_path=None, tb_dir=None,
           save_dir=None, save_interval=0, load_path=None, resume=False, scripted_opponents=None, local_radius=None,
-          oriented=True, rays=False):
+          oriented=True, rays=False, all_snakes=False):
     """ppo_multi_agent.py:231-404 (hyper-parameters of test/ppo1_single_test.py:42-47 as defaults).
 
     Checkpoints (ppo_multi_agent.py:112-133, 296-306, 349-364, 392-404), weights only, under `save_dir`
@@ -613,9 +686,19 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
     carry the radius and the flag: loading the other kind is refused.
     `rays=True`: the learner and its network opponents are RayPolicies over their own snake's eight-direction rays
     (render_rays_device, one env call per step for all of them), an MLP on 32 bytes per snake; `oriented` means the same
-    as for windows.  Mutually exclusive with `local_radius`; weights and trainer states carry the kind here too."""
+    as for windows.  Mutually exclusive with `local_radius`; weights and trainer states carry the kind here too.
+    `all_snakes=True` (with `rays` or `local_radius`, an env created with auto_reset=False, no scripted opponents): every
+    snake is played by the learner's current weights and every snake's transitions are learned from
+    (Runner.run_all_snakes): the batch of an update is the valid (t, env, snake) samples, split into `nminibatches`
+    parts.  No opponent pool is kept.  The episode statistics stay the env's own (snake 0), so curves remain comparable;
+    the log gains agent_samples (the batch size) and sample_fps."""
     if rays and local_radius is not None:
         raise ValueError("rays=True and local_radius are mutually exclusive: a run trains on rays or on windows")
+    if all_snakes and not rays and local_radius is None:
+        raise ValueError("all_snakes=True needs rays=True or local_radius: one set of weights can play every column only "
+                         "on per-snake observations")
+    if all_snakes and scripted_opponents:
+        raise ValueError("all_snakes=True plays every snake with the learner's weights: scripted_opponents must be empty")
     torch.manual_seed(seed); random.seed(seed)
     dev = env.device
     n_snakes = env.n_snakes
@@ -632,8 +715,8 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
         raise ValueError(f"scripted_opponents: snake indices must lie in [1, {n_snakes}), got {sorted(scripted)}")
     team = ScriptedColumns(env) if scripted else None   # this run's own: nothing is left behind on the env
     opponents = [ScriptedOpponent(env, scripted[i + 1], i + 1, columns=team) if i + 1 in scripted else
-                 make_policy() for i in range(n_snakes - 1)]
-    learned = [i for i in range(n_snakes - 1) if i + 1 not in scripted]  # opponent slots played by past selves
+                 make_policy() for i in range(0 if all_snakes else n_snakes - 1)]
+    learned = [i for i in range(len(opponents)) if i + 1 not in scripted]  # opponent slots played by past selves
     if save_dir:
         os.makedirs(save_dir, exist_ok=True)
     if load_path:
@@ -676,7 +759,8 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
             pool.save(model)
         if save_dir:  # from the first pool file on there is a state a resume can start from
             save_trainer_state(0)
-    runner = Runner(env, model, opponents, nsteps, gamma, lam, local_radius=local_radius, oriented=oriented, rays=rays)
+    runner = Runner(env, model, opponents, nsteps, gamma, lam, local_radius=local_radius, oriented=oriented, rays=rays,
+                    all_snakes=all_snakes)
     nbatch = env.num_envs * nsteps
     nbatch_train = nbatch // nminibatches
     assert nbatch % nminibatches == 0
@@ -702,10 +786,12 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
         if mon:
             mon.write(epinfos)
         stats = []
+        nsamples = obs.shape[0]  # nbatch; with all_snakes the number of valid samples of this rollout
         for _ in range(noptepochs):
-            inds = torch.randperm(nbatch, device=dev)
-            for start in range(0, nbatch, nbatch_train):
-                mb = inds[start:start + nbatch_train]
+            inds = torch.randperm(nsamples, device=dev)
+            batches = ([b for b in torch.tensor_split(inds, nminibatches) if b.numel()] if all_snakes else
+                       [inds[start:start + nbatch_train] for start in range(0, nbatch, nbatch_train)])
+            for mb in batches:
                 logits, vpred = model(obs[mb])
                 loss, parts = ppo_loss(logits, vpred, actions[mb], returns[mb], values[mb], nlps[mb], clipnow,
                                        ent_coef, vf_coef)
@@ -732,6 +818,8 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
                    "time_elapsed": tnow - tfirst, "ep_rew_mean": eprew}
             if pools:
                 kvs["num_opponents"] = pools[0].num
+            if all_snakes:
+                kvs["agent_samples"], kvs["sample_fps"] = nsamples, int(nsamples / (tnow - tstart))
             kvs.update(dict(zip(("policy_loss", "value_loss", "policy_entropy", "approxkl", "clipfrac"), lossvals)))
             history.append(kvs)
             for sink in sinks:

@@ -12,6 +12,7 @@ All env state and all step outputs live in HBM; `step_device()` is the zero-copy
 PyTorch-ROCm policy (device tensors in, device tensors out, asynchronous on the current stream),
 `step()` is the NumPy-returning reference-compatible wrapper around it.
 """
+import collections
 import ctypes
 import time
 
@@ -170,6 +171,10 @@ COUNT_OUTPUTS = {kw: name for name, (_, _, kws) in COUNT_POLICIES.items() for kw
 CLONE_OVERRIDES = ("record_policy", "envs_per_block", "obs_scale", "auto_reset", "max_steps", "seed", "env_id_base")
 
 
+# what agent_outcomes_device() / step_agents_device() return of msnake_agent_outcomes: device tensors, None = not written
+AgentOutcomes = collections.namedtuple("AgentOutcomes", ("rew", "ate", "flags", "info"))
+
+
 class LazyInfos:
     """Sequence of per-env info dicts, materialised on access.
 
@@ -311,6 +316,11 @@ class MultiSnakeVecEnv:
         self._cells_fn = self._L.msnake_render_cells
         self._local_fn = self._L.msnake_render_local
         self._rays_fn = self._L.msnake_render_rays
+        self._agents_fn = self._L.msnake_agent_outcomes
+        # msnake_agent_outcomes: the tracker and the env's own outputs, allocated on first use; stale = the tracker no
+        # longer describes the state (a full reset, an installed or copied state, a tape): the next call arms it first
+        self._track = self._agents_own = None
+        self._track_stale = True
 
     # ------------------------------------------------------------------ device-side API
     def _stream(self):
@@ -349,6 +359,7 @@ class MultiSnakeVecEnv:
             if final_out is not None or truncated_out is not None:
                 raise ValueError("final_out / truncated_out need a mask (a full reset has no terminal observations)")
             _capi.check(self._L.msnake_reset(self._h, obs.data_ptr(), self._stream()), "msnake_reset")
+            self._track_stale = True
             return obs
         m = self._mask(mask)
         p_final = self._out(final_out).data_ptr() if final_out is not None else None
@@ -632,6 +643,81 @@ class MultiSnakeVecEnv:
             _capi.check(rc, "msnake_render_rays")
         return out if heading_out is None else (out, heading_out)
 
+    @property
+    def agent_tracker(self):
+        """The int32 [num_envs, n_snakes, 8] device tensor msnake_agent_outcomes keeps its "before" facts and episode
+        totals in (rows: _capi.AGENT_TRACK_WORDS); allocated on first use, owned by the env."""
+        if self._track is None:
+            with self._torch.cuda.device(self.device):
+                self._track = self._torch.zeros((self.num_envs, self.n_snakes, 8), dtype=self._torch.int32, device=self.device)
+        return self._track
+
+    def arm_agents_device(self):
+        """Write the tracker of agent_outcomes_device() from the env's current state, with every episode total zero
+        (msnake_agent_outcomes with MSNAKE_AGENT_ARM).  The env does this itself before the next outcomes call after
+        reset_device() without a mask, set_state_words(), set_state_all(), copy_envs_device() and rollout_device(); a
+        caller arms after anything else that moves the state without an outcomes call behind it (a step_device() whose
+        outcomes were skipped, a masked reset of an env that was not done).  Returns the tracker; nothing is synchronised."""
+        track = self.agent_tracker
+        rc = self._agents_fn(self._h, _capi.AGENT_ARM, track.data_ptr(), None, None, None, None, None,
+                             self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_agent_outcomes")
+        self._track_stale = False
+        return track
+
+    def agent_outcomes_device(self, done, rew_out=None, ate_out=None, flags_out=None, info_out=None):
+        """Every snake's outcome of the step just taken (msnake_agent_outcomes), called behind step_device() on an env
+        created with auto_reset=False; `done` is that step's done tensor.  rew_out float32 [num_envs, n_snakes]: the rule
+        set's reward formula applied to each snake (column 0 is the step's own reward); ate_out uint8 [num_envs,
+        n_snakes]: fruits eaten, at most 255; flags_out uint8 [num_envs, n_snakes]: _capi.AGENT_ALIVE | AGENT_WAS_ALIVE |
+        AGENT_DIED | AGENT_ENDED; info_out int32 [num_envs, n_snakes, 4]: ep_fruit, ep_alive_steps, first_death and
+        ep_return (f32 bits) of the env's current episode after this step.  Only the outputs given are written; with none
+        given all four go to tensors of the env's own, overwritten by the next such call.  Rows of a done env in the
+        tracker are set up for the reset the caller issues next (reset_device(mask=done)).  Returns an AgentOutcomes
+        (rew, ate, flags, info), None for what was not written; nothing is synchronised."""
+        torch = self._torch
+        n = (self.num_envs, self.n_snakes)
+        if rew_out is None and ate_out is None and flags_out is None and info_out is None:
+            if self._agents_own is None:
+                with torch.cuda.device(self.device):
+                    self._agents_own = AgentOutcomes(torch.zeros(n, dtype=torch.float32, device=self.device),
+                                                     torch.zeros(n, dtype=torch.uint8, device=self.device),
+                                                     torch.zeros(n, dtype=torch.uint8, device=self.device),
+                                                     torch.zeros(n + (4,), dtype=torch.int32, device=self.device))
+            res = self._agents_own
+        else:
+            res = AgentOutcomes(None if rew_out is None else self._checked(rew_out, "rew_out", torch.float32, n),
+                                None if ate_out is None else self._checked(ate_out, "ate_out", torch.uint8, n),
+                                None if flags_out is None else self._checked(flags_out, "flags_out", torch.uint8, n),
+                                None if info_out is None else self._checked(info_out, "info_out", torch.int32, n + (4,)))
+        done = self._mask(done)
+        if self._track_stale:
+            self.arm_agents_device()
+        rc = self._agents_fn(self._h, 0, self._track.data_ptr(), done.data_ptr(), *[None if t is None else t.data_ptr() for t in res],
+                             self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_agent_outcomes")
+        return res
+
+    def step_agents_device(self, actions, out=None):
+        """step_device(), every snake's outcome of that step, and the reset of the envs it finished, on one stream:
+        msnake_step -> msnake_agent_outcomes -> msnake_reset_envs(done).  Only on an env created with auto_reset=False.
+        Returns (obs, rew, done, info, agents): the first four are exactly what an auto_reset=True env returns from
+        step_device() (done envs show their reset observation), `agents` is the AgentOutcomes of
+        agent_outcomes_device() in tensors of the env's own.  Nothing is synchronised."""
+        if self._ctor["auto_reset"]:
+            raise ValueError("step_agents_device() needs an env created with auto_reset=False: the in-kernel auto reset "
+                             "overwrites the terminal state that the other snakes' outcomes are read from")
+        if self._track_stale:  # (before the step: the tracker holds the state the step starts from)
+            self.arm_agents_device()
+        obs, rew, done, info = self.step_device(actions, out)
+        agents = self.agent_outcomes_device(done)
+        rc = self._reset_envs_fn(self._h, self._p_done, obs.data_ptr(), None, None, self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_reset_envs")
+        return obs, rew, done, info, agents
+
     def rollout_device(self, tape, persistent=True, keep_obs=True):
         """T lockstep steps from an action tape int32 cuda [T, num_envs, >= n_snakes] in ONE call.
 
@@ -659,6 +745,7 @@ class MultiSnakeVecEnv:
         _capi.check(fn(self._h, tape.data_ptr(), int(tape.shape[2]), T, obs.data_ptr(), n * H * W * C if keep_obs else 0,
                        rew.data_ptr(), done.data_ptr(), info.data_ptr(), n, self._stream()),
                     "msnake_rollout_tape" if persistent else "msnake_step_tape")
+        self._track_stale = True
         return obs, rew, done, info
 
     def copy_envs_device(self, src, index=None):
@@ -691,6 +778,7 @@ class MultiSnakeVecEnv:
         rc = self._L.msnake_copy_envs(self._h, src._h, p_idx, self._cur_stream(self.device).cuda_stream)
         if rc < 0:
             _capi.check(rc, "msnake_copy_envs")
+        self._track_stale = True
 
     def clone(self, num_envs=None, **overrides):
         """A new MultiSnakeVecEnv with this env's configuration; `overrides` may change what a device-side copy lets
@@ -790,6 +878,7 @@ class MultiSnakeVecEnv:
 
     def set_state_words(self, env, words):
         w = np.ascontiguousarray(words, dtype=np.int32)
+        self._track_stale = True  # (also when the words are refused: arming once more is harmless)
         _capi.check(self._L.msnake_set_state(self._h, env, w.ctypes.data, len(w)), "msnake_set_state")
 
     def get_state_all(self):
@@ -801,6 +890,7 @@ class MultiSnakeVecEnv:
 
     def set_state_all(self, blob):
         b = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if not isinstance(blob, np.ndarray) else blob, dtype=np.uint8)
+        self._track_stale = True
         _capi.check(self._L.msnake_set_state_all(self._h, b.ctypes.data, b.nbytes), "msnake_set_state_all")
 
     @staticmethod

@@ -36,21 +36,27 @@ def main():
                     help="with --local-radius / --rays: windows / rays in board orientation and absolute actions (default: turned along the heading)")
     ap.add_argument("--rays", action="store_true",
                     help="train ray policies (an MLP) on each snake's eight-direction rays, 32 bytes per snake, instead of the frame")
+    ap.add_argument("--all-snakes", action="store_true",
+                    help="with --local-radius / --rays: the learner plays every snake and learns from every snake's transitions "
+                         "(per-snake rewards and deaths from the device), instead of from snake 0 against opponents")
     args = ap.parse_args()
     if args.rays and args.local_radius is not None:
         ap.error("--rays and --local-radius are mutually exclusive")
     if args.no_orient and args.local_radius is None and not args.rays:
         ap.error("--no-orient needs --local-radius or --rays")
+    if args.all_snakes and (args.local_radius is None and not args.rays or args.opponent != "pool"):
+        ap.error("--all-snakes needs --local-radius or --rays, and no --opponent")
     import torch
     from msnake import selfplay
 
+    # (--all-snakes: the step is followed by the per-snake outcomes and a masked reset, so the handle does not reset itself)
     env = msnake.MultiSnakeVecEnv(args.envs, dim=args.dim, n_snakes=args.snakes, rules=args.rules, seed=0,
-                                  obs_scale=args.scale)
+                                  obs_scale=args.scale, auto_reset=not args.all_snakes)
     selfplay.learn(env, nsteps=args.nsteps, total_timesteps=args.timesteps, csv_path=args.csv,
                    monitor_path=args.monitor, json_path=args.json, tb_dir=args.tensorboard,
                    amp_dtype=torch.bfloat16 if args.bf16 else None, save_dir=args.save, save_interval=args.save_interval,
                    load_path=args.load, resume=args.resume, local_radius=args.local_radius, oriented=not args.no_orient, rays=args.rays,
-                   scripted_opponents=None if args.opponent == "pool" else {s: args.opponent for s in range(1, args.snakes)})
+                   all_snakes=args.all_snakes, scripted_opponents=None if args.opponent == "pool" else {s: args.opponent for s in range(1, args.snakes)})
     print(env.stats())
     env.close()
 
