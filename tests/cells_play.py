@@ -9,6 +9,8 @@ A plain helper module like scripted_play / space_play; imported by tests/test_ce
 """
 import numpy as np
 
+import board_states as bs
+
 # the frame's colours (snake_multiple_test.py:35-58) -> the codes of the plane of the view they are drawn in
 COLOURS = {(0, 0, 0): 0, (255, 0, 0): 1, (0, 204, 0): 2, (191, 242, 191): 3, (0, 51, 204): 4, (128, 154, 230): 5}
 WALL = (255, 255, 255)
@@ -80,19 +82,18 @@ def oracle_rows(ora):
 def _paint_order_states(dim, ns, fruit_list):
     """States in which the paint order decides a cell: a head under a later snake's body, fruits under bodies and
     heads, every head on one cell, heads outside the grid, empty bodies, a body that covers the whole board."""
-    import test_scripted_gpu as tsg
     a, b, c, d = (0, 0), (1, 0), (dim - 1, dim - 1), (0, dim - 1)
     fr = lambda *cells: [cells[i % len(cells)] for i in range(fruit_list)]
     take = lambda bodies: [list(x) for x in bodies[:ns]] + [[]] * (ns - len(bodies[:ns]))
     out = [
-        tsg._st(take([[a], [b], [c, b, a, a], [d, c, a]]), fr(d)),        # heads of snakes 0 and 1 under the body of snake 2
-        tsg._st(take([[c, b, a, a], [d, c, a], [a], [b]]), fr(d)),        # ... and the later heads on top of an earlier body
-        tsg._st(take([[a, b], [c], [d], [b, a]]), fr(b, c, a, d)),        # fruits under a body and under heads
-        tsg._st(take([[a, b, b, b], [a], [a], [a, c]]), fr(a)),           # every head on one cell: the last snake's wins
-        tsg._st(take([[(-1, 0)], [(dim, dim - 1), c], [(0, -1), a], [(dim - 1, dim)]]), fr(a, c)),   # heads outside the grid
-        tsg._st(take([[], [], [], []]), fr(a, b, c, d)),                  # empty bodies: the fruits alone
-        tsg._st(take([[], [b, b], [], [a]]), fr(b)),
-        tsg._st(take([tsg._line(dim * dim, dim)[::-1], [c], [a, d], [b]]), fr(c, a)),   # a body on every cell of the board
+        bs.state(take([[a], [b], [c, b, a, a], [d, c, a]]), fr(d)),        # heads of snakes 0 and 1 under the body of snake 2
+        bs.state(take([[c, b, a, a], [d, c, a], [a], [b]]), fr(d)),        # ... and the later heads on top of an earlier body
+        bs.state(take([[a, b], [c], [d], [b, a]]), fr(b, c, a, d)),        # fruits under a body and under heads
+        bs.state(take([[a, b, b, b], [a], [a], [a, c]]), fr(a)),           # every head on one cell: the last snake's wins
+        bs.state(take([[(-1, 0)], [(dim, dim - 1), c], [(0, -1), a], [(dim - 1, dim)]]), fr(a, c)),   # heads outside the grid
+        bs.state(take([[], [], [], []]), fr(a, b, c, d)),                  # empty bodies: the fruits alone
+        bs.state(take([[], [b, b], [], [a]]), fr(b)),
+        bs.state(take([bs.line(dim * dim, dim)[::-1], [c], [a, d], [b]]), fr(c, a)),   # a body on every cell of the board
     ]
     return out
 
@@ -100,13 +101,12 @@ def _paint_order_states(dim, ns, fruit_list):
 def _table_states(dim, ns, fruit_list):
     """States that vary what only the table shows: each of the five velocities (none and the four directions) on every
     snake in turn, and grow_to below, at and above the body length."""
-    import test_scripted_gpu as tsg
     vels = [[0, 0], [1, 0], [0, 1], [-1, 0], [0, -1]]
     cells = [(0, 0), (1, 0), (dim - 1, dim - 1), (0, dim - 1)]
     out = []
     for k in range(5):
         bodies = [[cells[(s + k) % 4]] * (1 + (s + k) % 3) for s in range(ns)]
-        st = tsg._st(bodies, [cells[(k + i) % 4] for i in range(fruit_list)])
+        st = bs.state(bodies, [cells[(k + i) % 4] for i in range(fruit_list)])
         st["vels"] = [list(vels[(k + s) % 5]) for s in range(ns)]
         st["grow_to"] = [(1, len(bodies[s]), len(bodies[s]) + 3 + k, 1000)[(k + s) % 4] for s in range(ns)]
         out.append(st)
@@ -117,21 +117,17 @@ def snake_env_states(dim, ns=3):
     """Hand-built snake_env states: the border / random / dense builders of the scripted and space tests (border and
     corner heads, heads at -1 and dim, stacked duplicates, empty bodies; bodies over 64 cells at dim >= 19) plus the
     paint-order states."""
-    import test_scripted_gpu as tsg
-    import test_space_gpu as tspg
     rng = np.random.default_rng([11, dim])
-    states = tsg._border_states(dim, ns, ns, rng) + tsg._random_states(dim, ns, ns, rng, 20, dup=True)
-    states += tspg._dense_states(dim, ns, ns, rng, 12 if dim < 62 else 5)
+    states = bs.border_states(dim, ns, ns, rng) + bs.random_states(dim, ns, ns, rng, 20, dup=True)
+    states += bs.dense_states(dim, ns, ns, rng, 12 if dim < 62 else 5)
     return states + _table_states(dim, ns, ns) + _paint_order_states(dim, ns, ns)
 
 
 def new_world_states(dim, ns, nf):
     """new_world: every other state has dead snakes whose bodies are kept (alive False, in and out of dead_snakes)."""
-    import test_scripted_gpu as tsg
-    import test_space_gpu as tspg
     rng = np.random.default_rng([12, dim, ns, nf])
-    states = tsg._border_states(dim, ns, nf, rng)[::3] + tsg._random_states(dim, ns, nf, rng, 16, dup=True)
-    states += tspg._dense_states(dim, ns, nf, rng, 8) if ns > 1 else []
+    states = bs.border_states(dim, ns, nf, rng)[::3] + bs.random_states(dim, ns, nf, rng, 16, dup=True)
+    states += bs.dense_states(dim, ns, nf, rng, 8) if ns > 1 else []
     states += _table_states(dim, ns, nf) + _paint_order_states(dim, ns, nf)
     for k, st in enumerate(states[::2]):
         st["alive"] = [bool(rng.integers(0, 2)) for _ in range(ns)]
@@ -143,15 +139,13 @@ def new_world_states(dim, ns, nf):
 
 def adversarial_states(dim, ns):
     """adversarial: fruit lists of 0 .. the list's capacity entries (past 64: the strided part), entries at -1 / dim."""
-    import test_space_gpu as tspg
     rng = np.random.default_rng([13, dim, ns])
     fcap = (ns + ns * (dim * dim + 2) + 63) // 64 * 64           # the handle's fruit-list capacity
     states = []
     for n_list in (0, 1, 63, 64, 65, min(130, fcap - 3), fcap):
-        states += tspg._dense_states(dim, ns, n_list, rng, 3, fruit_lo=-1, fruit_hi=dim + 1) if ns > 1 else []
+        states += bs.dense_states(dim, ns, n_list, rng, 3, fruit_lo=-1, fruit_hi=dim + 1) if ns > 1 else []
         states += _paint_order_states(dim, ns, n_list)[:5]
     edge = [(-1, -1), (dim, dim), (-1, 3), (3, dim), (dim, 0), (0, -1)]
-    import test_scripted_gpu as tsg
-    states.append(tsg._st([[(2, 2)]] + [[]] * (ns - 1), edge * 12))    # 72 entries, every one outside the grid
+    states.append(bs.state([[(2, 2)]] + [[]] * (ns - 1), edge * 12))    # 72 entries, every one outside the grid
     states += _table_states(dim, ns, 3)
     return states

@@ -472,3 +472,20 @@ def turn_back(key):
     if nw:
         rows = [[0] + r[:ns - 1] for r in rows]
     return state_words(ns, fruits, snakes, t=5), rows
+
+
+# ------------------------------------------------------------------------------------------ canonical words, read and compared
+def blob_words(blob):
+    """Per-env canonical words of a get_state_all blob (layout: include/msnake.h)."""
+    b = np.ascontiguousarray(blob, dtype=np.uint8)
+    n = int(b[8:12].view(np.int32)[0])
+    offs = b[40:40 + 8 * (n + 1)].view(np.uint64).astype(np.int64)
+    w = b[40 + 8 * (n + 1):].view(np.int32)
+    assert offs[-1] == len(w)
+    return [w[offs[e]:offs[e + 1]].copy() for e in range(n)]
+
+
+def assert_words(got, want, what=None):
+    assert len(got) == len(want)
+    bad = [e for e, (g, w) in enumerate(zip(got, want)) if not np.array_equal(g, w)]
+    assert not bad, (what, bad[:8], got[bad[0]][:16], want[bad[0]][:16])

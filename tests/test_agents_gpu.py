@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 
 import agents_play as ap
+import gpu_harness as gh
 import scripted_play as sp
-import test_scripted_gpu as tsg   # its helpers (nothing of it is collected here)
 
 pytestmark = pytest.mark.gpu
 
@@ -22,49 +22,28 @@ GW = 3            # guard elements in front of and behind an int32 / float32 buf
 GB = 64           # guard bytes around a uint8 buffer
 IFILL, FFILL, BFILL = -7777, -77.5, 0xA5
 OUTPUTS = ("rew", "ate", "flags", "info")
-_mk = tsg._mk
+_mk = gh.make_env
 
 
 def _env(cfg, **kw):
     return _mk(cfg, **dict(dict(auto_reset=False), **kw))
 
 
-class Bufs:
+def Bufs(env):
     """The tracker and the four outputs of one handle, each between guards."""
+    n, S = env.num_envs, env.n_snakes
+    word = dict(guard=GW, align=16)
+    b = gh.GuardedOutputs(env.device, dict(track=dict(word, dtype="int32", shape=(n, S, 8), fill=IFILL),
+                                           rew=dict(word, dtype="float32", shape=(n, S), fill=FFILL),
+                                           ate=dict(dtype="uint8", shape=(n, S), fill=BFILL, guard=GB, align=4),
+                                           flags=dict(dtype="uint8", shape=(n, S), fill=BFILL, guard=GB, align=4),
+                                           info=dict(word, dtype="int32", shape=(n, S, 4), fill=IFILL)))
+    assert all(_ptr(b, k) % 16 == 12 for k in ("track", "rew", "info")) and _ptr(b, "ate") % 4 == 0 and _ptr(b, "flags") % 4 == 0
+    return b
 
-    def __init__(self, env):
-        import torch
-        n, S, dev = env.num_envs, env.n_snakes, env.device
-        self.n, self.S = n, S
-        spec = dict(track=(n * S * 8, torch.int32, IFILL, GW), rew=(n * S, torch.float32, FFILL, GW), ate=(n * S, torch.uint8, BFILL, GB),
-                    flags=(n * S, torch.uint8, BFILL, GB), info=(n * S * 4, torch.int32, IFILL, GW))
-        self.all, self.view, self.fill, self.guard = {}, {}, {}, {}
-        for k, (count, dtype, fill, g) in spec.items():
-            self.all[k] = torch.full((count + 2 * g,), fill, dtype=dtype, device=dev)
-            self.view[k] = self.all[k][g:g + count]
-            self.fill[k], self.guard[k] = fill, g
-            assert self.view[k].data_ptr() % 4 == 0 and (dtype == torch.uint8 or self.view[k].data_ptr() % 16 == 12)
-        self.shape = dict(track=(n, S, 8), rew=(n, S), ate=(n, S), flags=(n, S), info=(n, S, 4))
 
-    def ptr(self, k):
-        return self.view[k].data_ptr()
-
-    def refill(self, keys=OUTPUTS):
-        for k in keys:
-            self.all[k].fill_(self.fill[k])
-
-    def get(self, k):
-        return self.view[k].cpu().numpy().reshape(self.shape[k])
-
-    def untouched(self, k):
-        return bool((self.all[k] == self.fill[k]).all())
-
-    def guards_intact(self):
-        for k, a in self.all.items():
-            a, g = a.cpu().numpy(), self.guard[k]
-            if not ((a[:g] == self.fill[k]).all() and (a[-g:] == self.fill[k]).all()):
-                return False
-        return True
+def _ptr(b, k):
+    return getattr(b, k).data_ptr()
 
 
 def _raw(env, flags, track, done=None, rew=None, ate=None, flg=None, info=None):
@@ -75,12 +54,12 @@ def _raw(env, flags, track, done=None, rew=None, ate=None, flg=None, info=None):
 
 
 def _arm(env, b):
-    assert _raw(env, 1, b.ptr("track")) == 0
+    assert _raw(env, 1, _ptr(b, "track")) == 0
 
 
 def _outcomes(env, b, done, which=OUTPUTS):
     key = dict(rew="rew", ate="ate", flg="flags", info="info")
-    assert _raw(env, 0, b.ptr("track"), done.data_ptr(), **{a: (b.ptr(k) if k in which else None) for a, k in key.items()}) == 0
+    assert _raw(env, 0, _ptr(b, "track"), done.data_ptr(), **{a: (_ptr(b, k) if k in which else None) for a, k in key.items()}) == 0
 
 
 def _same(got, want, what):
@@ -94,10 +73,10 @@ def _same(got, want, what):
 def _check_outputs(b, tw, what, which=OUTPUTS):
     for k in OUTPUTS:
         if k in which:
-            _same(b.get(k), getattr(tw, k), (what, k))
+            _same(b.host(k), getattr(tw, k), (what, k))
         else:
             assert b.untouched(k), (what, k, "was written")
-    _same(b.get("track"), tw.track, (what, "track"))
+    _same(b.host("track"), tw.track, (what, "track"))
     assert b.guards_intact(), what
 
 
@@ -112,19 +91,19 @@ def _loop(cfg, steps, env=None, which=OUTPUTS, obs_every=20, tw=None, b=None, cl
     if fresh:
         _same(env.reset(), tw.obs, "reset obs")
         _arm(env, b)
-        _same(b.get("track"), tw.track, "armed track")
+        _same(b.host("track"), tw.track, "armed track")
     ev = dict(done=0, died_other=0, ate_other=0, ended_alive=0)
     for t in range(steps):
         act = tw.step()
         obs, rew, done, info = env.step_device(torch.from_numpy(act).to(env.device))
-        b.refill()
+        b.refill(OUTPUTS)
         _outcomes(env, b, done, which)
         env.reset_device(mask=done)
         _same(done.cpu().numpy(), tw.done, (t, "done"))
         _same(rew.cpu().numpy(), tw.step_rew, (t, "step rew"))
         _check_outputs(b, tw, t, which)
         if "rew" in which:
-            _same(b.get("rew")[:, 0], rew.cpu().numpy(), (t, "column 0 is the step's reward"))
+            _same(b.host("rew")[:, 0], rew.cpu().numpy(), (t, "column 0 is the step's reward"))
         if t % obs_every == 0 or t == steps - 1:
             _same(obs.cpu().numpy(), tw.obs, (t, "obs"))
         died = (tw.flags & ap.DIED) != 0
@@ -189,14 +168,14 @@ def test_arm_after_a_persistent_rollout_tape():
     tw.states = [tw.read(e) for e in range(tw.E)]
     b = Bufs(env)
     _arm(env, b)
-    _same(b.get("track"), tw.track, "armed behind the tape")
+    _same(b.host("track"), tw.track, "armed behind the tape")
     fin = np.array([tw.ora.finished(e) for e in range(tw.E)], np.uint8)
     assert fin.any() and not fin.all()
     tw.ora.reset_envs(fin, final_obs=None, truncated=None)
     env.reset_device(mask=torch.from_numpy(fin).to(env.device))
     tw.states = [tw.read(e) for e in range(tw.E)]
     _arm(env, b)
-    _same(b.get("track"), tw.track, "armed behind the masked reset")
+    _same(b.host("track"), tw.track, "armed behind the masked reset")
     assert b.guards_intact()
     _loop(cfg, 15, env=env, tw=tw, b=b)
 
@@ -209,10 +188,10 @@ def test_arm_writes_the_facts_and_zero_totals_whatever_the_tracker_held():
     _same(env.reset(), tw.obs, "reset obs")
     _arm(env, b)
     _loop(cfg, 30, env=env, tw=tw, b=b, close=False)   # (totals are running now)
-    assert (b.get("track")[:, :, 2:7] != 0).any()
+    assert (b.host("track")[:, :, 2:7] != 0).any()
     _arm(env, b)
     want = np.stack([ap.track_rows(st, cfg["rules"], ap.zero_totals(4)) for st in tw.states])
-    _same(b.get("track"), want, "re-armed")
+    _same(b.host("track"), want, "re-armed")
     assert (want[:, :, ap.TR_ALIVE] == 0).any(), "some new_world snake is not alive: the alive bit is what is read"
     assert b.guards_intact()
     env.close()
@@ -235,7 +214,7 @@ def test_done_rows_equal_an_armed_tracker_after_reset_envs():
         env.reset_device(mask=done)
         _arm(env, b2)
         d = tw.done != 0
-        got, armed = b.get("track"), b2.get("track")
+        got, armed = b.host("track"), b2.host("track")
         _same(got[d], armed[d], (t, "done rows"))
         _same(got[d][:, :, :2], np.broadcast_to([3, 1], got[d][:, :, :2].shape), (t, "grow_to 3, alive"))
         _same(got[~d][:, :, :2], armed[~d][:, :, :2], (t, "facts of the others"))
@@ -257,7 +236,7 @@ def test_each_output_alone_gives_the_bytes_of_all_together():
         act = tw.step()
         for e, b, which in zip(envs, bufs, [OUTPUTS] + [(k,) for k in OUTPUTS]):
             _, _, done, _ = e.step_device(torch.from_numpy(act).to(e.device))
-            b.refill()
+            b.refill(OUTPUTS)
             _outcomes(e, b, done, which)
             e.reset_device(mask=done)
             _check_outputs(b, tw, (t, which), which)
@@ -283,7 +262,7 @@ def test_ate_clamps_at_255_and_rew_does_not():
     env._L.msnake_set_state(env._h, 1, words.ctypes.data, len(words))   # (the bare call: the arming below is the test's own)
     tw.states[1] = tw.read(1)
     _arm(env, b)
-    _same(b.get("track"), tw.track, "armed")
+    _same(b.host("track"), tw.track, "armed")
     act = tw.step(np.array([[0, 0, 0], [1, 1, 0]], np.int32))
     _, rew, done, _ = env.step_device(torch.from_numpy(act).to(env.device))
     _outcomes(env, b, done)
@@ -396,7 +375,7 @@ def test_graph_of_step_outcomes_reset_envs_replayed_50_times():
     dones = 0
     for t in range(K):
         acts.copy_(torch.from_numpy(tw.step()))
-        b.refill()
+        b.refill(OUTPUTS)
         g.replay()
         _same(env._done.cpu().numpy(), tw.done, (t, "done"))
         _same(env._rew.cpu().numpy(), tw.step_rew, (t, "step rew"))
@@ -450,7 +429,7 @@ def test_every_refusal():
     b = Bufs(env)
     env.reset()
     done = torch.zeros(5, dtype=torch.uint8, device=env.device)
-    T, D, R, A, F, I = b.ptr("track"), done.data_ptr(), b.ptr("rew"), b.ptr("ate"), b.ptr("flags"), b.ptr("info")
+    T, D, R, A, F, I = _ptr(b, "track"), done.data_ptr(), _ptr(b, "rew"), _ptr(b, "ate"), _ptr(b, "flags"), _ptr(b, "info")
     last = lambda: env._L.msnake_last_error().decode()
     for flags in (2, 3, 4, -1, 1 << 31 - 1):
         assert _raw(env, flags, T, D, R) == E["ARG"] and "flags" in last(), flags
@@ -478,7 +457,7 @@ def test_every_refusal():
     _arm(env, b)
     assert _raw(env, 0, T, D, None, A + 1, F + 3) == 0, "the byte outputs need no alignment"
     torch.cuda.synchronize()
-    assert b.untouched("rew") and b.untouched("info") and (b.all["ate"][GB + 1:GB + 16] == 0).all()
+    assert b.untouched("rew") and b.untouched("info") and (torch.as_strided(b.ate, (15,), (1,), b.ate.storage_offset() + 1) == 0).all()
     # the wrapper's own checks
     with pytest.raises(ValueError, match="rew_out"):
         env.agent_outcomes_device(done, rew_out=torch.zeros((5, 3), dtype=torch.float64, device=env.device))

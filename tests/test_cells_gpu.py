@@ -12,50 +12,20 @@ import numpy as np
 import pytest
 
 import cells_play as cp
+import gpu_harness as gh
 import scripted_play as sp
-import test_scripted_gpu as tsg   # its state builders (helpers only: nothing of it is collected here)
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
-FILL = 0xA5
-FILL32 = int(np.array([0xA5A5A5A5], np.uint32).view(np.int32)[0])
-_mk = tsg._mk
+_mk = gh.make_env
 
 
-class Guarded:
-    """A uint8 [n, V, dim, dim] plane buffer that starts `offset` bytes behind its 64 guard bytes and an int32 [n, ns, 8]
-    table between 64 guard words, all filled with 0xA5."""
-
-    def __init__(self, env, n_planes, offset=0):
-        import torch
-        n, dim = env.num_envs, env.cells_shape[1]
-        self.size, self.lo = n * n_planes * dim * dim, GUARD + offset
-        self.c_all = torch.full((self.lo + self.size + GUARD + 3,), FILL, dtype=torch.uint8, device=env.device)
-        assert self.c_all.data_ptr() % 4 == 0
-        self.cells = self.c_all[self.lo:self.lo + self.size].view(n, n_planes, dim, dim) if n_planes else None
-        self.t_all = torch.full((n * env.n_snakes * 8 + 2 * GUARD,), FILL32, dtype=torch.int32, device=env.device)
-        self.table = self.t_all[GUARD:-GUARD].view(n, env.n_snakes, 8)
-
-    def refill(self):
-        self.c_all.fill_(FILL), self.t_all.fill_(FILL32)
-
-    def planes(self):
-        return self.c_all.cpu().numpy()[self.lo:self.lo + self.size].reshape(tuple(self.cells.shape))
-
-    def rows(self):
-        return self.t_all.cpu().numpy()[GUARD:-GUARD].reshape(tuple(self.table.shape))
-
-    def guards_intact(self):
-        c, t = self.c_all.cpu().numpy(), self.t_all.cpu().numpy()
-        return ((c[:self.lo] == FILL).all() and (c[self.lo + self.size:] == FILL).all() and
-                (t[:GUARD] == FILL32).all() and (t[-GUARD:] == FILL32).all())
-
-    def cells_untouched(self):
-        return (self.c_all.cpu().numpy() == FILL).all()
-
-    def table_untouched(self):
-        return (self.t_all.cpu().numpy() == FILL32).all()
+def Guarded(env, n_planes, offset=0):
+    """A uint8 [n, V, dim, dim] plane buffer `cells` that starts `offset` bytes behind its 64 guard bytes (3 more bytes
+    of slack behind the back guard) and an int32 [n, ns, 8] `table` between 64 guard words, all filled with 0xA5."""
+    n, dim = env.num_envs, env.cells_shape[1]
+    return gh.GuardedOutputs(env.device, {"cells": dict(dtype="uint8", shape=(n, n_planes, dim, dim), fill=0xA5, offset=offset, align=4, slack=3),
+                                          "table": dict(dtype="int32", shape=(n, env.n_snakes, 8), fill=0xA5A5A5A5)})
 
 
 def _n_views(env):
@@ -76,32 +46,22 @@ def _check(env, ora, frames=None, views=None, buf=None, offset=0, table=True, wh
     want = cp.decode_frame(ora.render() if frames is None else frames, sel)
     res = env.render_cells_device(views=views, out=buf.cells, snakes_out=buf.table if table else None)
     assert (res[0] is buf.cells and res[1] is buf.table) if table else res is buf.cells
-    got = buf.planes()
+    got = buf.host("cells")
     bad = np.argwhere(got != want)
     assert bad.size == 0, (what, "cells", bad[:5].tolist(), got[bad[0][0]].tolist(), want[bad[0][0]].tolist())
     if table:
-        got_r, want_r = buf.rows(), _want_rows(ora)
+        got_r, want_r = buf.host("table"), _want_rows(ora)
         bad = np.argwhere(got_r != want_r)
         assert bad.size == 0, (what, "table", bad[:5].tolist(), got_r[bad[0][0]].tolist(), want_r[bad[0][0]].tolist())
     else:
-        assert buf.table_untouched(), what
+        assert buf.untouched("table"), what
     assert buf.guards_intact(), what
     return buf
 
 
 def _install(cfg, states, **kw):
     """The same state dicts into a fresh handle (set_state_words) and a fresh oracle (Oracle.set_state)."""
-    from oracle.snake_oracle import flat_to_state, state_to_flat
-    cfg = dict(cfg, num_envs=len(states), seed=1, env_id_base=0, max_steps=2000)
-    env, ora = _mk(cfg, **kw), sp.make_oracle(cfg)
-    env.reset(), ora.reset()
-    for e, st in enumerate(states):
-        env.set_state_words(e, state_to_flat(st, cfg["n_snakes"]))
-        ora.set_state(e, st)
-    for e in (0, len(states) - 1):   # the state went in as it was built
-        got = flat_to_state(env.get_state_words(e))
-        assert got["snakes"] == states[e]["snakes"] and got["fruits"] == states[e]["fruits"]
-    return env, ora
+    return gh.install(cfg, states, with_oracle=True, **kw)
 
 
 def _ragged(states):
@@ -121,7 +81,7 @@ def test_hand_built_snake_env_states(dim):
     env, ora = _install(dict(rules=0, dim=dim, n_snakes=3, n_fruits=3), states)
     buf = _check(env, ora, what=("snake_env", dim))
     first = len(states) - 8                                 # the first paint-order state, stated without the helper
-    assert buf.planes()[first, :, 0, 0].tolist() == [4, 4, 2] and buf.rows()[first, 0, :3].tolist() == [1, 0, 0]
+    assert buf.host("cells")[first, :, 0, 0].tolist() == [4, 4, 2] and buf.host("table")[first, 0, :3].tolist() == [1, 0, 0]
     env.close()
 
 
@@ -136,7 +96,7 @@ def test_hand_built_new_world_states(dim, ns, nf):
     env, ora = _install(dict(rules=1, dim=dim, n_snakes=ns, n_fruits=nf), states)
     assert env.cells_shape[0] == ns
     buf = _check(env, ora, what=("new_world", dim, ns, nf))
-    rows, planes = buf.rows(), buf.planes()
+    rows, planes = buf.host("table"), buf.host("cells")
     for e, st in enumerate(states):                         # the dead keep their rows; a board of the dead alone shows no snake
         assert rows[e, :, 6].tolist() == [int(a) for a in st["alive"]] and rows[e, :, 0].tolist() == [len(b) for b in st["snakes"]]
         if not any(st["alive"]):
@@ -165,7 +125,7 @@ def test_hand_built_adversarial_states(dim, ns):
     assert env.cells_shape[0] == 3
     buf = _check(env, ora, what=("adversarial", dim, ns))
     if ns == 2:
-        last = buf.planes()[:, 2]
+        last = buf.host("cells")[:, 2]
         assert not ((last == 2) | (last == 3)).any() and (last == 5).any()
     env.close()
 
@@ -185,7 +145,7 @@ def test_every_view_mask_table_only_and_cells_only(rules, dim, ns, nf):
     # the table alone: no plane byte is written
     buf = Guarded(env, 1)
     res = env.render_cells_device(views=[], snakes_out=buf.table)
-    assert res is buf.table and np.array_equal(buf.rows(), _want_rows(ora)) and buf.cells_untouched() and buf.guards_intact()
+    assert res is buf.table and np.array_equal(buf.host("table"), _want_rows(ora)) and buf.untouched("cells") and buf.guards_intact()
     # fresh tensors of the env's own
     cells, table = env.render_cells_device(snakes=True)
     assert tuple(cells.shape) == (len(states),) + env.cells_shape and tuple(table.shape) == (len(states), ns, 8)
@@ -256,7 +216,7 @@ def test_the_call_changes_no_state():
     snap = saved = None
     resets = 0
     for t in range(30):
-        states = tsg._states(ora)
+        states = gh.oracle_states(ora)
         before, st_before = env.get_state_all().tobytes(), env.stats()
         buf.refill()
         _check(env, ora, buf=buf, what=("before", t))
@@ -321,8 +281,8 @@ def test_graph_of_step_then_render_cells():
         torch.cuda.synchronize()
         o_obs, o_rew, o_done, *_ = ora.step(act)
         assert np.array_equal(out[1].cpu().numpy(), o_rew) and np.array_equal(out[2].cpu().numpy(), o_done), k
-        assert np.array_equal(buf.planes(), cp.decode_frame(o_obs, [0, 1, 2])), k
-        assert np.array_equal(buf.rows(), _want_rows(ora)), k
+        assert np.array_equal(buf.host("cells"), cp.decode_frame(o_obs, [0, 1, 2])), k
+        assert np.array_equal(buf.host("table"), _want_rows(ora)), k
         assert buf.guards_intact(), k
     env.close()
 
@@ -362,7 +322,7 @@ def test_argument_errors_leave_the_outputs_untouched():
         rc, msg = call(*args)
         assert rc == -3 and "handle" in msg, (args[1:], rc, msg)   # MSNAKE_E_HANDLE, before any argument check
     torch.cuda.synchronize()
-    assert buf.cells_untouched() and buf.table_untouched()
+    assert buf.untouched("cells") and buf.untouched("table")
     # the wrapper's own refusals, before the library is asked
     for kw in (dict(out=buf.cells[:, :2]), dict(out=buf.cells.to(torch.int8)), dict(views=[0], out=buf.cells),
                dict(snakes_out=buf.table[:, :1]), dict(snakes_out=buf.table.to(torch.int64)), dict(views=[]),
@@ -370,7 +330,7 @@ def test_argument_errors_leave_the_outputs_untouched():
         with pytest.raises(ValueError):
             env.render_cells_device(**kw)
     torch.cuda.synchronize()
-    assert buf.cells_untouched() and buf.table_untouched()
+    assert buf.untouched("cells") and buf.untouched("table")
     # what is NOT an error: an unaligned cells_dev, and each output alone
     assert call(env._h, 0b010, pc + 1, None)[0] == 0 and call(env._h, 0, None, pt)[0] == 0 and call(env._h, 0b111, pc, None)[0] == 0
     torch.cuda.synchronize()

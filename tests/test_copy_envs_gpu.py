@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import scripted_play as sp
+from state_domain import assert_words, blob_words, export as ora_words
 
 pytestmark = pytest.mark.gpu
 
@@ -23,16 +24,6 @@ ORACLE_KW = ("seed", "env_id_base", "max_steps", "auto_reset")
 
 
 # ------------------------------------------------------------------------------------------ helpers
-def blob_words(blob):
-    """Per-env canonical words of a get_state_all blob (layout: include/msnake.h)."""
-    b = np.ascontiguousarray(blob, dtype=np.uint8)
-    n = int(b[8:12].view(np.int32)[0])
-    offs = b[40:40 + 8 * (n + 1)].view(np.uint64).astype(np.int64)
-    w = b[40 + 8 * (n + 1):].view(np.int32)
-    assert offs[-1] == len(w)
-    return [w[offs[e]:offs[e + 1]].copy() for e in range(n)]
-
-
 class Pair:
     """A MultiSnakeVecEnv and the oracle of the same configuration, stepped together and compared in everything."""
 
@@ -86,16 +77,6 @@ class Pair:
         self.env.close()
 
 
-def ora_words(ora, i):
-    """orc_export_state plus the oracle's `finished` bit where the product's words carry it (bit 8 of word 7)."""
-    n = ora.L.orc_export_state(ora.h, i, None, 0)
-    buf = np.zeros(n, np.int32)
-    ora.L.orc_export_state(ora.h, i, buf.ctypes.data, n)
-    if ora.finished(i):
-        buf[7] |= 0x100
-    return buf
-
-
 def ora_copy(o_dst, o_src, idx):
     """orc_dst.set_state(e, orc_src.get_state(idx[e])) for every selected e; all sources are read first."""
     idx = range(o_dst.num_envs) if idx is None else [int(i) for i in idx]
@@ -108,12 +89,6 @@ def ora_copy(o_dst, o_src, idx):
 def expected_words(src_before, dst_before, idx):
     idx = range(len(dst_before)) if idx is None else idx
     return [src_before[i] if 0 <= i < len(src_before) else dst_before[e] for e, i in enumerate(idx)]
-
-
-def assert_words(got, want, what=None):
-    assert len(got) == len(want)
-    bad = [e for e, (g, w) in enumerate(zip(got, want)) if not np.array_equal(g, w)]
-    assert not bad, (what, bad[:8], got[bad[0]][:16], want[bad[0]][:16])
 
 
 def copy_both(dst, src, idx, what=None, via="numpy"):

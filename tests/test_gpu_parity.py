@@ -4,6 +4,7 @@ this is integer / byte work, there is no tolerance anywhere."""
 import numpy as np
 import pytest
 
+from board_states import serpentine_body
 from golden_util import blob_to_obs, crc_rows, edge_cases, load_tape, state_view, tape_names, unpack_state
 
 pytestmark = pytest.mark.gpu
@@ -429,17 +430,6 @@ def test_vecenv_surface_like_the_reference_runner_uses_it():
         e2.close()
 
 
-def _serpentine(dim, length, start_row, rs):
-    """A self-avoiding boustrophedon body of `length` cells starting in row `start_row` (head last
-    visited, i.e. head first in the list), so bodies far longer than one 64-cell chunk are legal."""
-    path = []
-    for r in range(start_row, dim):
-        cols = range(dim) if (r - start_row) % 2 == 0 else range(dim - 1, -1, -1)
-        path += [[c, r] for c in cols]
-    path = path[:length]
-    return path[::-1]
-
-
 @pytest.mark.parametrize("rules", ["snake_env", "new_world", "adversarial"])
 def test_fuzz_long_bodies_against_oracle(rules):
     """Hand-built states with bodies of 50..250 cells (up to 4 chunks of 64): the ring path of the
@@ -453,8 +443,8 @@ def test_fuzz_long_bodies_against_oracle(rules):
     env.reset(); ora.reset()
     for e in range(n):
         la, lb = int(rs.integers(50, 250)), int(rs.integers(1, 60))
-        a = _serpentine(dim, la, 0, rs)
-        b = _serpentine(dim, lb, 15, rs)
+        a = serpentine_body(dim, la, 0)
+        b = serpentine_body(dim, lb, 15)
         # head of a is at the end of its last (partial) row, moving along that row
         hr = a[0][1]
         va = [1, 0] if (hr % 2 == 0) else [-1, 0]

@@ -11,53 +11,24 @@ import ctypes
 import numpy as np
 import pytest
 
+import board_states as bs
 import cells_play as cp
+import gpu_harness as gh
 import local_play as lp
 import scripted_play as sp
-import test_scripted_gpu as tsg   # its state builders (helpers only: nothing of it is collected here)
-import test_space_gpu as tspg
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
-FILL = 0xA5
 RADII = (1, 2, 5, 31)
-_mk = tsg._mk
+_mk, _install = gh.make_env, gh.install
 
 
-class Guarded:
-    """A uint8 [n, S, W, W] window buffer that starts `offset` bytes behind its 64 guard bytes and a uint8 [n, S] heading
-    buffer between 64 guard bytes, all filled with 0xA5."""
-
-    def __init__(self, env, n_sel, radius, offset=0):
-        import torch
-        n, w = env.num_envs, 2 * radius + 1
-        self.size, self.lo = n * n_sel * w * w, GUARD + offset
-        self.w_all = torch.full((self.lo + self.size + GUARD + 3,), FILL, dtype=torch.uint8, device=env.device)
-        assert self.w_all.data_ptr() % 4 == 0
-        self.win = self.w_all[self.lo:self.lo + self.size].view(n, n_sel, w, w)
-        self.h_all = torch.full((n * n_sel + 2 * GUARD,), FILL, dtype=torch.uint8, device=env.device)
-        self.head = self.h_all[GUARD:GUARD + n * n_sel].view(n, n_sel)
-
-    def refill(self):
-        self.w_all.fill_(FILL), self.h_all.fill_(FILL)
-
-    def windows(self):
-        return self.w_all.cpu().numpy()[self.lo:self.lo + self.size].reshape(tuple(self.win.shape))
-
-    def headings(self):
-        return self.h_all.cpu().numpy()[GUARD:-GUARD].reshape(tuple(self.head.shape))
-
-    def guards_intact(self):
-        w, h = self.w_all.cpu().numpy(), self.h_all.cpu().numpy()
-        return ((w[:self.lo] == FILL).all() and (w[self.lo + self.size:] == FILL).all() and
-                (h[:GUARD] == FILL).all() and (h[-GUARD:] == FILL).all())
-
-    def windows_untouched(self):
-        return (self.w_all.cpu().numpy() == FILL).all()
-
-    def headings_untouched(self):
-        return (self.h_all.cpu().numpy() == FILL).all()
+def Guarded(env, n_sel, radius, offset=0):
+    """A uint8 [n, S, W, W] window buffer `win` that starts `offset` bytes behind its 64 guard bytes (3 more bytes of
+    slack behind the back guard) and a uint8 [n, S] heading buffer `head` between 64 guard bytes, all filled with 0xA5."""
+    n, w = env.num_envs, 2 * radius + 1
+    return gh.GuardedOutputs(env.device, {"win": dict(dtype="uint8", shape=(n, n_sel, w, w), fill=0xA5, offset=offset, align=4, slack=3),
+                                          "head": dict(dtype="uint8", shape=(n, n_sel), fill=0xA5)})
 
 
 def _check(env, states, radius, snakes=None, oriented=True, offset=0, heading=True, planes=None, buf=None, what=""):
@@ -69,31 +40,16 @@ def _check(env, states, radius, snakes=None, oriented=True, offset=0, heading=Tr
     want_w, want_h = lp.np_local_all(states, dim, ns, rules, sel, radius, oriented, planes=planes)
     res = env.render_local_device(radius, snakes=snakes, oriented=oriented, out=buf.win, heading_out=buf.head if heading else None)
     assert (res[0] is buf.win and res[1] is buf.head) if heading else res is buf.win
-    got = buf.windows()
+    got = buf.host("win")
     bad = np.argwhere(got != want_w)
     assert bad.size == 0, (what, "windows", bad[:5].tolist(), got[tuple(bad[0][:2])].tolist(), want_w[tuple(bad[0][:2])].tolist())
     if heading:
-        got_h = buf.headings()
+        got_h = buf.host("head")
         assert np.array_equal(got_h, want_h), (what, "heading", np.argwhere(got_h != want_h)[:5].tolist())
     else:
-        assert buf.headings_untouched(), what
+        assert buf.untouched("head"), what
     assert buf.guards_intact(), what
     return buf
-
-
-def _install(cfg, states, **kw):
-    """The state dicts into a fresh handle (set_state_words); read back, they are what was built, velocities included."""
-    from oracle.snake_oracle import flat_to_state, state_to_flat
-    cfg = dict(cfg, num_envs=len(states), seed=1, env_id_base=0, max_steps=2000)
-    env = _mk(cfg, **kw)
-    env.reset()
-    for e, st in enumerate(states):
-        env.set_state_words(e, state_to_flat(st, cfg["n_snakes"]))
-    for e in (0, len(states) // 2, len(states) - 1):
-        got = flat_to_state(env.get_state_words(e))
-        assert got["snakes"] == states[e]["snakes"] and got["fruits"] == states[e]["fruits"]
-        assert [list(v) for v in got["vels"]] == [list(v) for v in states[e]["vels"]]
-    return env
 
 
 def _ragged(states):
@@ -113,7 +69,7 @@ def _all_radii(env, states, radii=RADII, what=""):
 def test_hand_built_snake_env_states(dim):
     """Border and corner heads, heads at -1 / dim (the centre of the window is 6), stacked duplicates, dense boards, empty
     bodies, every velocity on every kind of body; windows smaller and larger than the board."""
-    states = cp.snake_env_states(dim) + [tsg._st([[], [], []], [(0, 0), (dim - 1, 0), (1, 1)])]
+    states = cp.snake_env_states(dim) + [bs.state([[], [], []], [(0, 0), (dim - 1, 0), (1, 1)])]
     states = lp.deal_velocities(_ragged(states), 3)
     shares = lp.heading_shares(states, 3)
     assert min(shares) >= 1 / 8, shares
@@ -155,7 +111,7 @@ def test_hand_built_adversarial_states(dim):
 @pytest.mark.parametrize("dim", [19, 20])
 def test_pieces_in_the_overflow_ring_inside_the_window(dim):
     """Bodies over 64 cells whose pieces >= 64 lie next to the head: they show in the radius-5 window."""
-    states, _ = tspg._overflow_states(dim, 3)
+    states, _ = bs.overflow_states(dim, 3)
     states = lp.deal_velocities(_ragged(states), 3, start=1)
     near = 0
     for st in states:
@@ -186,17 +142,17 @@ def test_closed_loop_with_the_oracle_as_master(name, steps):
     buf = Guarded(env, ns, 5, offset=1)
     seen = set()
     for t in range(steps):
-        act = sp.choose_actions(cfg, tsg._states(ora), rs)
+        act = sp.choose_actions(cfg, gh.oracle_states(ora), rs)
         _, rew, done, _ = env.step_device(torch.from_numpy(act).to(env.device))
         o_obs, o_rew, o_done, *_ = ora.step(act)
         assert np.array_equal(rew.cpu().numpy(), o_rew) and np.array_equal(done.cpu().numpy(), o_done), t
-        states = tsg._states(ora)
+        states = gh.oracle_states(ora)
         buf.refill()
         _check(env, states, 5, buf=buf, what=(name, t))
-        seen |= set(buf.headings().ravel().tolist())
+        seen |= set(buf.host("head").ravel().tolist())
         if t % 10 == 0 or t == steps - 1:
             want = lp.windows_from_planes(cp.decode_frame(o_obs, list(range(ns))), states, list(range(ns)), 5, True)
-            assert np.array_equal(buf.windows(), want), (name, t, "frame")
+            assert np.array_equal(buf.host("win"), want), (name, t, "frame")
     assert seen == {0, 1, 2, 3} and env.stats()["errors"] == 0
     env.close()
 
@@ -247,8 +203,8 @@ def test_batch_sizes_record_policies_and_envs_per_block(n, record_policy):
         cfg = dict(rules=0, dim=19, n_snakes=3, n_fruits=3, num_envs=n, seed=6 + epb, env_id_base=2, max_steps=2000)
         env, ora = _mk(cfg, record_policy=record_policy, envs_per_block=epb), sp.make_oracle(cfg)
         assert np.array_equal(env.reset(), ora.reset())
-        tsg._play_random(env, ora, 12, np.random.default_rng(epb))
-        states = tsg._states(ora)
+        gh.play_random(env, ora, 12, np.random.default_rng(epb))
+        states = gh.oracle_states(ora)
         _check(env, states, 5, what=(n, record_policy, epb))
         _check(env, states, 2, snakes=[0, 2], oriented=False, offset=3, what=(n, record_policy, epb, "r2"))
         env.close()
@@ -314,9 +270,9 @@ def test_graph_of_step_then_render_local():
         if k % 20 == 19:
             assert np.array_equal(out[1].cpu().numpy(), o_rew) and np.array_equal(out[2].cpu().numpy(), o_done), k
     torch.cuda.synchronize()
-    states = tsg._states(ora)
+    states = gh.oracle_states(ora)
     want_w, want_h = lp.np_local_all(states, 19, ns, 0, range(ns), 5, True)
-    assert np.array_equal(buf.windows(), want_w) and np.array_equal(buf.headings(), want_h) and buf.guards_intact()
+    assert np.array_equal(buf.host("win"), want_w) and np.array_equal(buf.host("head"), want_h) and buf.guards_intact()
     for e in range(n):
         got = flat_to_state(env.get_state_words(e))
         for key in ("snakes", "fruits", "vels", "t"):
@@ -351,7 +307,7 @@ def test_argument_errors_leave_the_outputs_untouched():
         rc, msg = call(dead, *args)
         assert rc == -3 and "handle" in msg, (args, rc, msg)                       # before any argument check
     torch.cuda.synchronize()
-    assert buf.windows_untouched() and buf.headings_untouched()
+    assert buf.untouched("win") and buf.untouched("head")
     # the wrapper's own refusals, before the library is asked
     for kw in (dict(radius=0), dict(radius=32), dict(radius=2.5), dict(snakes=[]), dict(snakes=[2]), dict(snakes=[1, 0]),
                dict(oriented=2), dict(oriented=None), dict(out=buf.win[:, :1]), dict(out=buf.win.to(torch.int8)),
@@ -363,7 +319,7 @@ def test_argument_errors_leave_the_outputs_untouched():
         name = {"snakes": "snake"}.get(next(iter(kw)), next(iter(kw)))     # (the argument the message must name)
         assert name in str(err.value), (kw, str(err.value))
     torch.cuda.synchronize()
-    assert buf.windows_untouched() and buf.headings_untouched()
+    assert buf.untouched("win") and buf.untouched("head")
     # what is NOT an error: an unaligned windows_dev, heading_dev NULL, fresh tensors of the env's own
     assert call(env._h, 5, 0b10, 0, pw + 1, None)[0] == 0 and call(env._h, 1, 0b11, 1, pw, ph)[0] == 0
     win, head = env.render_local_device(1, heading=True)

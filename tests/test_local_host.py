@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import cells_play as cp
+from fake_envs import FakeEnv, FakeLocalEnv as _FakeLocalEnv
 import local_play as lp
 import msnake
 import scripted_play as sp
@@ -254,39 +255,6 @@ def test_weights_of_the_other_kind_are_refused(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------ the driver
-class _FakeLocalEnv:
-    """CPU stand-in with the device-side surface learn(local_radius=...) uses: frames nobody looks at, seeded windows and
-    headings through render_local_device, and a record of every call."""
-
-    def __init__(self, n=8, n_snakes=3, seed=0):
-        self.num_envs, self.n_snakes, self.obs_shape, self.device = n, n_snakes, (12, 12, 9), torch.device("cpu")
-        self.g = torch.Generator().manual_seed(seed)
-        self.renders, self.actions = [], []
-
-    def reset_device(self):
-        return torch.zeros((self.num_envs,) + self.obs_shape, dtype=torch.uint8)
-
-    def local_shape(self, radius, snakes=None):
-        return msnake.MultiSnakeVecEnv.local_shape(self, radius, snakes)
-
-    def render_local_device(self, radius, snakes=None, oriented=True, out=None, heading_out=None):
-        assert tuple(out.shape) == (self.num_envs,) + self.local_shape(radius, snakes) and out.dtype == torch.uint8
-        assert tuple(heading_out.shape) == tuple(out.shape[:2]) and heading_out.dtype == torch.uint8
-        out.copy_(torch.randint(0, 7, out.shape, dtype=torch.uint8, generator=self.g))
-        heading_out.copy_(torch.randint(0, 4, heading_out.shape, dtype=torch.uint8, generator=self.g))
-        self.renders.append((radius, list(snakes), bool(oriented)))
-        return out, heading_out
-
-    def step_device(self, actions):
-        assert actions.shape == (self.num_envs, self.n_snakes) and actions.dtype == torch.int32
-        assert int(actions.min()) >= 0 and int(actions.max()) <= 4
-        self.actions.append(actions.clone())
-        done = torch.rand(self.num_envs, generator=self.g) < 0.3
-        info = torch.zeros((self.num_envs, 4), dtype=torch.int32)
-        info[:, 0] = torch.full((self.num_envs,), 7.0).view(torch.int32)
-        return self.reset_device(), torch.ones(self.num_envs), done.to(torch.uint8), info
-
-
 def test_runner_feeds_windows_and_maps_relative_actions():
     torch.manual_seed(1)
     for oriented in (True, False):
@@ -308,7 +276,6 @@ def test_runner_feeds_windows_and_maps_relative_actions():
 
 
 def test_learn_on_windows_and_the_refusal_of_the_other_kind(tmp_path):
-    import test_selfplay_cpu as tsc
     kw = dict(nsteps=4, total_timesteps=8 * 4 * 2, nminibatches=2, noptepochs=1, opponent_save_interval=1, log_fn=None)
     d = str(tmp_path / "win")
     model, hist = selfplay.learn(_FakeLocalEnv(n_snakes=2), save_dir=d, local_radius=2, **kw)
@@ -317,12 +284,12 @@ def test_learn_on_windows_and_the_refusal_of_the_other_kind(tmp_path):
     assert selfplay.window_kind(torch.load(path, weights_only=True)) == (2, True)
     selfplay.learn(_FakeLocalEnv(n_snakes=2), load_path=path, local_radius=2, **kw)          # the same kind loads
     for other in (dict(local_radius=None), dict(local_radius=3), dict(local_radius=2, oriented=False)):
-        env = _FakeLocalEnv(n_snakes=2) if other["local_radius"] else tsc._FakeEnv()
+        env = _FakeLocalEnv(n_snakes=2) if other["local_radius"] else FakeEnv()
         with pytest.raises(RuntimeError, match="cannot be loaded"):
             selfplay.learn(env, load_path=path, **dict(kw, **other))
         with pytest.raises(RuntimeError, match="cannot be loaded"):                          # nor resumed
             selfplay.learn(env, save_dir=d, resume=True, **dict(kw, **other))
     d2 = str(tmp_path / "frames")
-    selfplay.learn(tsc._FakeEnv(), save_dir=d2, **kw)
+    selfplay.learn(FakeEnv(), save_dir=d2, **kw)
     with pytest.raises(RuntimeError, match="full frames"):
         selfplay.learn(_FakeLocalEnv(n_snakes=2), load_path=os.path.join(d2, "snake_model_num2.pt"), local_radius=2, **kw)

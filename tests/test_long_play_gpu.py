@@ -13,16 +13,9 @@ import numpy as np
 import pytest
 
 import scripted_play as sp
+from gpu_harness import make_env as _mk
 
 pytestmark = pytest.mark.gpu
-
-
-def _mk(cfg, **kw):
-    import msnake
-    base = dict(num_envs=cfg["num_envs"], dim=cfg["dim"], n_snakes=cfg["n_snakes"], n_fruits=cfg["n_fruits"],
-                rules=cfg["rules"], seed=cfg["seed"], env_id_base=cfg["env_id_base"], max_steps=cfg["max_steps"])
-    base.update(kw)
-    return msnake.MultiSnakeVecEnv(**base)
 
 
 def _state(env, e):

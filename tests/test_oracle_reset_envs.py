@@ -18,6 +18,7 @@ import pytest
 
 from golden_util import GOLDEN, crc_rows, feed_step, load_tape, state_view, tape_names, unpack_state
 from oracle import snake_oracle as so
+from reset_emulation import cut_by_time, emulated_masked_reset, raw_words
 
 with np.load(os.path.join(GOLDEN, "random_configs.npz")) as _z:
     META, REC = json.loads(str(_z["meta"])), {k: _z[k] for k in _z.files if k != "meta"}
@@ -96,32 +97,6 @@ def test_random_configuration_through_step_and_reset_envs(case):
 
 
 # ---------------------------------------------------------------------------------- against the export / import emulation
-def raw_words(ora, e):
-    n = ora.L.orc_export_state(ora.h, e, None, 0)
-    buf = np.zeros(n, np.int32)
-    ora.L.orc_export_state(ora.h, e, buf.ctypes.data, n)
-    return buf
-
-
-def cut_by_time(words, rules, max_steps):
-    """The truncation flag of a FINISHED episode from its canonical words: t >= max_steps and the rule set's own end
-    condition does not hold ([S]/[A]: the main snake is dead = its body is empty; [N]: its alive bit, done = alive)."""
-    k = 8 + 2 * int(words[6])  # snake 0: len, v0, v1, grow_to, alive, in_dead
-    ended = bool(words[k + 4]) if rules == "new_world" else int(words[k]) == 0
-    return int(words[0]) >= max_steps and not ended
-
-
-def emulated_masked_reset(ora, mask):
-    """The masked reset as the GPU tests emulated it before orc_reset_envs existed: the unselected envs' words are exported,
-    every env is reset, and the saved words are imported again; then every row is re-rendered.  (The import drops the
-    oracle's `finished`, which its export does not carry: callers of this helper keep that bit themselves.)"""
-    keep = {e: raw_words(ora, e) for e in range(ora.num_envs) if not mask[e]}
-    ora.reset()
-    for e, w in keep.items():
-        assert ora.L.orc_import_state(ora.h, e, w.ctypes.data, len(w)) == 0
-    return ora.render().copy()
-
-
 @pytest.mark.parametrize("rules,dim,ns,nf", RULESETS)
 def test_reset_envs_equals_the_export_import_emulation(rules, dim, ns, nf):
     n, max_steps = 48, 9

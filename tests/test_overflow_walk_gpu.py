@@ -29,7 +29,7 @@ import pytest
 import cells_play as cp
 import scripted_play as sp
 import space_play as spp
-from test_copy_envs_gpu import assert_words, blob_words, ora_words
+from state_domain import assert_words, blob_words, export as ora_words
 
 pytestmark = pytest.mark.gpu
 

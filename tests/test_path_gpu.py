@@ -11,18 +11,17 @@ reads the levels off in two ways, with the staged field (field_dev given) and wi
 import numpy as np
 import pytest
 
+import board_states as bs
+import gpu_harness as gh
 import path_play as pp
 import scripted_play as sp
 import space_play as spp
-import test_scripted_gpu as tsg   # state builders and guarded buffers (helpers only: nothing of it is collected here)
-import test_space_gpu as tspg     # likewise: dense boards, mazes, overflow-ring bodies, the install
 
 pytestmark = pytest.mark.gpu
 
-GUARD = tsg.GUARD
 NONE = pp.NONE
-_st, _mk, _states, _install = tsg._st, tsg._mk, tsg._states, tspg._install
-SENT = 0xA5A5
+_st, _mk, _states, _install = bs.state, gh.make_env, gh.oracle_states, gh.install
+FILL, SENT = -77, 0xA5A5   # the sentinels of the action buffer (gpu_harness.action_spec) and of the uint16 buffers
 
 
 # ------------------------------------------------------------------------------------------ expectations
@@ -47,39 +46,15 @@ def _cfg(name, **kw):
     return dict(sp.SCENARIOS[name], eps=0.0, policy="path_greedy", **kw)
 
 
-class Guarded(tsg.Guarded):
-    """tsg.Guarded plus a uint16 [n, ns, 4] path buffer and a uint16 [n, dim, dim] field buffer between guard elements,
-    filled with the sentinel 0xA5A5.  shift = 1 starts both one element later: 2-byte aligned and no more."""
-
-    def __init__(self, env, stride=None, fill=-77, shift=0):
-        import torch
-        super().__init__(env, stride, fill)
-        n, ns, dim = env.num_envs, env.n_snakes, int(env.cfg.dim)
-        self.shift = shift
-        self.p_all = torch.full((n * ns * 4 + 2 * GUARD + shift,), SENT - 0x10000, dtype=torch.int16, device=env.device)
-        self.f_all = torch.full((n * dim * dim + 2 * GUARD + shift,), SENT - 0x10000, dtype=torch.int16, device=env.device)
-        self.path = self.p_all[GUARD + shift:GUARD + shift + n * ns * 4].view(torch.uint16).view(n, ns, 4)
-        self.field = self.f_all[GUARD + shift:GUARD + shift + n * dim * dim].view(torch.uint16).view(n, dim, dim)
-        assert self.path.data_ptr() % 4 == 2 * shift and self.field.data_ptr() % 4 == 2 * shift
-
-    def _inner(self, t, shape):
-        return t.cpu().numpy().view(np.uint16)[GUARD + self.shift:-GUARD].reshape(shape)
-
-    def paths(self):
-        return self._inner(self.p_all, self.path.shape)
-
-    def fields(self):
-        return self._inner(self.f_all, self.field.shape)
-
-    def refill(self):
-        self.a_all.fill_(self.fill), self.s_all.fill_(0xA5), self.p_all.fill_(SENT - 0x10000), self.f_all.fill_(SENT - 0x10000)
-
-    def guards_intact(self):
-        ok = super().guards_intact()
-        for t in (self.p_all, self.f_all):
-            c = t.cpu().numpy().view(np.uint16)
-            ok = ok and (c[:GUARD + self.shift] == SENT).all() and (c[-GUARD:] == SENT).all()
-        return ok
+def Guarded(env, stride=None, shift=0):
+    """Actions, mask, a uint16 [n, ns, 4] buffer `path` and a uint16 [n, dim, dim] buffer `field`, each between guard
+    elements.  shift = 1 starts the two uint16 payloads one element later: 2-byte aligned and no more."""
+    dim = int(env.cfg.dim)
+    u16 = dict(dtype="uint16", fill=SENT, offset=2 * shift, align=4)
+    buf = gh.GuardedOutputs(env.device, dict(gh.action_spec(env, stride), path=dict(u16, shape=(env.num_envs, env.n_snakes, 4)),
+                                             field=dict(u16, shape=(env.num_envs, dim, dim))))
+    assert buf.path.data_ptr() % 4 == 2 * shift and buf.field.data_ptr() % 4 == 2 * shift
+    return buf
 
 
 def _diff(what, name, got, want, states):
@@ -96,17 +71,17 @@ def _check_call(env, states, buf=None, what="", want=None):
     buf.refill()
     out, safe, path, field = env.scripted_actions_device("path_greedy", out=buf.act, safe_out=buf.safe, path_out=buf.path,
                                                          field_out=buf.field)
-    _diff(what, "field", buf.fields(), want_f, states)
-    _diff(what, "path", buf.paths(), want_p, states)
+    _diff(what, "field", buf.host("field"), want_f, states)
+    _diff(what, "path", buf.host("path"), want_p, states)
     _diff(what, "mask", safe.cpu().numpy(), want_m, states)
     _diff(what, "action", out.cpu().numpy()[:, :ns], want_a, states)
     assert buf.guards_intact(), what
     buf.refill()
     out, safe, path = env.scripted_actions_device("path_greedy", out=buf.act, safe_out=buf.safe, path_out=buf.path)
-    _diff(what, "path without the field", buf.paths(), want_p, states)
+    _diff(what, "path without the field", buf.host("path"), want_p, states)
     _diff(what, "mask without the field", safe.cpu().numpy(), want_m, states)
     _diff(what, "action without the field", out.cpu().numpy()[:, :ns], want_a, states)
-    assert (buf.f_all.cpu().numpy().view(np.uint16) == SENT).all() and buf.guards_intact(), what
+    assert buf.untouched("field") and buf.guards_intact(), what
     return want_a
 
 
@@ -117,8 +92,8 @@ def test_hand_built_snake_env_states(dim):
     under bodies and duplicated fruits come with the random draws and are counted."""
     ns = 3
     rng = np.random.default_rng([17, dim])
-    states = tsg._border_states(dim, ns, ns, rng) + tsg._random_states(dim, ns, ns, rng, 24, dup=True)
-    states += tspg._dense_states(dim, ns, ns, rng, 24 if dim < 62 else 10)
+    states = bs.border_states(dim, ns, ns, rng) + bs.random_states(dim, ns, ns, rng, 24, dup=True)
+    states += bs.dense_states(dim, ns, ns, rng, 24 if dim < 62 else 10)
     states.append(_st([[], [], []], [(0, 0)] * ns))                        # empty bodies: every path NONE, the field is whole
     states.append(_st([[(0, 0)], [(dim - 1, dim - 1)], []], [(0, 0), (dim - 1, dim - 1), (0, 0)]))   # every fruit under a head
     states.append(_st([[(0, 0)], [], []], [(dim - 1, dim - 1)] * ns))      # one fruit three times, the far corner
@@ -139,8 +114,8 @@ def test_hand_built_new_world_states_with_four_snakes(dim):
     """Four snakes, some dead with their bodies kept (alive False, in and out of dead_snakes), stacked duplicates."""
     ns, nf = 4, 5
     rng = np.random.default_rng([18, dim])
-    states = tsg._border_states(dim, ns, nf, rng) + tsg._random_states(dim, ns, nf, rng, 30, dup=True)
-    states += tspg._dense_states(dim, ns, nf, rng, 30)
+    states = bs.border_states(dim, ns, nf, rng) + bs.random_states(dim, ns, nf, rng, 30, dup=True)
+    states += bs.dense_states(dim, ns, nf, rng, 30)
     for st in states[::2]:
         st["alive"] = [bool(rng.integers(0, 2)) for _ in range(ns)]
         st["in_dead"] = [not a and bool(rng.integers(0, 2)) for a in st["alive"]]
@@ -163,7 +138,7 @@ def test_hand_built_adversarial_states_with_long_fruit_lists(dim):
     fcap = (3 + 3 * (dim * dim + 2) + 63) // 64 * 64      # the handle's fruit-list capacity
     states = []
     for n_list in (0, 1, 63, 64, 65, min(130, fcap - 3), fcap):   # (dim 6: the capacity is 128 entries)
-        for st in tspg._dense_states(dim, ns, n_list, rng, 5, fruit_lo=-1, fruit_hi=dim + 1):
+        for st in bs.dense_states(dim, ns, n_list, rng, 5, fruit_lo=-1, fruit_hi=dim + 1):
             states.append(st)
     h = (dim // 2, dim // 2)
     first = len(states)
@@ -206,7 +181,7 @@ def test_serpentine_mazes(dim, transposed):
     buf = Guarded(env)
     _check_call(env, states, buf, what=("maze", dim, transposed))
     env.scripted_actions_device("path_greedy", out=buf.act, path_out=buf.path, field_out=buf.field)
-    got_p, got_f, got_a = buf.paths(), buf.fields(), buf.act.cpu().numpy()
+    got_p, got_f, got_a = buf.host("path"), buf.host("field"), buf.act.cpu().numpy()
     longest = 0
     for e, (i, j) in enumerate(pairs):
         head = corridor[i]
@@ -237,7 +212,7 @@ def test_separating_piece_in_the_overflow_ring(rules, dim, ns):
     library and the oracle alike, compared after the install and after each of a few steps under path_greedy."""
     import torch
     from oracle.snake_oracle import state_to_flat
-    states, walled = tspg._overflow_states(dim, ns)
+    states, walled = bs.overflow_states(dim, ns)
     states = [dict(st) for st in states]
     for st in states[len(states) - walled:]:
         # the wall of pieces >= 64 lies between snake 1's move 2 and the fruits at (0, 0); move 4 eats
@@ -268,49 +243,23 @@ def test_separating_piece_in_the_overflow_ring(rules, dim, ns):
 
 
 # ------------------------------------------------------------------------------------------ 4. closed loop
-def _closed_loop(cfg, env, steps, control=None, stride=None, obs_every=50):
-    """The oracle is the master: at every step the helpers' actions, masks, paths and fields on the oracle's state are
-    compared with the library's for every env, snake, move and cell, both are stepped with the helper's actions, and the
-    step outputs are compared.  control=(rng, snakes): only `snakes` are scripted, the other columns carry seeded random
-    actions.  Even steps ask for the field, odd steps do not (the two read-offs)."""
-    import torch
-    E, ns, dim = cfg["num_envs"], cfg["n_snakes"], cfg["dim"]
-    ora = sp.make_oracle(cfg)
-    assert np.array_equal(env.reset(), ora.reset())
-    buf = Guarded(env, stride)
-    for t in range(steps):
-        states = _states(ora)
-        want_a, want_m, want_p, want_f = expected(states, dim, ns)
-        snakes = None
-        if control is not None:
-            rng, snakes = control
-            rand = rng.integers(0, 5, (E, buf.stride)).astype(np.int32)
-            rand[:, ns:] = -5 - t % 3                              # surplus columns: never written
-            buf.act.copy_(torch.from_numpy(rand).to(env.device))
-            keep = [s for s in range(ns) if s not in snakes]
-            want_a[:, keep] = rand[:, keep]
-        kw = dict(field_out=buf.field) if t % 2 == 0 else {}
-        buf.f_all.fill_(SENT - 0x10000)
-        out, safe, *_ = env.scripted_actions_device("path_greedy", snakes=snakes, out=buf.act, safe_out=buf.safe,
-                                                    path_out=buf.path, **kw)
-        got = out.cpu().numpy()
-        _diff(t, "action", got[:, :ns], want_a, states)
-        if control is not None:
-            assert np.array_equal(got[:, ns:], rand[:, ns:]), t
-        _diff(t, "mask", safe.cpu().numpy(), want_m, states)
-        _diff(t, "path", buf.paths(), want_p, states)
-        if kw:
-            _diff(t, "field", buf.fields(), want_f, states)
-        else:
-            assert (buf.fields() == SENT).all()
-        obs, rew, done, info = env.step_device(out)
-        o_obs, o_rew, o_done, o_ns, _, _ = ora.step(want_a)
-        assert np.array_equal(rew.cpu().numpy(), o_rew) and np.array_equal(done.cpu().numpy(), o_done), t
-        assert np.array_equal(info.cpu().numpy()[:, 2], o_ns), t
-        if t % obs_every == 0 or t == steps - 1:
-            assert np.array_equal(obs.cpu().numpy(), o_obs), t
-    assert buf.guards_intact()
-    assert env.stats()["errors"] == 0
+def _closed_loop(cfg, env, steps, **kw):
+    """gpu_harness.closed_loop under path_greedy with actions, mask and paths.  Even steps ask for the field too, odd
+    steps do not (the two read-offs): then the field buffer must keep its sentinel."""
+    step = [-1]
+
+    def want(states):
+        step[0] += 1
+        want_a, want_m, want_p, want_f = expected(states, cfg["dim"], cfg["n_snakes"])
+        return want_a, want_m, want_p, want_f if step[0] % 2 == 0 else np.full_like(want_f, SENT)
+
+    def call(env, buf, snakes):
+        buf.refill(["field"])
+        field = dict(field_out=buf.field) if step[0] % 2 == 0 else {}
+        out, safe, *_ = env.scripted_actions_device("path_greedy", snakes=snakes, out=buf.act, safe_out=buf.safe, path_out=buf.path, **field)
+        return out, safe, buf.host("path"), buf.host("field")
+
+    gh.closed_loop(cfg, env, call, want, steps, buffers=Guarded, **kw)
 
 
 @pytest.mark.parametrize("name,steps", [("S19x3", 150), ("A10x3", 150), ("N10x4", 100)])
@@ -337,7 +286,7 @@ def test_batch_sizes(n):
     cfg = _cfg("N10x4", num_envs=n)
     env, ora = _mk(cfg), sp.make_oracle(cfg)
     env.reset(), ora.reset()
-    tsg._play_random(env, ora, 6, np.random.default_rng(n), threads=1)
+    gh.play_random(env, ora, 6, np.random.default_rng(n), threads=1)
     _check_call(env, _states(ora), Guarded(env, shift=1), what=n)
     env.close()
 
@@ -397,23 +346,21 @@ def test_each_output_alone_and_all_together(stride, shift):
     cfg = _cfg("N10x4", num_envs=13)
     env, ora = _mk(cfg), sp.make_oracle(cfg)
     env.reset(), ora.reset()
-    tsg._play_random(env, ora, 6, np.random.default_rng(stride), threads=1)
+    gh.play_random(env, ora, 6, np.random.default_rng(stride), threads=1)
     states = _states(ora)
     want_a, want_m, want_p, want_f = expected(states, 10, 4)
     buf = Guarded(env, stride, shift=shift)
-    acts_untouched = lambda: (buf.a_all.cpu().numpy() == buf.fill).all()
-    safe_untouched = lambda: (buf.s_all.cpu().numpy() == 0xA5).all()
-    path_untouched = lambda: (buf.p_all.cpu().numpy().view(np.uint16) == SENT).all()
-    field_untouched = lambda: (buf.f_all.cpu().numpy().view(np.uint16) == SENT).all()
+    acts_untouched, safe_untouched = lambda: buf.untouched("act"), lambda: buf.untouched("safe")
+    path_untouched, field_untouched = lambda: buf.untouched("path"), lambda: buf.untouched("field")
     # path_dev alone
     assert env.path_device(out=buf.path) is buf.path
-    assert np.array_equal(buf.paths(), want_p) and acts_untouched() and safe_untouched() and field_untouched() and buf.guards_intact()
+    assert np.array_equal(buf.host("path"), want_p) and acts_untouched() and safe_untouched() and field_untouched() and buf.guards_intact()
     got = env.path_device()                                                    # a fresh tensor of the env's
     assert got.dtype == __import__("torch").uint16 and np.array_equal(got.cpu().numpy(), want_p)
     # field_dev alone
     buf.refill()
     assert env.fruit_field_device(out=buf.field) is buf.field
-    assert np.array_equal(buf.fields(), want_f) and acts_untouched() and safe_untouched() and path_untouched() and buf.guards_intact()
+    assert np.array_equal(buf.host("field"), want_f) and acts_untouched() and safe_untouched() and path_untouched() and buf.guards_intact()
     got = env.fruit_field_device()
     assert tuple(got.shape) == (13, 10, 10) and np.array_equal(got.cpu().numpy(), want_f)
     # safe_dev alone (an empty selection): no action word, no path and no field is written
@@ -424,16 +371,16 @@ def test_each_output_alone_and_all_together(stride, shift):
     buf.refill()
     out = env.scripted_actions_device("path_greedy", snakes=[3, 1], out=buf.act)
     got = out.cpu().numpy()
-    assert np.array_equal(got[:, [1, 3]], want_a[:, [1, 3]]) and (got[:, [0, 2] + list(range(4, stride))] == buf.fill).all()
+    assert np.array_equal(got[:, [1, 3]], want_a[:, [1, 3]]) and (got[:, [0, 2] + list(range(4, stride))] == FILL).all()
     assert safe_untouched() and path_untouched() and field_untouched() and buf.guards_intact()
     # all four, snake 2 only: the mask, the paths and the field are written for every snake whatever the selection
     buf.refill()
     res = env.scripted_actions_device("path_greedy", snakes=[2], out=buf.act, safe_out=buf.safe, path_out=buf.path, field_out=buf.field)
     assert [t.data_ptr() for t in res] == [buf.act.data_ptr(), buf.safe.data_ptr(), buf.path.data_ptr(), buf.field.data_ptr()]
     got = res[0].cpu().numpy()
-    assert np.array_equal(got[:, 2], want_a[:, 2]) and (got[:, [0, 1, 3] + list(range(4, stride))] == buf.fill).all()
-    assert np.array_equal(buf.safe.cpu().numpy(), want_m) and np.array_equal(buf.paths(), want_p)
-    assert np.array_equal(buf.fields(), want_f) and buf.guards_intact()
+    assert np.array_equal(got[:, 2], want_a[:, 2]) and (got[:, [0, 1, 3] + list(range(4, stride))] == FILL).all()
+    assert np.array_equal(buf.safe.cpu().numpy(), want_m) and np.array_equal(buf.host("path"), want_p)
+    assert np.array_equal(buf.host("field"), want_f) and buf.guards_intact()
     # the results do not depend on which outputs are asked for: every combination, with and without the actions
     names = ("safe_out", "path_out", "field_out")
     for with_actions in (True, False):
@@ -445,12 +392,12 @@ def test_each_output_alone_and_all_together(stride, shift):
             env.scripted_actions_device("path_greedy", snakes=None if with_actions else [], out=buf.act, **kw)
             got = buf.act.cpu().numpy()
             if with_actions:
-                assert np.array_equal(got[:, :4], want_a) and (got[:, 4:] == buf.fill).all(), kw.keys()
+                assert np.array_equal(got[:, :4], want_a) and (got[:, 4:] == FILL).all(), kw.keys()
             else:
                 assert acts_untouched(), kw.keys()
             assert np.array_equal(buf.safe.cpu().numpy(), want_m) if pick[0] else safe_untouched(), kw.keys()
-            assert np.array_equal(buf.paths(), want_p) if pick[1] else path_untouched(), kw.keys()
-            assert np.array_equal(buf.fields(), want_f) if pick[2] else field_untouched(), kw.keys()
+            assert np.array_equal(buf.host("path"), want_p) if pick[1] else path_untouched(), kw.keys()
+            assert np.array_equal(buf.host("field"), want_f) if pick[2] else field_untouched(), kw.keys()
             assert buf.guards_intact(), kw.keys()
     # the env's own cached action buffer, shared with the other policies
     a = env.scripted_actions_device("path_greedy", snakes=[2])

@@ -14,16 +14,15 @@ import os
 import numpy as np
 import pytest
 
+import gpu_harness as gh
 import local_play as lp
 import rays_play as rp
 import scripted_play as sp
-import test_scripted_gpu as tsg   # its helpers (nothing of it is collected here)
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
 FILL = 0xA5
-_mk = tsg._mk
+_mk = gh.make_env
 
 
 class _Sets:
@@ -39,38 +38,14 @@ class _Sets:
 SETS = _Sets()
 
 
-class Guarded:
-    """A uint8 [n, S, 8, 4] ray buffer (4-byte aligned) and a uint8 [n, S] heading buffer, each between 64 guard bytes,
-    all filled with 0xA5."""
-
-    def __init__(self, env, n_sel):
-        import torch
-        n = env.num_envs
-        self.size = n * n_sel * 32
-        self.r_all = torch.full((2 * GUARD + self.size,), FILL, dtype=torch.uint8, device=env.device)
-        assert self.r_all.data_ptr() % 4 == 0
-        self.rays = self.r_all[GUARD:GUARD + self.size].view(n, n_sel, 8, 4)
-        self.h_all = torch.full((n * n_sel + 2 * GUARD,), FILL, dtype=torch.uint8, device=env.device)
-        self.head = self.h_all[GUARD:GUARD + n * n_sel].view(n, n_sel)
-
-    def refill(self):
-        self.r_all.fill_(FILL), self.h_all.fill_(FILL)
-
-    def get_rays(self):
-        return self.r_all.cpu().numpy()[GUARD:-GUARD].reshape(tuple(self.rays.shape))
-
-    def headings(self):
-        return self.h_all.cpu().numpy()[GUARD:-GUARD].reshape(tuple(self.head.shape))
-
-    def guards_intact(self):
-        r, h = self.r_all.cpu().numpy(), self.h_all.cpu().numpy()
-        return ((r[:GUARD] == FILL).all() and (r[-GUARD:] == FILL).all() and (h[:GUARD] == FILL).all() and (h[-GUARD:] == FILL).all())
-
-    def rays_untouched(self):
-        return (self.r_all.cpu().numpy() == FILL).all()
-
-    def headings_untouched(self):
-        return (self.h_all.cpu().numpy() == FILL).all()
+def Guarded(env, n_sel):
+    """A uint8 [n, S, 8, 4] ray buffer `rays` (4-byte aligned) and a uint8 [n, S] heading buffer `head`, each between 64
+    guard bytes, all filled with 0xA5."""
+    n = env.num_envs
+    buf = gh.GuardedOutputs(env.device, {"rays": dict(dtype="uint8", shape=(n, n_sel, 8, 4), fill=FILL, align=4),
+                                         "head": dict(dtype="uint8", shape=(n, n_sel), fill=FILL)})
+    assert buf.rays.data_ptr() % 4 == 0
+    return buf
 
 
 @functools.lru_cache(maxsize=None)
@@ -92,31 +67,22 @@ def _compare(env, want_rays, want_head, snakes, oriented, heading=True, buf=None
     buf = buf or Guarded(env, len(sel))
     res = env.render_rays_device(snakes=snakes, oriented=oriented, out=buf.rays, heading_out=buf.head if heading else None)
     assert (res[0] is buf.rays and res[1] is buf.head) if heading else res is buf.rays
-    got = buf.get_rays()
+    got = buf.host("rays")
     bad = np.argwhere(got != want_rays)
     assert bad.size == 0, (what, "rays", bad[:5].tolist(), got[tuple(bad[0][:2])].tolist(), want_rays[tuple(bad[0][:2])].tolist())
     if heading:
-        got_h = buf.headings()
+        got_h = buf.host("head")
         assert np.array_equal(got_h, want_head), (what, "heading", np.argwhere(got_h != want_head)[:5].tolist())
     else:
-        assert buf.headings_untouched(), what
+        assert buf.untouched("head"), what
     assert buf.guards_intact(), what
     return buf
 
 
 def _install(name, **kw):
     """The builder set's states into a fresh handle, one env per state."""
-    from oracle.snake_oracle import flat_to_state, state_to_flat
     _, rules, dim, ns, nf, states = SETS[name]
-    cfg = dict(rules=rules, dim=dim, n_snakes=ns, n_fruits=nf, num_envs=len(states), seed=1, env_id_base=0, max_steps=2000)
-    env = _mk(cfg, **kw)
-    env.reset()
-    for e, st in enumerate(states):
-        env.set_state_words(e, state_to_flat(st, ns))
-    for e in (0, len(states) // 2, len(states) - 1):
-        got = flat_to_state(env.get_state_words(e))
-        assert got["snakes"] == states[e]["snakes"] and [list(v) for v in got["vels"]] == [list(v) for v in states[e]["vels"]]
-    return env
+    return gh.install(dict(rules=rules, dim=dim, n_snakes=ns, n_fruits=nf), states, **kw)
 
 
 def _masks(ns):
@@ -169,7 +135,7 @@ def test_space_greedy_play_followed_on_the_oracle(dim, ns, compiled):
         _, o_rew, o_done, *_ = ora.step(act, want_obs=False)
         assert np.array_equal(rew.cpu().numpy(), o_rew) and np.array_equal(done.cpu().numpy(), o_done), t
         if t % 10 == 9:
-            states = tsg._states(ora)
+            states = gh.oracle_states(ora)
             oriented = t % 20 == 9
             want, want_h = rp.np_rays_all(states, dim, ns, 0, range(ns), oriented)
             buf.refill()
@@ -259,8 +225,8 @@ def test_graph_of_step_then_render_rays():
         e_rays, e_head = twin.render_rays_device(heading=True)
         torch.cuda.synchronize()
         assert torch.equal(out[1], e_out[1]) and torch.equal(out[2], e_out[2]), k
-        assert np.array_equal(buf.get_rays(), e_rays.cpu().numpy()) and np.array_equal(buf.headings(), e_head.cpu().numpy()), k
-        assert buf.guards_intact() and (buf.get_rays()[..., rp.WALL] >= 1).mean() > 0.5   # (a snake that died has no rays)
+        assert np.array_equal(buf.host("rays"), e_rays.cpu().numpy()) and np.array_equal(buf.host("head"), e_head.cpu().numpy()), k
+        assert buf.guards_intact() and (buf.host("rays")[..., rp.WALL] >= 1).mean() > 0.5   # (a snake that died has no rays)
     assert env.get_state_all().tobytes() == twin.get_state_all().tobytes()
     env.close(), twin.close()
 
@@ -294,7 +260,7 @@ def test_argument_errors_leave_the_outputs_untouched():
         rc, msg = call(dead, *args)
         assert rc == -3 and "handle" in msg, (args, rc, msg)                                   # before any argument check
     torch.cuda.synchronize()
-    assert buf.rays_untouched() and buf.headings_untouched()
+    assert buf.untouched("rays") and buf.untouched("head")
     # the wrapper's own refusals, before the library is asked
     odd = torch.full((5 * 2 * 32 + 4,), FILL, dtype=torch.uint8, device=env.device)[1:1 + 5 * 2 * 32].view(5, 2, 8, 4)
     for kw in (dict(snakes=[]), dict(snakes=[2]), dict(snakes=[1, 0]), dict(oriented=2), dict(oriented=None),
@@ -307,7 +273,7 @@ def test_argument_errors_leave_the_outputs_untouched():
         name = {"snakes": "snake"}.get(next(iter(kw)), next(iter(kw)))     # (the argument the message must name)
         assert name in str(err.value), (kw, str(err.value))
     torch.cuda.synchronize()
-    assert buf.rays_untouched() and buf.headings_untouched() and (odd.cpu().numpy() == FILL).all()
+    assert buf.untouched("rays") and buf.untouched("head") and (odd.cpu().numpy() == FILL).all()
     # what is NOT an error: heading_dev NULL or unaligned, fresh tensors of the env's own
     assert call(env._h, 0b10, 0, pr, None)[0] == 0 and call(env._h, 0b01, 1, pr, ph + 1)[0] == 0
     rays, head = env.render_rays_device(heading=True)

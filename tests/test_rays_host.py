@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from fake_envs import FakeEnv, FakeLocalEnv
 import local_play as lp
 import msnake
 import rays_play as rp
@@ -294,8 +295,6 @@ def test_runner_feeds_rays_and_maps_relative_actions():
 
 
 def test_learn_on_rays_and_the_refusals(tmp_path):
-    import test_local_host as tlh
-    import test_selfplay_cpu as tsc
     kw = dict(nsteps=4, total_timesteps=8 * 4 * 2, nminibatches=2, noptepochs=1, opponent_save_interval=1, log_fn=None)
     d = str(tmp_path / "rays")
     env = _FakeRayEnv(n_snakes=3)
@@ -310,13 +309,13 @@ def test_learn_on_rays_and_the_refusals(tmp_path):
     d2 = str(tmp_path / "rays2")
     selfplay.learn(_FakeRayEnv(n_snakes=2), save_dir=d2, rays=True, **kw)
     path2 = os.path.join(d2, "snake_model_num2.pt")
-    for other, fake in ((dict(), tsc._FakeEnv()), (dict(local_radius=2), tlh._FakeLocalEnv(n_snakes=2)),
+    for other, fake in ((dict(), FakeEnv()), (dict(local_radius=2), FakeLocalEnv(n_snakes=2)),
                         (dict(rays=True, oriented=False), _FakeRayEnv(n_snakes=2))):
         with pytest.raises(RuntimeError, match="cannot be loaded"):
             selfplay.learn(fake, load_path=path2, **dict(kw, **other))
         with pytest.raises(RuntimeError, match="cannot be loaded"):                           # nor resumed
             selfplay.learn(fake, save_dir=d2, resume=True, **dict(kw, **other))
     d3 = str(tmp_path / "win")
-    selfplay.learn(tlh._FakeLocalEnv(n_snakes=2), save_dir=d3, local_radius=2, **kw)
+    selfplay.learn(FakeLocalEnv(n_snakes=2), save_dir=d3, local_radius=2, **kw)
     with pytest.raises(RuntimeError, match="windows of radius 2"):
         selfplay.learn(_FakeRayEnv(n_snakes=2), load_path=os.path.join(d3, "snake_model_num2.pt"), rays=True, **kw)

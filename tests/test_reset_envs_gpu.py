@@ -86,7 +86,7 @@ def test_masked_reset_without_auto_reset():
     import torch
     n, ns, dim, max_steps, sentinel = 40, 3, 10, 12, 0xA5
     kw = dict(num_envs=n, dim=dim, n_snakes=ns, rules="snake_env", seed=8, max_steps=max_steps)
-    from test_oracle_reset_envs import cut_by_time, emulated_masked_reset
+    from reset_emulation import cut_by_time, emulated_masked_reset
     env = _mk(auto_reset=False, **kw)
     ora = _oracle(auto_reset=False, **kw)
     emu = _oracle(auto_reset=False, **kw)  # the same oracle, on which the masked reset is emulated by state export / import

@@ -14,7 +14,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from test_gpu_parity import _serpentine
+from board_states import serpentine_body
 
 pytestmark = pytest.mark.gpu
 
@@ -250,7 +250,7 @@ def test_masked_reset_of_long_bodies_long_fruit_lists_and_wrapping_counters(rule
     ks = list(range(4 * ns + 1))
     for e in range(n):
         la, lb = int(rs.integers(50, 250)), int(rs.integers(1, 60))
-        a, b = _serpentine(dim, la, 0, rs), _serpentine(dim, lb, 15, rs)
+        a, b = serpentine_body(dim, la, 0), serpentine_body(dim, lb, 15)
         va = [1, 0] if a[0][1] % 2 == 0 else [-1, 0]
         # [N]: the alive bit (the body stays; the episode ends while it is ON); [S]/[A]: a dead snake has no body
         main_dead = e % 2 == 1 if rules == "new_world" else e % 5 == 4

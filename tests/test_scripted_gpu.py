@@ -8,11 +8,14 @@ expected mask is the NumPy statement scripted_play.np_safe_mask.  Neither ever c
 import numpy as np
 import pytest
 
+import board_states as bs
+import gpu_harness as gh
 import scripted_play as sp
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64  # guard elements on each side of an output buffer
+FILL = -77  # the sentinel of the action buffer (gpu_harness.action_spec)
+_st, _mk, _states, _play_random = bs.state, gh.make_env, gh.oracle_states, gh.play_random
 
 
 # ------------------------------------------------------------------------------------------ expectations
@@ -30,37 +33,10 @@ def _cfg(name, **kw):
     return dict(sp.SCENARIOS[name], eps=0.0, **kw)
 
 
-def _mk(cfg, **kw):
-    import msnake
-    base = dict(num_envs=cfg["num_envs"], dim=cfg["dim"], n_snakes=cfg["n_snakes"], n_fruits=cfg["n_fruits"],
-                rules=cfg["rules"], seed=cfg["seed"], env_id_base=cfg["env_id_base"], max_steps=cfg["max_steps"])
-    base.update(kw)
-    return msnake.MultiSnakeVecEnv(**base)
-
-
-class Guarded:
-    """An int32 [n, stride] action buffer and a uint8 [n, ns] mask buffer between guard elements, filled with sentinels."""
-
-    def __init__(self, env, stride=None, fill=-77):
-        import torch
-        n, ns = env.num_envs, env.n_snakes
-        self.stride = stride or ns
-        self.a_all = torch.full((n * self.stride + 2 * GUARD,), fill, dtype=torch.int32, device=env.device)
-        self.s_all = torch.full((n * ns + 2 * GUARD,), 0xA5, dtype=torch.uint8, device=env.device)
-        self.act = self.a_all[GUARD:GUARD + n * self.stride].view(n, self.stride)
-        self.safe = self.s_all[GUARD:GUARD + n * ns].view(n, ns)
-        self.fill = fill
-
-    def guards_intact(self):
-        a, s = self.a_all.cpu().numpy(), self.s_all.cpu().numpy()
-        return ((a[:GUARD] == self.fill).all() and (a[-GUARD:] == self.fill).all() and (s[:GUARD] == 0xA5).all() and
-                (s[-GUARD:] == 0xA5).all())
-
-
 def _check_call(env, policy, states, buf=None, what=""):
     """One call with actions and mask, compared for every env and snake; returns the expected actions."""
     dim, ns = env.cfg.dim, env.n_snakes
-    buf = buf or Guarded(env)
+    buf = buf or gh.action_buffers(env)
     want_a, want_m = expected(policy, states, dim, ns)
     out, safe = env.scripted_actions_device(policy, out=buf.act, safe_out=buf.safe)
     got_a, got_m = out.cpu().numpy()[:, :ns], safe.cpu().numpy()
@@ -87,49 +63,22 @@ REACH = {"S19x3": dict(longest_body=93, env_steps_over_64=913, episodes=358),
 
 
 def _closed_loop(cfg, env, expect, control=None, stride=None, obs_every=50, steps=None):
-    """The oracle is the master: at every step the helper's actions on the oracle's state are compared with the
-    library's for every env and snake, both are stepped with the helper's, and the step outputs are compared.
+    """gpu_harness.closed_loop under cfg["policy"], with the coverage of the play counted on the ORACLE's numbers.
     control=(rng, k): snakes 0..k-1 get seeded random actions pre-filled in the buffer, the others are scripted."""
-    import torch
     E, ns, dim, T = cfg["num_envs"], cfg["n_snakes"], cfg["dim"], steps or cfg["steps"]
-    ora = sp.make_oracle(cfg)
-    read = sp._StateReader(ora)
-    assert np.array_equal(env.reset(), ora.reset())
-    buf = Guarded(env, stride)
     body_max, n_fr = np.zeros((T, E), np.int16), np.zeros((T, E), np.int16)
     done_all, ep_len = np.zeros((T, E), np.uint8), np.zeros((T, E), np.int32)
-    states = [read(e) for e in range(E)]
-    for t in range(T):
-        want_a, want_m = expected(cfg["policy"], states, dim, ns)
-        snakes = None
-        if control is not None:
-            rng, k = control
-            rand = rng.integers(0, 5, (E, buf.stride)).astype(np.int32)
-            rand[:, ns:] = -5 - t % 3                              # surplus columns: never written
-            buf.act.copy_(torch.from_numpy(rand).to(env.device))
-            want_a = np.concatenate([rand[:, :k], want_a[:, k:]], axis=1)
-            snakes = range(k, ns)
-        out, safe = env.scripted_actions_device(cfg["policy"], snakes=snakes, out=buf.act, safe_out=buf.safe)
-        got = out.cpu().numpy()
-        assert np.array_equal(got[:, :ns], want_a), (t, np.argwhere(got[:, :ns] != want_a)[:4].tolist())
-        if control is not None:
-            assert np.array_equal(got[:, ns:], rand[:, ns:]), t   # (column 0 is part of want_a)
-        assert np.array_equal(safe.cpu().numpy(), want_m), (t, "mask")
-        obs, rew, done, info = env.step_device(out)
-        o_obs, o_rew, o_done, o_ns, o_er, o_el = ora.step(want_a)
-        info = info.cpu().numpy()
-        assert np.array_equal(rew.cpu().numpy(), o_rew) and np.array_equal(done.cpu().numpy(), o_done), t
-        assert np.array_equal(info[:, 2], o_ns), t
-        if t % obs_every == 0 or t == T - 1:
-            assert np.array_equal(obs.cpu().numpy(), o_obs), t
-        states = [read(e) for e in range(E)]
+
+    def observe(t, states, wants, o_done, o_el):
         body_max[t] = [max(len(b) for b in st["snakes"]) for st in states]
         n_fr[t] = [len(st["fruits"]) for st in states]
         done_all[t], ep_len[t] = o_done, o_el
-    assert buf.guards_intact()
+
+    gh.closed_loop(cfg, env, lambda env, buf, snakes: env.scripted_actions_device(cfg["policy"], snakes=snakes, out=buf.act, safe_out=buf.safe),
+                   lambda states: expected(cfg["policy"], states, dim, ns), T, stride=stride, obs_every=obs_every, observe=observe,
+                   control=control and (control[0], range(control[1], ns)))
     cov = sp.coverage(cfg, body_max, n_fr, done_all, ep_len)
     sp.check_coverage(dict(cfg, expect=list(expect)), cov)
-    assert env.stats()["errors"] == 0
     return cov
 
 
@@ -152,97 +101,8 @@ def test_mixed_control_leaves_the_other_columns_untouched(name, steps, stride):
 
 
 # ------------------------------------------------------------------------------------------ 3. hand-built states
-def _st(snakes, fruits, alive=None, in_dead=None):
-    n = len(snakes)
-    return {"t": 3, "ctr": 40, "spare_fruits": 0, "ep_len": 3, "ep_return": 0.0, "fruits": [list(f) for f in fruits],
-            "snakes": [[list(c) for c in b] for b in snakes], "vels": [[1, 0]] * n, "grow_to": [max(len(b), 1) for b in snakes],
-            "alive": alive or [True] * n, "in_dead": in_dead or [False] * n}
-
-
-def _line(cells, dim):
-    """Boustrophedon path over the board as a list of cells (for long bodies)."""
-    out = []
-    for y in range(dim):
-        xs = range(dim) if y % 2 == 0 else range(dim - 1, -1, -1)
-        out += [(x, y) for x in xs]
-    return out[:cells]
-
-
-def _border_states(dim, ns, nf, rng):
-    """Heads on every corner and border (all of them for small boards), at -1 / dim, single cells and short bodies."""
-    cells = [(x, y) for x in range(dim) for y in range(dim) if x in (0, dim - 1) or y in (0, dim - 1)]
-    if len(cells) > 40:
-        keep = {(0, 0), (0, dim - 1), (dim - 1, 0), (dim - 1, dim - 1)}
-        cells = sorted(keep) + [cells[i] for i in rng.choice(len(cells), 36, replace=False)]
-    outside = [(-1, y) for y in (0, dim // 2, dim - 1)] + [(dim, y) for y in (0, dim // 2, dim - 1)] + \
-              [(x, -1) for x in (0, dim // 2, dim - 1)] + [(x, dim) for x in (0, dim // 2, dim - 1)]
-    states = []
-    for head in cells + outside:
-        bodies = [[head]]
-        for s in range(1, ns):   # the other snakes: random cells, sometimes next to the head, sometimes empty
-            k = int(rng.integers(0, 4))
-            near = [(head[0] + d0, head[1] + d1) for d0, d1 in sp.DIRS.values()]
-            near = [c for c in near if 0 <= c[0] < dim and 0 <= c[1] < dim]
-            body = [tuple(rng.integers(0, dim, 2)) for _ in range(k)]
-            if near and rng.random() < 0.6:
-                body.append(near[int(rng.integers(0, len(near)))])
-            bodies.append(body)
-        fruits = [tuple(rng.integers(0, dim, 2)) for _ in range(nf)]
-        states.append(_st(bodies, fruits))
-    return states
-
-
-def _random_states(dim, ns, nf, rng, count, fruit_lo=0, fruit_hi=None, dup=False):
-    fruit_hi = dim if fruit_hi is None else fruit_hi
-    states = []
-    for _ in range(count):
-        bodies = []
-        for s in range(ns):
-            k = int(rng.integers(0, min(dim * dim, 40) + 1)) if rng.random() < 0.9 else 0
-            body = [tuple(int(v) for v in rng.integers(0, dim, 2)) for _ in range(k)]
-            if dup and k > 2:
-                body[2] = body[1]
-            bodies.append(body)
-        fruits = [tuple(int(v) for v in rng.integers(fruit_lo, fruit_hi, 2)) for _ in range(nf)]
-        states.append(_st(bodies, fruits))
-    return states
-
-
-def _tie_states(dim):
-    """Two snakes on a board of dim >= 6: for every pair of directions, the two other moves blocked by snake 1 and the
-    distances of the two open ones equal (one fruit on the head: every move is at distance 1; two fruits at equal
-    distances behind the targets); every single direction open alone; all four blocked."""
-    h = (dim // 2, dim // 2)
-    tgt = {a: (h[0] + d[0], h[1] + d[1]) for a, d in sp.DIRS.items()}
-    far = {a: (h[0] + 2 * d[0], h[1] + 2 * d[1]) for a, d in sp.DIRS.items()}
-    states = []
-    for a in range(1, 5):
-        for b in range(a + 1, 5):
-            blockers = [tgt[c] for c in range(1, 5) if c not in (a, b)]
-            states.append(_st([[h], blockers], [h, h]))
-            states.append(_st([[h], blockers], [far[a], far[b]]))
-            states.append(_st([[h], blockers], [far[b], far[a]]))
-            states.append(_st([[h], []], [far[a], far[b]]))          # nothing blocked: the tie decides alone
-    for a in range(1, 5):
-        states.append(_st([[h], [tgt[c] for c in range(1, 5) if c != a]], [h, far[a]]))
-    states.append(_st([[h], [tgt[c] for c in range(1, 5)]], [h, h]))                    # every move blocked by the other snake
-    states.append(_st([[h, tgt[1], tgt[2]], [tgt[3], tgt[4]]], [h, h]))                 # ... by both bodies
-    states.append(_st([[(0, 0), (1, 0)], [(0, 1)]], [h, h]))                            # ... by the wall and both bodies
-    states.append(_st([[h], []], [(h[0] + 2, h[1] + 2), (0, 0)]))                       # a diagonal fruit: moves 1 and 2 tie
-    states.append(_st([[h], []], [(h[0] - 2, h[1] - 2), (0, 0)]))                       # moves 3 and 4 tie
-    states.append(_st([[], []], [h, h]))                                                # empty bodies
-    return states
-
-
 def _install_and_check(cfg, states, policies):
-    env = _mk(dict(cfg, num_envs=len(states), seed=1, env_id_base=0, max_steps=2000))
-    from oracle.snake_oracle import flat_to_state, state_to_flat
-    env.reset()
-    for e, st in enumerate(states):
-        env.set_state_words(e, state_to_flat(st, cfg["n_snakes"]))
-    for e in (0, len(states) - 1):   # the state went in as it was built
-        got = flat_to_state(env.get_state_words(e))
-        assert got["snakes"] == states[e]["snakes"] and got["fruits"] == states[e]["fruits"]
+    env = gh.install(cfg, states)
     for pol in policies:
         _check_call(env, pol, states, what=(cfg["rules"], cfg["dim"]))
     return env
@@ -252,9 +112,9 @@ def _install_and_check(cfg, states, policies):
 @pytest.mark.parametrize("ns", [1, 2, 3])
 def test_hand_built_snake_env_states(dim, ns):
     rng = np.random.default_rng([dim, ns])
-    states = _border_states(dim, ns, ns, rng) + _random_states(dim, ns, ns, rng, 60)
+    states = bs.border_states(dim, ns, ns, rng) + bs.random_states(dim, ns, ns, rng, 60)
     if ns == 2 and dim >= 6:
-        states += _tie_states(dim)
+        states += bs.tie_states(dim)
     pols = ["safe_greedy"] + (["hamiltonian"] if dim % 2 == 0 else [])
     _install_and_check(dict(rules=0, dim=dim, n_snakes=ns, n_fruits=ns), states, pols).close()
 
@@ -278,7 +138,7 @@ def test_hand_built_adversarial_states_with_long_fruit_lists(dim):
                 states.append(_st([[h], [(0, dim - 1)], []], fl))
         states.append(_st([[h], [], []], [tuple(int(v) for v in rng.integers(-1, dim + 1, 2)) for _ in range(n_list)]))
     assert sum(1 for _, n, at in nearest if n > 64 and at >= 64) >= 6
-    states += _random_states(dim, 3, 90, rng, 40, fruit_lo=-1, fruit_hi=dim + 1)
+    states += bs.random_states(dim, 3, 90, rng, 40, fruit_lo=-1, fruit_hi=dim + 1)
     pols = ["safe_greedy"] + (["hamiltonian"] if dim % 2 == 0 else [])
     env = _install_and_check(dict(rules=2, dim=dim, n_snakes=3, n_fruits=3), states, pols)
     # the nearest-fruit cases once more, stated without the helper: the fruit ON the target of move a wins
@@ -294,7 +154,7 @@ def test_hand_built_new_world_states(nf, ns):
     """n_fruits 0 and 32, four snakes, stacked duplicate cells, bodies kept after a self-hit (alive False)."""
     dim = 10
     rng = np.random.default_rng([nf, ns])
-    states = _border_states(dim, ns, nf, rng) + _random_states(dim, ns, nf, rng, 60, dup=True)
+    states = bs.border_states(dim, ns, nf, rng) + bs.random_states(dim, ns, nf, rng, 60, dup=True)
     for st in states[::3]:   # every third state: some snakes dead with their bodies kept
         st["alive"] = [bool(rng.integers(0, 2)) for _ in range(ns)]
         st["in_dead"] = [not a and bool(rng.integers(0, 2)) for a in st["alive"]]
@@ -304,17 +164,6 @@ def test_hand_built_new_world_states(nf, ns):
     _install_and_check(dict(rules=1, dim=dim, n_snakes=ns, n_fruits=nf), states, ["safe_greedy", "hamiltonian"]).close()
 
 
-def _cycle(dim):
-    """The cells of scripted_play's Hamiltonian cycle of an even board, from (0, 0)."""
-    tab, c, out = sp.hamiltonian_table(dim), (0, 0), []
-    for _ in range(dim * dim):
-        out.append(c)
-        d = sp.DIRS[tab[c[0]][c[1]]]
-        c = (c[0] + d[0], c[1] + d[1])
-    assert c == (0, 0) and len(set(out)) == dim * dim
-    return out
-
-
 @pytest.mark.parametrize("rules,dim,ns", [(0, 10, 2), (0, 19, 3), (1, 12, 2), (2, 10, 3)])
 def test_blocking_piece_in_the_overflow_ring(rules, dim, ns):
     """Bodies of more than 64 cells laid along the Hamiltonian cycle with the head in the return lane (column 0): the
@@ -322,21 +171,7 @@ def test_blocking_piece_in_the_overflow_ring(rules, dim, ns):
     and the same bodies cut to 64 pieces, where that move is open.  Installed in the library and the oracle alike, then
     both are stepped (the overflow ring's head moves) and compared after the install and after every step."""
     from oracle.snake_oracle import state_to_flat
-    d = dim - dim % 2
-    cyc = _cycle(d)
-    N = d * d
-    states = []
-    for y in (1, 2, 3):
-        k = N - y                                   # cyc[k] = (0, y), on the way up the return lane
-        assert cyc[k] == (0, y)
-        far = (k - cyc.index((1, y))) % N           # piece index of (1, y) in a body whose head is cyc[k]
-        for n in sorted({far + 1, far + 4, min(far + 20, N - 8)} | {64}):
-            if n < 64 or n > N - 8:
-                continue
-            body = [cyc[(k - i) % N] for i in range(n)]
-            free = [c for c in cyc if c not in set(body)]
-            others = [[free[3 + s]] for s in range(ns - 1)]
-            states.append(_st([body] + others, [free[-1 - s] for s in range(ns)]))
+    states = bs.return_lane_states(dim, ns)
     cfg = dict(rules=rules, dim=dim, n_snakes=ns, n_fruits=ns, num_envs=len(states), seed=2, env_id_base=0, max_steps=2000,
                policy="safe_greedy")
     env = _mk(cfg)
@@ -366,21 +201,6 @@ def test_blocking_piece_in_the_overflow_ring(rules, dim, ns):
 
 
 # ------------------------------------------------------------------------------------------ 4. scale and layout
-def _play_random(env, ora, steps, rng, threads=16, p_greedy=0.0):
-    """Seeded random play of both (random play dies young, which keeps resets in the picture); outputs compared."""
-    import torch
-    for t in range(steps):
-        act = rng.integers(0, 5, (env.num_envs, env.n_snakes)).astype(np.int32)
-        _, rew, done, _ = env.step_device(torch.from_numpy(act).to(env.device))
-        _, o_rew, o_done, *_ = ora.step(act, threads=threads, want_obs=False)
-        assert np.array_equal(done.cpu().numpy(), o_done) and np.array_equal(rew.cpu().numpy(), o_rew), t
-
-
-def _states(ora):
-    read = sp._StateReader(ora)
-    return [read(e) for e in range(ora.num_envs)]
-
-
 @pytest.mark.parametrize("n", [16384, 20000])
 def test_large_batches_compare_every_env(n):
     cfg = dict(_cfg("S19x3"), num_envs=n, seed=21, env_id_base=7)
@@ -502,20 +322,20 @@ def test_outputs_guards_and_policy_none(n):
     states = _states(ora)
     want_a, want_m = expected("safe_greedy", states, 10, 4)
     for stride in (4, 6):
-        buf = Guarded(env, stride)
+        buf = gh.action_buffers(env, stride)
         # the mask alone (MSNAKE_POLICY_NONE): no action word is written
         out, safe = env.scripted_actions_device(None, out=buf.act, safe_out=buf.safe)
-        assert (out.cpu().numpy() == buf.fill).all() and np.array_equal(safe.cpu().numpy(), want_m) and buf.guards_intact()
+        assert (out.cpu().numpy() == FILL).all() and np.array_equal(safe.cpu().numpy(), want_m) and buf.guards_intact()
         assert np.array_equal(env.safe_moves_device().cpu().numpy(), want_m)
         # an empty selection with a mask: the same
-        buf.safe.fill_(0xA5)
+        buf.refill(["safe"])
         out, safe = env.scripted_actions_device("safe_greedy", snakes=[], out=buf.act, safe_out=buf.safe)
-        assert (out.cpu().numpy() == buf.fill).all() and np.array_equal(safe.cpu().numpy(), want_m)
+        assert (out.cpu().numpy() == FILL).all() and np.array_equal(safe.cpu().numpy(), want_m)
         # snakes 1 and 3 only, no mask
         out = env.scripted_actions_device("safe_greedy", snakes=[3, 1], out=buf.act)
         got = out.cpu().numpy()
-        assert np.array_equal(got[:, [1, 3]], want_a[:, [1, 3]]) and (got[:, [0, 2] + list(range(4, stride))] == buf.fill).all()
-        assert (buf.s_all.cpu().numpy()[:GUARD] == 0xA5).all() and buf.guards_intact()
+        assert np.array_equal(got[:, [1, 3]], want_a[:, [1, 3]]) and (got[:, [0, 2] + list(range(4, stride))] == FILL).all()
+        assert buf.guards_intact()
     # the env's own cached buffer: zero-filled, the same tensor on every call
     a = env.scripted_actions_device("hamiltonian", snakes=[2])
     assert a.data_ptr() == env.scripted_actions_device("hamiltonian", snakes=[2]).data_ptr()

@@ -4,6 +4,7 @@ import pandas as pd
 import pytest
 import torch
 
+from fake_envs import FakeEnv as _FakeEnv
 from msnake import selfplay
 
 
@@ -152,29 +153,6 @@ def test_json_and_tensorboard_sinks_round_trip(tmp_path):
             d = dict(fields(v))
             vals[d[1].decode()] = d[2]
         assert vals == {k: float(np.float32(v)) for k, v in row.items()}
-
-
-class _FakeEnv:
-    """CPU stand-in with the device-side surface learn() uses (reset_device / step_device)."""
-
-    def __init__(self, n=8, n_snakes=2, seed=0):
-        self.num_envs, self.n_snakes, self.obs_shape, self.device = n, n_snakes, (12, 12, 9), torch.device("cpu")
-        self.g = torch.Generator().manual_seed(seed)
-        self.len = torch.zeros(n, dtype=torch.int32)
-
-    def reset_device(self):
-        return torch.randint(0, 256, (self.num_envs,) + self.obs_shape, dtype=torch.uint8, generator=self.g)
-
-    def step_device(self, actions):
-        assert actions.shape == (self.num_envs, self.n_snakes) and actions.dtype == torch.int32
-        self.len += 1
-        done = (torch.rand(self.num_envs, generator=self.g) < 0.3)
-        rew = torch.randint(0, 2, (self.num_envs,), generator=self.g).float()
-        info = torch.zeros((self.num_envs, 4), dtype=torch.int32)
-        info[:, 0] = torch.full((self.num_envs,), 7.0).view(torch.int32)
-        info[:, 1] = self.len
-        self.len = torch.where(done, torch.zeros_like(self.len), self.len)
-        return self.reset_device(), rew, done.to(torch.uint8), info
 
 
 def test_checkpoints_save_load_and_resume(tmp_path):

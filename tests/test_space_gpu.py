@@ -9,14 +9,15 @@ ever comes from the library under test.  Every output sits between guard element
 import numpy as np
 import pytest
 
+import board_states as bs
+import gpu_harness as gh
 import scripted_play as sp
 import space_play as spp
-import test_scripted_gpu as tsg   # its state builders and guarded buffers (helpers only: nothing of it is collected here)
 
 pytestmark = pytest.mark.gpu
 
-GUARD = tsg.GUARD
-_st, _mk, _states = tsg._st, tsg._mk, tsg._states
+FILL = -77  # the sentinel of the action buffer (gpu_harness.action_spec)
+_st, _mk, _states, _install = bs.state, gh.make_env, gh.oracle_states, gh.install
 
 
 # ------------------------------------------------------------------------------------------ expectations
@@ -35,25 +36,9 @@ def _cfg(name, **kw):
     return dict(sp.SCENARIOS[name], eps=0.0, policy="space_greedy", **kw)
 
 
-class Guarded(tsg.Guarded):
-    """tsg.Guarded plus a uint16 [n, ns, 4] count buffer between guard elements, filled with the sentinel 0xA5A5."""
-
-    def __init__(self, env, stride=None, fill=-77):
-        import torch
-        super().__init__(env, stride, fill)
-        n, ns = env.num_envs, env.n_snakes
-        self.c_all = torch.full((n * ns * 4 + 2 * GUARD,), 0xA5A5 - 0x10000, dtype=torch.int16, device=env.device)
-        self.space = self.c_all[GUARD:GUARD + n * ns * 4].view(torch.uint16).view(n, ns, 4)
-
-    def counts(self):
-        return self.c_all.cpu().numpy().view(np.uint16)[GUARD:-GUARD].reshape(self.space.shape)
-
-    def refill(self):
-        self.a_all.fill_(self.fill), self.s_all.fill_(0xA5), self.c_all.fill_(0xA5A5 - 0x10000)
-
-    def guards_intact(self):
-        c = self.c_all.cpu().numpy().view(np.uint16)
-        return super().guards_intact() and (c[:GUARD] == 0xA5A5).all() and (c[-GUARD:] == 0xA5A5).all()
+def Guarded(env, stride=None):
+    """Actions, mask and a uint16 [n, ns, 4] count buffer `space`, each between guard elements."""
+    return gh.GuardedOutputs(env.device, dict(gh.action_spec(env, stride), **gh.count_spec(env, "space")))
 
 
 def _check_call(env, states, buf=None, what=""):
@@ -62,7 +47,7 @@ def _check_call(env, states, buf=None, what=""):
     buf = buf or Guarded(env)
     want_a, want_m, want_c = expected(states, dim, ns)
     out, safe, space = env.scripted_actions_device("space_greedy", out=buf.act, safe_out=buf.safe, space_out=buf.space)
-    got_a, got_m, got_c = out.cpu().numpy()[:, :ns], safe.cpu().numpy(), buf.counts()
+    got_a, got_m, got_c = out.cpu().numpy()[:, :ns], safe.cpu().numpy(), buf.host("space")
     bad = np.argwhere(got_c != want_c)
     assert bad.size == 0, (what, "space", bad[:5].tolist(), got_c[bad[0][0]].tolist(), want_c[bad[0][0]].tolist(), states[bad[0][0]])
     bad = np.argwhere(got_m != want_m)
@@ -73,42 +58,14 @@ def _check_call(env, states, buf=None, what=""):
     return want_a
 
 
-def _install(cfg, states):
-    from oracle.snake_oracle import flat_to_state, state_to_flat
-    env = _mk(dict(cfg, num_envs=len(states), seed=1, env_id_base=0, max_steps=2000))
-    env.reset()
-    for e, st in enumerate(states):
-        env.set_state_words(e, state_to_flat(st, cfg["n_snakes"]))
-    for e in (0, len(states) - 1):   # the state went in as it was built
-        got = flat_to_state(env.get_state_words(e))
-        assert got["snakes"] == states[e]["snakes"] and got["fruits"] == states[e]["fruits"]
-    return env
-
-
 # ------------------------------------------------------------------------------------------ 1. hand-built states
-def _dense_states(dim, ns, nf, rng, count, fruit_lo=0, fruit_hi=None):
-    """Boards with 25 .. 65 % of their cells in bodies (many separate regions, pockets of every size), dealt to the
-    snakes at random; heads anywhere, sometimes stacked on a body.  Bodies reach the overflow ring on boards >= 19."""
-    fruit_hi = dim if fruit_hi is None else fruit_hi
-    cells = [(x, y) for x in range(dim) for y in range(dim)]
-    states = []
-    for _ in range(count):
-        k = int(rng.uniform(0.25, 0.65) * dim * dim)
-        pick = [cells[i] for i in rng.permutation(len(cells))[:k]]
-        cuts = sorted(int(v) for v in rng.integers(0, k + 1, ns - 1))
-        bodies = [pick[a:b] for a, b in zip([0] + cuts, cuts + [k])]
-        fruits = [tuple(int(v) for v in rng.integers(fruit_lo, fruit_hi, 2)) for _ in range(nf)]
-        states.append(_st(bodies, fruits))
-    return states
-
-
 @pytest.mark.parametrize("dim", [2, 3, 6, 19, 32, 33, 62])
 def test_hand_built_snake_env_states(dim):
     """Border and corner heads, heads at -1 / dim, random bodies, stacked duplicates, empty bodies, dense boards."""
     ns = 3
     rng = np.random.default_rng([7, dim])
-    states = tsg._border_states(dim, ns, ns, rng) + tsg._random_states(dim, ns, ns, rng, 30, dup=True)
-    states += _dense_states(dim, ns, ns, rng, 30 if dim < 62 else 12)
+    states = bs.border_states(dim, ns, ns, rng) + bs.random_states(dim, ns, ns, rng, 30, dup=True)
+    states += bs.dense_states(dim, ns, ns, rng, 30 if dim < 62 else 12)
     states.append(_st([[], [], []], [(0, 0)] * ns))
     env = _install(dict(rules=0, dim=dim, n_snakes=ns, n_fruits=ns), states)
     _check_call(env, states, what=("snake_env", dim))
@@ -120,8 +77,8 @@ def test_hand_built_new_world_states_with_four_snakes(dim):
     """Four snakes, some dead with their bodies kept (alive False, in and out of dead_snakes), stacked duplicates."""
     ns, nf = 4, 5
     rng = np.random.default_rng([8, dim])
-    states = tsg._border_states(dim, ns, nf, rng) + tsg._random_states(dim, ns, nf, rng, 30, dup=True)
-    states += _dense_states(dim, ns, nf, rng, 30)
+    states = bs.border_states(dim, ns, nf, rng) + bs.random_states(dim, ns, nf, rng, 30, dup=True)
+    states += bs.dense_states(dim, ns, nf, rng, 30)
     for st in states[::2]:
         st["alive"] = [bool(rng.integers(0, 2)) for _ in range(ns)]
         st["in_dead"] = [not a and bool(rng.integers(0, 2)) for a in st["alive"]]
@@ -143,7 +100,7 @@ def test_hand_built_adversarial_states_with_long_fruit_lists(dim):
     fcap = (3 + 3 * (dim * dim + 2) + 63) // 64 * 64      # the handle's fruit-list capacity
     states = []
     for n_list in (0, 1, 63, 64, 65, min(130, fcap - 3), fcap):   # (dim 6: the capacity is 128 entries)
-        for st in _dense_states(dim, ns, n_list, rng, 5, fruit_lo=-1, fruit_hi=dim + 1):
+        for st in bs.dense_states(dim, ns, n_list, rng, 5, fruit_lo=-1, fruit_hi=dim + 1):
             states.append(st)
     h = (dim // 2, dim // 2)
     first = len(states)
@@ -186,7 +143,7 @@ def test_serpentine_mazes(dim, transposed):
     env = _install(dict(rules=0, dim=dim, n_snakes=2, n_fruits=2), states)
     buf = Guarded(env)
     want = _check_call(env, states, buf, what=("maze", dim, transposed))
-    got = buf.counts()
+    got = buf.host("space")
     for e, (a, b) in enumerate(sizes):      # the closed form, without the helper
         assert sorted(v for v in got[e, 0].tolist() if v) == sorted(v for v in (a, b) if v), (e, a, b, got[e].tolist())
     # the stack of duplicates is longer than the smaller part: the move into the larger part, away from the fruit
@@ -198,44 +155,13 @@ def test_serpentine_mazes(dim, transposed):
 
 
 # ------------------------------------------------------------------------------------------ 3. overflow ring
-def _overflow_states(dim, ns):
-    """The bodies of test_scripted_gpu.test_blocking_piece_in_the_overflow_ring, laid along the Hamiltonian cycle with
-    the head in the return lane (the piece beside the head has an index >= 64); on even boards also a body whose
-    pieces >= 64 are a wall: it covers row 1 over columns 1..dim-1 first and then 64 + 2 more cells of the cycle, so
-    that snake 1's head at (0, 1) sees the cells above the wall by move 4 and the cells below it by move 2."""
-    d = dim - dim % 2
-    cyc = tsg._cycle(d)
-    N = d * d
-    states = []
-    for y in (1, 2, 3):
-        k = N - y
-        far = (k - cyc.index((1, y))) % N
-        for n in sorted({far + 1, far + 4, min(far + 20, N - 8)} | {64}):
-            if n < 64 or n > N - 8:
-                continue
-            body = [cyc[(k - i) % N] for i in range(n)]
-            free = [c for c in cyc if c not in set(body)]
-            others = [[free[3 + s]] for s in range(ns - 1)]
-            states.append(_st([body] + others, [free[-1 - s] for s in range(ns)]))
-    walled = 0
-    if dim % 2 == 0:
-        t0 = cyc.index((dim - 1, 1))
-        for extra in (2, 5):
-            n = 64 + (dim - 1) + extra
-            body = [cyc[t0 + n - 1 - i] for i in range(n)]             # the tail (dim-1, 1), the head n - 1 cells further on
-            assert body[-1] == (dim - 1, 1) and all(c[0] >= 1 for c in body) and body.index((1, 1)) >= 64
-            states.append(_st([body, [(0, 1)]] + [[]] * (ns - 2), [(0, 0)] * ns))
-            walled += 1
-    return states, walled
-
-
 @pytest.mark.parametrize("rules,dim,ns", [(0, 10, 2), (0, 19, 3), (1, 12, 2), (2, 10, 3), (0, 20, 3)])
 def test_separating_piece_in_the_overflow_ring(rules, dim, ns):
     """Pieces with an index >= 64 block a move or wall two regions off.  Installed in the library and the oracle alike,
     compared after the install and after each of a few steps under space_greedy."""
     import torch
     from oracle.snake_oracle import state_to_flat
-    states, walled = _overflow_states(dim, ns)
+    states, walled = bs.overflow_states(dim, ns)
     for st in states[len(states) - walled:]:     # the wall: two regions of different sizes; one region without the pieces >= 64
         full = spp.np_space(st, dim, ns)[1]
         cut = spp.np_space(dict(st, snakes=[b[:64] for b in st["snakes"]]), dim, ns)[1]
@@ -263,44 +189,17 @@ def test_separating_piece_in_the_overflow_ring(rules, dim, ns):
 
 
 # ------------------------------------------------------------------------------------------ 4. closed loop
-def _closed_loop(cfg, env, steps, control=None, stride=None, obs_every=50):
-    """The oracle is the master: at every step the helpers' actions, masks and counts on the oracle's state are compared
-    with the library's for every env, snake and move, both are stepped with the helper's actions, and the step outputs
-    are compared.  control=(rng, snakes): only `snakes` are scripted, the other columns carry seeded random actions."""
-    import torch
-    E, ns, dim = cfg["num_envs"], cfg["n_snakes"], cfg["dim"]
-    ora = sp.make_oracle(cfg)
-    assert np.array_equal(env.reset(), ora.reset())
-    buf = Guarded(env, stride)
-    episodes = 0
-    for t in range(steps):
-        want_a, want_m, want_c = expected(_states(ora), dim, ns)
-        snakes = None
-        if control is not None:
-            rng, snakes = control
-            rand = rng.integers(0, 5, (E, buf.stride)).astype(np.int32)
-            rand[:, ns:] = -5 - t % 3                              # surplus columns: never written
-            buf.act.copy_(torch.from_numpy(rand).to(env.device))
-            keep = [s for s in range(ns) if s not in snakes]
-            want_a[:, keep] = rand[:, keep]
-        out, safe, _ = env.scripted_actions_device("space_greedy", snakes=snakes, out=buf.act, safe_out=buf.safe, space_out=buf.space)
-        got = out.cpu().numpy()
-        assert np.array_equal(got[:, :ns], want_a), (t, np.argwhere(got[:, :ns] != want_a)[:4].tolist())
-        if control is not None:
-            assert np.array_equal(got[:, ns:], rand[:, ns:]), t
-        assert np.array_equal(safe.cpu().numpy(), want_m), (t, "mask")
-        got_c = buf.counts()
-        assert np.array_equal(got_c, want_c), (t, "space", np.argwhere(got_c != want_c)[:4].tolist())
-        obs, rew, done, info = env.step_device(out)
-        o_obs, o_rew, o_done, o_ns, _, _ = ora.step(want_a)
-        assert np.array_equal(rew.cpu().numpy(), o_rew) and np.array_equal(done.cpu().numpy(), o_done), t
-        assert np.array_equal(info.cpu().numpy()[:, 2], o_ns), t
-        if t % obs_every == 0 or t == steps - 1:
-            assert np.array_equal(obs.cpu().numpy(), o_obs), t
-        episodes += int(o_done.sum())
-    assert buf.guards_intact()
-    assert env.stats()["errors"] == 0
-    return episodes
+def _call(env, buf, snakes=None):
+    out, safe, _ = env.scripted_actions_device("space_greedy", snakes=snakes, out=buf.act, safe_out=buf.safe, space_out=buf.space)
+    return out, safe, buf.host("space")
+
+
+def _closed_loop(cfg, env, steps, **kw):
+    """gpu_harness.closed_loop under space_greedy with all three outputs; returns the number of episodes that ended."""
+    episodes = []
+    gh.closed_loop(cfg, env, _call, lambda states: expected(states, cfg["dim"], cfg["n_snakes"]), steps, buffers=Guarded,
+                   observe=lambda t, states, wants, o_done, o_el: episodes.append(int(o_done.sum())), **kw)
+    return sum(episodes)
 
 
 @pytest.mark.parametrize("name,steps", [("S19x3", 150), ("A10x3", 150), ("N10x4", 100)])
@@ -327,7 +226,7 @@ def test_batch_sizes(n):
     cfg = _cfg("N10x4", num_envs=n)
     env, ora = _mk(cfg), sp.make_oracle(cfg)
     env.reset(), ora.reset()
-    tsg._play_random(env, ora, 6, np.random.default_rng(n), threads=1)
+    gh.play_random(env, ora, 6, np.random.default_rng(n), threads=1)
     _check_call(env, _states(ora), what=n)
     env.close()
 
@@ -385,37 +284,37 @@ def test_each_output_alone_and_all_together(stride):
     cfg = _cfg("N10x4", num_envs=13)
     env, ora = _mk(cfg), sp.make_oracle(cfg)
     env.reset(), ora.reset()
-    tsg._play_random(env, ora, 6, np.random.default_rng(stride), threads=1)
+    gh.play_random(env, ora, 6, np.random.default_rng(stride), threads=1)
     states = _states(ora)
     want_a, want_m, want_c = expected(states, 10, 4)
     buf = Guarded(env, stride)
-    untouched = lambda: (buf.a_all.cpu().numpy() == buf.fill).all()
+    untouched = lambda: buf.untouched("act")
     # space_dev alone
     assert env.reachable_space_device(out=buf.space) is buf.space
-    assert np.array_equal(buf.counts(), want_c) and untouched() and (buf.s_all.cpu().numpy() == 0xA5).all() and buf.guards_intact()
+    assert np.array_equal(buf.host("space"), want_c) and untouched() and buf.untouched("safe") and buf.guards_intact()
     assert np.array_equal(env.reachable_space_device().cpu().numpy(), want_c)      # a fresh tensor of the env's
     # safe_dev alone (an empty selection): no action word and no count is written
     buf.refill()
     out, safe = env.scripted_actions_device("space_greedy", snakes=[], out=buf.act, safe_out=buf.safe)
-    assert np.array_equal(safe.cpu().numpy(), want_m) and untouched() and (buf.counts() == 0xA5A5).all() and buf.guards_intact()
+    assert np.array_equal(safe.cpu().numpy(), want_m) and untouched() and buf.untouched("space") and buf.guards_intact()
     # actions alone, snakes 3 and 1 only
     buf.refill()
     out = env.scripted_actions_device("space_greedy", snakes=[3, 1], out=buf.act)
     got = out.cpu().numpy()
-    assert np.array_equal(got[:, [1, 3]], want_a[:, [1, 3]]) and (got[:, [0, 2] + list(range(4, stride))] == buf.fill).all()
-    assert (buf.s_all.cpu().numpy() == 0xA5).all() and (buf.counts() == 0xA5A5).all() and buf.guards_intact()
+    assert np.array_equal(got[:, [1, 3]], want_a[:, [1, 3]]) and (got[:, [0, 2] + list(range(4, stride))] == FILL).all()
+    assert buf.untouched("safe") and buf.untouched("space") and buf.guards_intact()
     # all three, snake 2 only: the mask and the counts are written for every snake whatever the selection
     buf.refill()
     out, safe, space = env.scripted_actions_device("space_greedy", snakes=[2], out=buf.act, safe_out=buf.safe, space_out=buf.space)
     got = out.cpu().numpy()
-    assert np.array_equal(got[:, 2], want_a[:, 2]) and (got[:, [0, 1, 3] + list(range(4, stride))] == buf.fill).all()
-    assert np.array_equal(safe.cpu().numpy(), want_m) and np.array_equal(buf.counts(), want_c) and buf.guards_intact()
+    assert np.array_equal(got[:, 2], want_a[:, 2]) and (got[:, [0, 1, 3] + list(range(4, stride))] == FILL).all()
+    assert np.array_equal(safe.cpu().numpy(), want_m) and np.array_equal(buf.host("space"), want_c) and buf.guards_intact()
     # the results do not depend on which outputs are asked for
     for kw in (dict(safe_out=buf.safe), dict(space_out=buf.space), dict()):
         buf.refill()
         res = env.scripted_actions_device("space_greedy", out=buf.act, **kw)
         got = (res if not kw else res[0]).cpu().numpy()
-        assert np.array_equal(got[:, :4], want_a) and (got[:, 4:] == buf.fill).all() and buf.guards_intact(), kw
+        assert np.array_equal(got[:, :4], want_a) and (got[:, 4:] == FILL).all() and buf.guards_intact(), kw
     # the env's own cached action buffer, shared with the other policies
     a = env.scripted_actions_device("space_greedy", snakes=[2])
     assert a.data_ptr() == env.scripted_actions_device("safe_greedy", snakes=[1]).data_ptr()

@@ -10,7 +10,6 @@ import numpy as np
 import pytest
 
 import state_domain as sd
-from test_copy_envs_gpu import blob_words
 
 pytestmark = pytest.mark.gpu
 
@@ -34,7 +33,7 @@ class Both:
         assert sd.imports(self.ora, e, words) == 0
 
     def words(self):
-        return blob_words(self.env.get_state_all())
+        return sd.blob_words(self.env.get_state_all())
 
     def check_words(self, what, skip=()):
         for e, got in enumerate(self.words()):

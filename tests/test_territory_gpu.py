@@ -11,18 +11,21 @@ none of them ever comes from the library under test.  Every output sits between 
 import numpy as np
 import pytest
 
+import board_states as bs
+import gpu_harness as gh
 import scripted_play as sp
 import space_play as spp
 import territory_play as tp
-import test_scripted_gpu as tsg   # state builders and guarded buffers (helpers only: nothing of it is collected here)
-import test_space_gpu as tspg     # likewise: its count buffer, dense boards and overflow-ring bodies
 
 pytestmark = pytest.mark.gpu
 
-GUARD = tsg.GUARD
-_st, _mk, _states = tsg._st, tsg._mk, tsg._states
-_install = tspg._install
-Guarded = tspg.Guarded            # its uint16 [n, ns, 4] buffer `space` between guards takes the territory counts here
+FILL = -77  # the sentinel of the action buffer (gpu_harness.action_spec)
+_st, _mk, _states, _install = bs.state, gh.make_env, gh.oracle_states, gh.install
+
+
+def Guarded(env, stride=None):
+    """Actions, mask and a uint16 [n, ns, 4] count buffer `terr`, each between guard elements."""
+    return gh.GuardedOutputs(env.device, dict(gh.action_spec(env, stride), **gh.count_spec(env, "terr")))
 
 
 # ------------------------------------------------------------------------------------------ expectations
@@ -47,7 +50,8 @@ def _cfg(name, **kw):
 
 
 def _call(env, buf, snakes=None):
-    return env.scripted_actions_device("territory_greedy", snakes=snakes, out=buf.act, safe_out=buf.safe, territory_out=buf.space)
+    out, safe, _ = env.scripted_actions_device("territory_greedy", snakes=snakes, out=buf.act, safe_out=buf.safe, territory_out=buf.terr)
+    return out, safe, buf.host("terr")
 
 
 def _check_call(env, states, buf=None, what="", bfs_every=0):
@@ -56,7 +60,7 @@ def _check_call(env, states, buf=None, what="", bfs_every=0):
     buf = buf or Guarded(env)
     want_a, want_m, want_c = expected(states, dim, ns, bfs_every)
     out, safe, _ = _call(env, buf)
-    got_a, got_m, got_c = out.cpu().numpy()[:, :ns], safe.cpu().numpy(), buf.counts()
+    got_a, got_m, got_c = out.cpu().numpy()[:, :ns], safe.cpu().numpy(), buf.host("terr")
     bad = np.argwhere(got_c != want_c)
     assert bad.size == 0, (what, "territory", bad[:5].tolist(), got_c[bad[0][0]].tolist(), want_c[bad[0][0]].tolist(), states[bad[0][0]])
     bad = np.argwhere(got_m != want_m)
@@ -72,8 +76,8 @@ def _check_call(env, states, buf=None, what="", bfs_every=0):
 def test_hand_built_snake_env_states(dim, ns):
     """Border and corner heads, heads at -1 / dim, random bodies, stacked duplicates, empty bodies, boards 25 - 65 % full."""
     rng = np.random.default_rng([17, dim, ns])
-    states = tsg._border_states(dim, ns, ns, rng) + tsg._random_states(dim, ns, ns, rng, 30, dup=True)
-    states += tspg._dense_states(dim, ns, ns, rng, 30 if dim < 62 else 12)
+    states = bs.border_states(dim, ns, ns, rng) + bs.random_states(dim, ns, ns, rng, 30, dup=True)
+    states += bs.dense_states(dim, ns, ns, rng, 30 if dim < 62 else 12)
     states.append(_st([[] for _ in range(ns)], [(0, 0)] * ns))
     env = _install(dict(rules=0, dim=dim, n_snakes=ns, n_fruits=ns), states)
     _, _, want_c = _check_call(env, states, what=("snake_env", dim, ns), bfs_every=1 if dim <= 6 else 9 if dim < 62 else 25)
@@ -88,8 +92,8 @@ def test_hand_built_new_world_states_with_four_snakes():
     body is an opponent like any other."""
     dim, ns, nf = 10, 4, 5
     rng = np.random.default_rng([18, dim])
-    states = tsg._border_states(dim, ns, nf, rng) + tsg._random_states(dim, ns, nf, rng, 30, dup=True)
-    states += tspg._dense_states(dim, ns, nf, rng, 30)
+    states = bs.border_states(dim, ns, nf, rng) + bs.random_states(dim, ns, nf, rng, 30, dup=True)
+    states += bs.dense_states(dim, ns, nf, rng, 30)
     for st in states[::2]:
         st["alive"] = [bool(rng.integers(0, 2)) for _ in range(ns)]
         st["in_dead"] = [not a and bool(rng.integers(0, 2)) for a in st["alive"]]
@@ -110,7 +114,7 @@ def test_hand_built_adversarial_states_with_long_fruit_lists():
     fcap = (3 + 3 * (dim * dim + 2) + 63) // 64 * 64      # the handle's fruit-list capacity
     states = []
     for n_list in (0, 1, 63, 64, 65, fcap - 3, fcap):
-        states += tspg._dense_states(dim, ns, n_list, rng, 5, fruit_lo=-1, fruit_hi=dim + 1)
+        states += bs.dense_states(dim, ns, n_list, rng, 5, fruit_lo=-1, fruit_hi=dim + 1)
     h = (dim // 2, dim // 2)
     first = len(states)
     for a in (1, 2, 3, 4):                                # an open board: the fruit at list index 70 sits on the target of move a
@@ -178,7 +182,7 @@ def test_serpentine_mazes_entered_from_both_ends(dim, transposed):
     env = _install(dict(rules=0, dim=dim, n_snakes=2, n_fruits=2), states)
     buf = Guarded(env)
     _check_call(env, states, buf, what=("maze", dim, transposed), bfs_every=1)
-    got = buf.counts()
+    got = buf.host("terr")
     nz = lambda row: sorted(int(v) for v in row if v)                       # the closed forms, without the helper
     assert nz(got[0, 0]) == [(L - 2) // 2] and nz(got[0, 1]) == [(L - 2) // 2]
     assert nz(got[1, 0]) == [L - 1] and nz(got[1, 1]) == []
@@ -194,7 +198,7 @@ def test_separating_piece_in_the_overflow_ring(rules, dim, ns):
     the library and the oracle alike, compared after the install and after each of a few steps under territory_greedy."""
     import torch
     from oracle.snake_oracle import state_to_flat
-    states, walled = tspg._overflow_states(dim, ns)
+    states, walled = bs.overflow_states(dim, ns)
     cfg = dict(rules=rules, dim=dim, n_snakes=ns, n_fruits=ns, num_envs=len(states), seed=2, env_id_base=0, max_steps=2000,
                policy="territory_greedy")
     env, ora = _mk(cfg), sp.make_oracle(cfg)
@@ -218,44 +222,18 @@ def test_separating_piece_in_the_overflow_ring(rules, dim, ns):
 
 
 # ------------------------------------------------------------------------------------------ 5. closed loop
-def _closed_loop(cfg, env, steps, control=None, stride=None, obs_every=50):
-    """The oracle is the master: at every step the helpers' actions, masks and counts on the oracle's state are compared
-    with the library's for every env, snake and move, both are stepped with the helper's actions, and the step outputs
-    are compared.  control=(rng, snakes): only `snakes` are scripted, the other columns carry seeded random actions."""
-    import torch
-    E, ns, dim = cfg["num_envs"], cfg["n_snakes"], cfg["dim"]
-    ora = sp.make_oracle(cfg)
-    assert np.array_equal(env.reset(), ora.reset())
-    buf = Guarded(env, stride)
-    contested = 0
-    for t in range(steps):
-        want_a, want_m, want_c = expected(_states(ora), dim, ns)
-        contested += int(((((want_m[:, :, None] >> np.arange(1, 5)) & 1) == 1) & (want_c == 0)).sum())
-        snakes = None
-        if control is not None:
-            rng, snakes = control
-            rand = rng.integers(0, 5, (E, buf.stride)).astype(np.int32)
-            rand[:, ns:] = -5 - t % 3                              # surplus columns: never written
-            buf.act.copy_(torch.from_numpy(rand).to(env.device))
-            keep = [s for s in range(ns) if s not in snakes]
-            want_a[:, keep] = rand[:, keep]
-        out, safe, _ = _call(env, buf, snakes)
-        got = out.cpu().numpy()
-        assert np.array_equal(got[:, :ns], want_a), (t, np.argwhere(got[:, :ns] != want_a)[:4].tolist())
-        if control is not None:
-            assert np.array_equal(got[:, ns:], rand[:, ns:]), t
-        assert np.array_equal(safe.cpu().numpy(), want_m), (t, "mask")
-        got_c = buf.counts()
-        assert np.array_equal(got_c, want_c), (t, "territory", np.argwhere(got_c != want_c)[:4].tolist())
-        obs, rew, done, info = env.step_device(out)
-        o_obs, o_rew, o_done, o_ns, _, _ = ora.step(want_a)
-        assert np.array_equal(rew.cpu().numpy(), o_rew) and np.array_equal(done.cpu().numpy(), o_done), t
-        assert np.array_equal(info.cpu().numpy()[:, 2], o_ns), t
-        if t % obs_every == 0 or t == steps - 1:
-            assert np.array_equal(obs.cpu().numpy(), o_obs), t
-    assert buf.guards_intact()
-    assert env.stats()["errors"] == 0
-    return contested
+def _closed_loop(cfg, env, steps, **kw):
+    """gpu_harness.closed_loop under territory_greedy with all three outputs; returns the number of contested targets
+    (open moves that count 0) the play came across."""
+    contested = []
+
+    def observe(t, states, wants, o_done, o_el):
+        _, want_m, want_c = wants
+        contested.append(int(((((want_m[:, :, None] >> np.arange(1, 5)) & 1) == 1) & (want_c == 0)).sum()))
+
+    gh.closed_loop(cfg, env, _call, lambda states: expected(states, cfg["dim"], cfg["n_snakes"]), steps, buffers=Guarded,
+                   observe=observe, **kw)
+    return sum(contested)
 
 
 @pytest.mark.parametrize("name,steps", [("S19x3", 150), ("A10x3", 150), ("N10x4", 100)])
@@ -282,7 +260,7 @@ def test_batch_sizes(n):
     cfg = _cfg("N10x4", num_envs=n)
     env, ora = _mk(cfg), sp.make_oracle(cfg)
     env.reset(), ora.reset()
-    tsg._play_random(env, ora, 6, np.random.default_rng(n), threads=1)
+    gh.play_random(env, ora, 6, np.random.default_rng(n), threads=1)
     _check_call(env, _states(ora), what=n, bfs_every=16)
     env.close()
 
@@ -363,42 +341,42 @@ def test_each_output_alone_and_all_together(stride):
     cfg = _cfg("N10x4", num_envs=13)
     env, ora = _mk(cfg), sp.make_oracle(cfg)
     env.reset(), ora.reset()
-    tsg._play_random(env, ora, 6, np.random.default_rng(stride), threads=1)
+    gh.play_random(env, ora, 6, np.random.default_rng(stride), threads=1)
     states = _states(ora)
     want_a, want_m, want_c = expected(states, 10, 4, bfs_every=1)
     buf = Guarded(env, stride)
-    untouched = lambda: (buf.a_all.cpu().numpy() == buf.fill).all()
+    untouched = lambda: buf.untouched("act")
     pol = "territory_greedy"
     # territory_dev alone
-    assert env.territory_device(out=buf.space) is buf.space
-    assert np.array_equal(buf.counts(), want_c) and untouched() and (buf.s_all.cpu().numpy() == 0xA5).all() and buf.guards_intact()
+    assert env.territory_device(out=buf.terr) is buf.terr
+    assert np.array_equal(buf.host("terr"), want_c) and untouched() and buf.untouched("safe") and buf.guards_intact()
     assert np.array_equal(env.territory_device().cpu().numpy(), want_c)            # a fresh tensor of the env's
     # safe_dev alone (an empty selection): no action word and no count is written
     buf.refill()
     out, safe = env.scripted_actions_device(pol, snakes=[], out=buf.act, safe_out=buf.safe)
-    assert np.array_equal(safe.cpu().numpy(), want_m) and untouched() and (buf.counts() == 0xA5A5).all() and buf.guards_intact()
+    assert np.array_equal(safe.cpu().numpy(), want_m) and untouched() and buf.untouched("terr") and buf.guards_intact()
     # actions alone, snakes 3 and 1 only
     buf.refill()
     out = env.scripted_actions_device(pol, snakes=[3, 1], out=buf.act)
     got = out.cpu().numpy()
-    assert np.array_equal(got[:, [1, 3]], want_a[:, [1, 3]]) and (got[:, [0, 2] + list(range(4, stride))] == buf.fill).all()
-    assert (buf.s_all.cpu().numpy() == 0xA5).all() and (buf.counts() == 0xA5A5).all() and buf.guards_intact()
+    assert np.array_equal(got[:, [1, 3]], want_a[:, [1, 3]]) and (got[:, [0, 2] + list(range(4, stride))] == FILL).all()
+    assert buf.untouched("safe") and buf.untouched("terr") and buf.guards_intact()
     # all three, snake 2 only: the mask and the counts are written for every snake whatever the selection
     buf.refill()
-    out, safe, terr = env.scripted_actions_device(pol, snakes=[2], out=buf.act, safe_out=buf.safe, territory_out=buf.space)
+    out, safe, terr = env.scripted_actions_device(pol, snakes=[2], out=buf.act, safe_out=buf.safe, territory_out=buf.terr)
     got = out.cpu().numpy()
-    assert np.array_equal(got[:, 2], want_a[:, 2]) and (got[:, [0, 1, 3] + list(range(4, stride))] == buf.fill).all()
-    assert np.array_equal(safe.cpu().numpy(), want_m) and np.array_equal(buf.counts(), want_c) and buf.guards_intact()
+    assert np.array_equal(got[:, 2], want_a[:, 2]) and (got[:, [0, 1, 3] + list(range(4, stride))] == FILL).all()
+    assert np.array_equal(safe.cpu().numpy(), want_m) and np.array_equal(buf.host("terr"), want_c) and buf.guards_intact()
     # the mask and the counts without actions
     buf.refill()
-    out, safe, terr = env.scripted_actions_device(pol, snakes=[], out=buf.act, safe_out=buf.safe, territory_out=buf.space)
-    assert np.array_equal(safe.cpu().numpy(), want_m) and np.array_equal(buf.counts(), want_c) and untouched() and buf.guards_intact()
+    out, safe, terr = env.scripted_actions_device(pol, snakes=[], out=buf.act, safe_out=buf.safe, territory_out=buf.terr)
+    assert np.array_equal(safe.cpu().numpy(), want_m) and np.array_equal(buf.host("terr"), want_c) and untouched() and buf.guards_intact()
     # the results do not depend on which outputs are asked for
-    for kw in (dict(safe_out=buf.safe), dict(territory_out=buf.space), dict()):
+    for kw in (dict(safe_out=buf.safe), dict(territory_out=buf.terr), dict()):
         buf.refill()
         res = env.scripted_actions_device(pol, out=buf.act, **kw)
         got = (res if not kw else res[0]).cpu().numpy()
-        assert np.array_equal(got[:, :4], want_a) and (got[:, 4:] == buf.fill).all() and buf.guards_intact(), kw
+        assert np.array_equal(got[:, :4], want_a) and (got[:, 4:] == FILL).all() and buf.guards_intact(), kw
     # the env's own cached action buffer, shared with the other policies
     a = env.scripted_actions_device(pol, snakes=[2])
     assert a.data_ptr() == env.scripted_actions_device("space_greedy", snakes=[1]).data_ptr()
@@ -419,7 +397,7 @@ def test_the_call_changes_no_state():
         if t % 25 == 0:
             before, st_before = env.get_state_all().tobytes(), env.stats()
         _call(env, buf)
-        env.territory_device(out=buf.space)
+        env.territory_device(out=buf.terr)
         env.scripted_actions_device("territory_greedy", snakes=[1])
         if t % 25 == 0:
             assert env.get_state_all().tobytes() == before and env.stats() == st_before

@@ -15,12 +15,9 @@ the constant action 1: snakes die and envs reset, as in untrained play).  The ou
 armed tracker and only read the state, so every leg sees the same boards.  Descriptive: nothing gates on it.
     python tools/agents_cost.py            # writes profiles/agents_cost.json"""
 import argparse
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import cost_harness as ch
 
 
 def main():
@@ -29,21 +26,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 32768])
     ap.add_argument("--play-steps", type=int, default=300)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "agents_cost.json"))
+    ap.add_argument("--out", default=os.path.join(ch.ROOT, "profiles", "agents_cost.json"))
     args = ap.parse_args()
     import torch
-    import msnake
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1000.0 / args.calls
-
-    med = lambda v: [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)]
     res = {"device": torch.cuda.get_device_name(0), "config": "snake_env 19x19, 3 snakes", "calls_per_leg": args.calls,
            "rounds": args.rounds, "play_steps": args.play_steps,
            "unit": "graph_us: median (min, max) over the rounds, us per call",
@@ -51,12 +37,7 @@ def main():
            "batches": {}}
     S = 3
     for n in args.envs:
-        env = msnake.MultiSnakeVecEnv(n, dim=19, n_snakes=S, rules="snake_env", seed=0, auto_reset=False)
-        acts = torch.ones((n, S), dtype=torch.int32, device=env.device)
-        env.reset_device()
-        for _ in range(args.play_steps):
-            _, _, done, _ = env.step_device(env.scripted_actions_device("safe_greedy", out=acts))
-            env.reset_device(mask=done)
+        env, _ = ch.played_env(n, args.play_steps, masked_reset=True, n_snakes=S, auto_reset=False)
         stepper = env.clone(auto_reset=True)
         ones = torch.ones((n, S), dtype=torch.int32, device=env.device)
         zero_done = torch.zeros(n, dtype=torch.uint8, device=env.device)
@@ -82,37 +63,17 @@ def main():
             "msnake_step": (lambda: stepper.step_device(ones), int(stepper.obs_shape[0] * stepper.obs_shape[1] * stepper.obs_shape[2])),
         }
         blob = env.get_state_all().tobytes()
-        graphs = {}
-        side = torch.cuda.Stream()
-        for name, (fn, _) in legs.items():
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture wants
-                fn(), fn()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
-                for _ in range(args.calls):
-                    fn()
-            graphs[name] = gr
-        times = {k: [] for k in legs}
-        for _ in range(args.rounds):
-            for name in legs:
-                times[name].append(timed(graphs[name].replay))
-        assert env.get_state_all().tobytes() == blob and env.stats()["errors"] == 0   # every leg on `env` only read the state
+        times = ch.graph_legs({k: fn for k, (fn, _) in legs.items()}, args.calls, args.rounds)
+        ch.assert_unchanged(env, blob)   # every leg on `env` only read the state
         # a quiet step on an armed tracker: nothing eaten, nobody died, and the composition says the same
         c_rew, c_ate, c_died = composition()
         env.arm_agents_device()
         env.agent_outcomes_device(zero_done, rew, ate, flags, info)
         assert torch.equal(c_rew, rew) and torch.equal(c_ate.to(torch.uint8), ate) and not bool(c_died.any())
         assert torch.equal((flags & 1) != 0, after[..., 0] > 0) and not bool((flags & 4).any())
-        res["batches"][str(n)] = {k: {"graph_us": med(v), "bytes_per_env": legs[k][1]} for k, v in times.items()}
+        res["batches"][str(n)] = {k: {"graph_us": ch.med(t["graph_us"]), "bytes_per_env": legs[k][1]} for k, t in times.items()}
         env.close(), stepper.close()
-    text = json.dumps(res, indent=1)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
-    print(text)
+    ch.write_json(res, args.out)
 
 
 if __name__ == "__main__":

@@ -11,13 +11,10 @@ bytes_per_env is what each leg writes; the state it reads is the same for all.  
 gates on it.
     python tools/cells_cost.py            # writes profiles/cells_cost.json"""
 import argparse
-import json
 import math
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import cost_harness as ch
 
 
 def main():
@@ -26,32 +23,17 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 32768])
     ap.add_argument("--play-steps", type=int, default=300)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cells_cost.json"))
+    ap.add_argument("--out", default=os.path.join(ch.ROOT, "profiles", "cells_cost.json"))
     args = ap.parse_args()
     import torch
-    import msnake
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1000.0 / args.calls
-
-    med = lambda v: [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)]
     res = {"device": torch.cuda.get_device_name(0), "config": "snake_env 19x19, 3 snakes", "calls_per_leg": args.calls,
            "rounds": args.rounds, "play_steps": args.play_steps,
            "unit": "graph_us: median (min, max) over the rounds, us per call",
            "graph_us": "calls captured into one HIP graph and replayed (kernel cadence), HIP events",
            "batches": {}}
     for n in args.envs:
-        env = msnake.MultiSnakeVecEnv(n, dim=19, n_snakes=3, rules="snake_env", seed=0)
-        acts = torch.ones((n, 3), dtype=torch.int32, device=env.device)
-        env.reset_device()
-        for _ in range(args.play_steps):
-            env.step_device(env.scripted_actions_device("safe_greedy", out=acts))
+        env, _ = ch.played_env(n, args.play_steps)
         one = torch.empty((n, 1, 19, 19), dtype=torch.uint8, device=env.device)
         full = torch.empty((n, 3, 19, 19), dtype=torch.uint8, device=env.device)
         table = torch.empty((n, 3, 8), dtype=torch.int32, device=env.device)
@@ -63,33 +45,13 @@ def main():
             "msnake_render": (lambda: env.render_device(out=frame), math.prod(env.obs_shape)),
         }
         blob = env.get_state_all().tobytes()
-        graphs = {}
-        side = torch.cuda.Stream()
-        for name, (fn, _) in legs.items():
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture wants
-                fn(), fn()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
-                for _ in range(args.calls):
-                    fn()
-            graphs[name] = gr
-        times = {k: [] for k in legs}
-        for _ in range(args.rounds):
-            for name in legs:
-                times[name].append(timed(graphs[name].replay))
-        assert env.get_state_all().tobytes() == blob and env.stats()["errors"] == 0   # every leg only read the state
+        times = ch.graph_legs({k: fn for k, (fn, _) in legs.items()}, args.calls, args.rounds)
+        ch.assert_unchanged(env, blob)   # every leg only read the state
         # the planes are the frame: a cell of view 0 is black in the frame iff its code is 0
         assert torch.equal(full[:, :1], one) and torch.equal((frame[:, 1:-1, 1:-1, :3] != 0).any(-1), one[:, 0] != 0)
-        res["batches"][str(n)] = {k: {"graph_us": med(v), "bytes_per_env": legs[k][1]} for k, v in times.items()}
+        res["batches"][str(n)] = {k: {"graph_us": ch.med(t["graph_us"]), "bytes_per_env": legs[k][1]} for k, t in times.items()}
         env.close()
-    text = json.dumps(res, indent=1)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
-    print(text)
+    ch.write_json(res, args.out)
 
 
 if __name__ == "__main__":

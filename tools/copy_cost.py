@@ -14,13 +14,10 @@ so it is timed with the host clock around the pair, after a device synchronise: 
 The comparison is descriptive: nothing gates on it.
     python tools/copy_cost.py            # writes profiles/copy_cost.json"""
 import argparse
-import json
 import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import cost_harness as ch
 
 
 def main():
@@ -29,21 +26,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 32768])
     ap.add_argument("--play-steps", type=int, default=300)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "copy_cost.json"))
+    ap.add_argument("--out", default=os.path.join(ch.ROOT, "profiles", "copy_cost.json"))
     args = ap.parse_args()
     import torch
-    import msnake
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1000.0 / args.calls
-
-    med = lambda v: [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)]
     res = {"device": torch.cuda.get_device_name(0), "config": "snake_env 19x19, 3 snakes", "calls_per_leg": args.calls,
            "rounds": args.rounds, "play_steps": args.play_steps,
            "unit": "median (min, max) over the rounds; graph_us / call_us: us per call, host_ms: ms per round trip",
@@ -52,11 +38,7 @@ def main():
            "host_ms": "dst.set_state_all(src.get_state_all()): host clock around the blocking pair",
            "batches": {}}
     for n in args.envs:
-        src = msnake.MultiSnakeVecEnv(n, dim=19, n_snakes=3, rules="snake_env", seed=0)
-        acts = torch.ones((n, 3), dtype=torch.int32, device=src.device)
-        src.reset_device()
-        for _ in range(args.play_steps):
-            src.step_device(src.scripted_actions_device("safe_greedy", out=acts))
+        src, _ = ch.played_env(n, args.play_steps)
         dst = src.clone(seed=1, env_id_base=n)
         g = torch.Generator().manual_seed(n)
         perm = torch.randperm(n, generator=g).to(device=src.device, dtype=torch.int32)
@@ -70,43 +52,21 @@ def main():
         }
         blob = src.get_state_all()
         words = (len(blob) - 40 - 8 * (n + 1)) // 4
-        graphs = {}
-        side = torch.cuda.Stream()
-        for name, fn in legs.items():
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture wants
-                fn(), fn()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
-                for _ in range(args.calls):
-                    fn()
-            graphs[name] = gr
-        times = {k: {"graph_us": [], "call_us": []} for k in legs}
+        # the step leg moves the source: every leg starts from the same state
+        times = ch.graph_legs(legs, args.calls, args.rounds, restore=lambda: src.set_state_all(blob), eager=True)
         host = []
         for _ in range(args.rounds):
-            for name, fn in legs.items():
-                src.set_state_all(blob)   # the step leg moves the source: every leg starts from the same state
-                times[name]["graph_us"].append(timed(graphs[name].replay))
-                src.set_state_all(blob)
-                times[name]["call_us"].append(timed(lambda: [fn() for _ in range(args.calls)]))
-            src.set_state_all(blob)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             dst.set_state_all(src.get_state_all())
             torch.cuda.synchronize()
             host.append((time.perf_counter() - t0) * 1000.0)
-        assert dst.get_state_all().tobytes() == blob.tobytes() and dst.stats()["errors"] == 0
-        out = {k: {kind: med(v) for kind, v in t.items()} for k, t in times.items()}
-        out["host_round_trip"] = {"host_ms": med(host), "state_words": words}
+        ch.assert_unchanged(dst, blob)
+        out = {k: {kind: ch.med(v) for kind, v in t.items()} for k, t in times.items()}
+        out["host_round_trip"] = {"host_ms": ch.med(host), "state_words": words}
         res["batches"][str(n)] = out
         src.close(), dst.close()
-    text = json.dumps(res, indent=1)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
-    print(text)
+    ch.write_json(res, args.out)
 
 
 if __name__ == "__main__":

@@ -18,10 +18,9 @@ import argparse
 import json
 import math
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import cost_harness as ch
+
 RADIUS = 5
 
 
@@ -48,24 +47,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 32768])
     ap.add_argument("--play-steps", type=int, default=300)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "local_cost.json"))
+    ap.add_argument("--out", default=os.path.join(ch.ROOT, "profiles", "local_cost.json"))
     ap.add_argument("--merge", nargs="+", metavar="JSON", help="combine the files of several processes into --out and exit")
     args = ap.parse_args()
     if args.merge:
         return merge(args.merge, args.out)
     import torch
-    import msnake
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1000.0 / args.calls
-
-    med = lambda v: [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)]
     w2 = (2 * RADIUS + 1) ** 2
     res = {"device": torch.cuda.get_device_name(0), "config": f"snake_env 19x19, 3 snakes, radius {RADIUS}", "calls_per_leg": args.calls,
            "rounds": args.rounds, "play_steps": args.play_steps,
@@ -73,11 +61,7 @@ def main():
            "graph_us": "calls captured into one HIP graph and replayed (kernel cadence), HIP events",
            "batches": {}}
     for n in args.envs:
-        env = msnake.MultiSnakeVecEnv(n, dim=19, n_snakes=3, rules="snake_env", seed=0)
-        acts = torch.ones((n, 3), dtype=torch.int32, device=env.device)
-        env.reset_device()
-        for _ in range(args.play_steps):
-            env.step_device(env.scripted_actions_device("safe_greedy", out=acts))
+        env, acts = ch.played_env(n, args.play_steps)
         env.scripted_actions_device("safe_greedy", out=acts)      # the actions the step leg replays
         win3 = torch.empty((n, 3, 2 * RADIUS + 1, 2 * RADIUS + 1), dtype=torch.uint8, device=env.device)
         head3 = torch.empty((n, 3), dtype=torch.uint8, device=env.device)
@@ -92,40 +76,18 @@ def main():
             "msnake_step": (lambda: env.step_device(acts), math.prod(env.obs_shape)),
         }
         blob = env.get_state_all()
-        graphs = {}
-        side = torch.cuda.Stream()
-        for name, (fn, _) in legs.items():
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture wants
-                fn(), fn()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
-                for _ in range(args.calls):
-                    fn()
-            graphs[name] = gr
-        env.set_state_all(blob)                # the step leg's warm-up aside: back to the boards after the play
-        times = {k: [] for k in legs}
-        for _ in range(args.rounds):
-            for name in legs:
-                times[name].append(timed(graphs[name].replay))
-                if name == "msnake_step":
-                    env.set_state_all(blob)
-        assert env.get_state_all().tobytes() == blob.tobytes() and env.stats()["errors"] == 0
+        # (the step leg moves the envs: back to the boards after the play before every leg and behind the last)
+        times = ch.graph_legs({k: fn for k, (fn, _) in legs.items()}, args.calls, args.rounds, restore=lambda: env.set_state_all(blob))
+        ch.assert_unchanged(env, blob)
         # snake 0's window is the same whether it is rendered alone or with the others; the centre of a window is the head's
         # own cell, and walls are in sight
-        graphs["cells_all_views"].replay(), graphs["local_three_oriented"].replay(), graphs["local_one"].replay()
+        legs["cells_all_views"][0](), legs["local_three_oriented"][0](), legs["local_one"][0]()
         torch.cuda.synchronize()
         assert torch.equal(win3[:, :1], win1) and float((win3[:, :, RADIUS, RADIUS] == 3).float().mean()) > 0.5
         assert int((win3 == 6).sum()) > 0 and int(head3.max()) <= 3
-        res["batches"][str(n)] = {k: {"graph_us": med(v), "bytes_per_env": legs[k][1]} for k, v in times.items()}
+        res["batches"][str(n)] = {k: {"graph_us": ch.med(t["graph_us"]), "bytes_per_env": legs[k][1]} for k, t in times.items()}
         env.close()
-    text = json.dumps(res, indent=1)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
-    print(text)
+    ch.write_json(res, args.out)
 
 
 if __name__ == "__main__":

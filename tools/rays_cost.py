@@ -12,12 +12,10 @@ headings: 32 bytes per env), "local_three_r5" and "local_one_r5" (the radius-5 w
 is descriptive: nothing gates on it.
     python tools/rays_cost.py                      # writes profiles/rays_cost.json"""
 import argparse
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import cost_harness as ch
+
 RADIUS = 5
 
 
@@ -27,21 +25,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 32768])
     ap.add_argument("--play-steps", type=int, default=300)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rays_cost.json"))
+    ap.add_argument("--out", default=os.path.join(ch.ROOT, "profiles", "rays_cost.json"))
     args = ap.parse_args()
     import torch
-    import msnake
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1000.0 / args.calls
-
-    med = lambda v: [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)]
     w = 2 * RADIUS + 1
     res = {"device": torch.cuda.get_device_name(0), "config": f"snake_env 19x19, 3 snakes, window radius {RADIUS}",
            "calls_per_leg": args.calls, "rounds": args.rounds, "play_steps": args.play_steps,
@@ -49,11 +36,7 @@ def main():
            "graph_us": "calls captured into one HIP graph and replayed (kernel cadence), HIP events",
            "batches": {}}
     for n in args.envs:
-        env = msnake.MultiSnakeVecEnv(n, dim=19, n_snakes=3, rules="snake_env", seed=0)
-        acts = torch.ones((n, 3), dtype=torch.int32, device=env.device)
-        env.reset_device()
-        for _ in range(args.play_steps):
-            env.step_device(env.scripted_actions_device("safe_greedy", out=acts))
+        env, _ = ch.played_env(n, args.play_steps)
         u8 = lambda *shape: torch.empty((n,) + shape, dtype=torch.uint8, device=env.device)
         rays3, rays1, head3 = u8(3, 8, 4), u8(1, 8, 4), u8(3)
         win3, win1, whead3, full = u8(3, w, w), u8(1, w, w), u8(3), u8(3, 19, 19)
@@ -65,24 +48,8 @@ def main():
             "cells_three_views": (lambda: env.render_cells_device(out=full), 3 * 361),
         }
         blob = env.get_state_all()
-        graphs = {}
-        side = torch.cuda.Stream()
-        for name, (fn, _) in legs.items():
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture wants
-                fn(), fn()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
-                for _ in range(args.calls):
-                    fn()
-            graphs[name] = gr
-        times = {k: [] for k in legs}
-        for _ in range(args.rounds):
-            for name in legs:
-                times[name].append(timed(graphs[name].replay))
-        assert env.get_state_all().tobytes() == blob.tobytes() and env.stats()["errors"] == 0
+        times = ch.graph_legs({k: fn for k, (fn, _) in legs.items()}, args.calls, args.rounds)
+        ch.assert_unchanged(env, blob)
         # snake 0's rays are the same whether they are rendered alone or with the others; a snake with a body (the centre
         # of its window is not 0) sees a wall in every direction; the step ahead of a head agrees with the window's entry
         # there; the headings agree
@@ -93,13 +60,9 @@ def main():
         ahead = win3[:, :, RADIUS + 1, RADIUS]
         assert torch.equal(rays3[:, :, 0, 0] == 1, ahead == 6) and torch.equal(rays3[:, :, 0, 1] == 1, ahead == 1)
         assert torch.equal(head3, whead3)
-        res["batches"][str(n)] = {k: {"graph_us": med(v), "bytes_per_env": legs[k][1]} for k, v in times.items()}
+        res["batches"][str(n)] = {k: {"graph_us": ch.med(t["graph_us"]), "bytes_per_env": legs[k][1]} for k, t in times.items()}
         env.close()
-    text = json.dumps(res, indent=1)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
-    print(text)
+    ch.write_json(res, args.out)
 
 
 if __name__ == "__main__":

@@ -16,13 +16,11 @@ Two figures per leg, both from HIP events after a warm-up, legs alternating in o
             Python caller pays when nothing else is queued; mostly the host's submission rate.
 The step leg plays the constant action 1 (with auto reset), so over its CALLS calls the batch leaves the state the run
 is labelled with; the scripted legs read the restored state every time.  The state is restored before every leg.
-    python tools/scripted_cost.py > profiles/path_cost.json"""
+    python tools/scripted_cost.py --out profiles/path_cost.json"""
 import argparse
-import json
-import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import cost_harness as ch
 
 
 def serpentine_states(dim, transposed):
@@ -59,18 +57,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 32768])
     ap.add_argument("--play-steps", type=int, default=500)
+    ap.add_argument("--out", default=None, help="also write the JSON to this file")
     args = ap.parse_args()
     import torch
     import msnake
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1000.0 / args.calls
 
     res = {"device": torch.cuda.get_device_name(0), "config": "snake_env 19x19, 3 snakes", "calls_per_leg": args.calls,
            "rounds": args.rounds, "unit": "us per call: median (min, max) over the rounds",
@@ -117,32 +107,10 @@ def main():
         for state in ("fresh_reset", f"after_{args.play_steps}_greedy_steps"):
             for e in (env, env20):
                 e.reset_device()
-                if state != "fresh_reset":
-                    for _ in range(args.play_steps):
-                        e.step_device(e.scripted_actions_device("safe_greedy", out=acts))
+                ch.play(e, acts, 0 if state == "fresh_reset" else args.play_steps)
             blob = env.get_state_all()
-            graphs = {}
-            side = torch.cuda.Stream()
-            for name, fn in legs.items():
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture wants
-                    fn(), fn()
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    for _ in range(args.calls):
-                        fn()
-                graphs[name] = g
-            times = {k: {"graph_us": [], "call_us": []} for k in legs}
-            for _ in range(args.rounds):
-                for name, fn in legs.items():
-                    env.set_state_all(blob)
-                    times[name]["graph_us"].append(timed(graphs[name].replay))
-                    env.set_state_all(blob)
-                    times[name]["call_us"].append(timed(lambda: [fn() for _ in range(args.calls)]))
-            med = lambda v: [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)]
-            out[state] = {k: {kind: med(v) for kind, v in t.items()} for k, t in times.items()}
+            times = ch.graph_legs(legs, args.calls, args.rounds, restore=lambda: env.set_state_all(blob), eager=True)
+            out[state] = {k: {kind: ch.med(v) for kind, v in t.items()} for k, t in times.items()}
             print(f"{n} envs, {state}: done", file=sys.stderr, flush=True)
         res["batches"][str(n)] = out
         env.close(), env20.close()
@@ -170,26 +138,15 @@ def main():
                                  ("path_greedy", "path_greedy", {"path_out": space}),
                                  ("path_greedy+field", "path_greedy", {"path_out": space, "field_out": field})):
                 fn = lambda: env.scripted_actions_device(pol, out=acts, **kw)
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    fn(), fn()
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    for _ in range(args.calls):
-                        fn()
-                v = [timed(g.replay) for _ in range(args.rounds)]
+                v = ch.graph_legs({leg: fn}, args.calls, args.rounds)[leg]["graph_us"]
                 count = space.view(torch.int16).to(torch.int32) & 0xFFFF
                 if pol == "path_greedy":  # the longest finite path (MSNAKE_PATH_NONE is no count)
                     count = torch.where(count == 0xFFFF, torch.zeros_like(count), count)
-                out[name][leg] = {"graph_us": [round(sorted(v)[len(v) // 2], 3), round(min(v), 3), round(max(v), 3)],
-                                  "largest_count": int(count.max())}
+                out[name][leg] = {"graph_us": ch.med(v), "largest_count": int(count.max())}
             env.close(), src.close()
             print(f"{n} envs, worst case {name}: done", file=sys.stderr, flush=True)
         res["worst_case_62x62"][str(n)] = out
-    print(json.dumps(res, indent=1))
+    ch.write_json(res, args.out)
 
 
 if __name__ == "__main__":
