@@ -37,6 +37,9 @@
  *                      (Voronoi territory) -- with the counts as per-move features.
  *   msnake_path_actions: no reference counterpart either; the BFS distance to the nearest fruit around the bodies, per
  *                      move and as a whole field, and the opponent that forages by it.
+ *   msnake_timed_actions: no reference counterpart either; when each body cell frees up (from len, grow_to and the piece
+ *                      order of the state), the flood fill that may pass through a cell once it has, and the opponent
+ *                      that counts its room that way.
  *   msnake_copy_envs <- no reference counterpart (a reference env can only be re-created and replayed); the analogue is
  *                      ALE's cloneState / restoreState, batched and on the device: snapshot, fork and restore of envs
  *                      between two handles without the host round trip of msnake_get_state / msnake_set_state.
@@ -360,6 +363,45 @@ int msnake_territory_actions(msnake_handle h, uint32_t snake_mask, int32_t* acti
 #define MSNAKE_PATH_NONE 0xFFFFu
 int msnake_path_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride,
                         uint8_t* safe_dev, uint16_t* path_dev, uint16_t* field_dev, void* stream);
+
+/* Cell lifetimes, the timed reach of every move, and the opponent timed_greedy, in the terms of the four calls above
+ * (`used`, moves 1..4, free, open).  Here bodies are NOT static: a body cell can be entered once the piece lying there has
+ * moved on.  Neither the velocity nor the alive bit plays a part (a new_world body kept after a self-hit counts like any
+ * other).
+ * Piece lifetime: for snake s with body length len and grow_to as the canonical state gives them, piece i (0 the head,
+ * len - 1 the tail) has l(s, i) = min(0xFFFE, (len - i) + max(0, grow_to - len)), formed without 32-bit overflow
+ * (grow_to of an installed state may be 2^31 - 1).  Under new_world with the handle's n_fruits == 0 every piece has
+ * l = MSNAKE_LIFE_NEVER: there the rule set never pops.
+ * Cell lifetime: Life(c) = the maximum of l over all pieces of all snakes that lie on c, stacked duplicates included; 0
+ * for a cell with no piece, so Life(c) > 0 <=> c in `used`.  Pieces outside the grid are ignored.  If every snake moves
+ * on every step and nobody eats or dies, cell c is free of today's pieces after exactly Life(c) steps.  The step pops
+ * before it tests collisions, so entering a cell only when Life < t (below) is one step conservative, the convention
+ * by which `open` counts tails as used.
+ * Timed fill from the target T of an open move: V_1 = F_1 = {T}; for t = 2, 3, ...: F_t = { c in the grid : c not in
+ * V_(t-1), Life(c) < t, c 4-adjacent to a cell of F_(t-1) }, V_t = V_(t-1) + F_t; stop when F_t is empty.  Only the
+ * last front expands: a cell is taken once, at the first level that both reaches and admits it, and a cell skipped
+ * because it was still occupied can be taken later only from another, later front cell.  At most dim^2 levels.
+ * reach_dev (may be NULL): uint16 [num_envs][n_snakes][4], written for every snake whatever snake_mask is: entry m =
+ * |V| of the fill from the target of move m + 1; 0 when that move is not open or the body is empty.  So reach >= space
+ * of msnake_space_actions entry for entry, reach == 0 <=> the move is not open, and reach == space where every
+ * lifetime is MSNAKE_LIFE_NEVER.  At most 62^2.  2-byte aligned (MSNAKE_E_ALIGN otherwise).
+ * life_dev (may be NULL): uint16 [num_envs][dim][dim], entry [c0][c1] = Life((c0, c1)), the indexing of the
+ * msnake_render_cells planes and of field_dev.  2-byte aligned (MSNAKE_E_ALIGN otherwise).
+ * safe_dev (may be NULL): exactly what the four calls above write there.
+ * actions_dev: int32 [num_envs][action_stride]; entry s of every row is written for each s with bit s of
+ * snake_mask set, all other entries are left untouched.  The policy timed_greedy is space_greedy with the timed reach
+ * in place of the space: the action is 0 if the body is empty or no move is open; otherwise need = min(len, max over
+ * the open moves of reach), the eligible moves are the open moves with reach >= need, and the action is the first
+ * eligible move, in the order 1, 2, 3, 4, whose target has the strictly smallest L1 distance to any fruit of the
+ * state's fruit list (adversarial: the complete list; distance 0 when the list is empty).
+ * Like its siblings the call only reads the handle's state, draws no random numbers, allocates nothing, does not
+ * synchronise and adds nothing to env_steps; asynchronous on `stream`, and it can be captured into a HIP graph in
+ * front of the step.  MSNAKE_E_ARG, before any device work: a snake_mask bit >= n_snakes; actions_dev NULL or
+ * action_stride < n_snakes when snake_mask != 0; nothing to write (snake_mask 0, safe_dev, reach_dev and life_dev
+ * NULL). */
+#define MSNAKE_LIFE_NEVER 0xFFFFu
+int msnake_timed_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride,
+                         uint8_t* safe_dev, uint16_t* reach_dev, uint16_t* life_dev, void* stream);
 
 /* Copy env state from `src` into `dst` on the device: destination env e receives the state of source env
  * src_index_dev[e] (int32 [dst.num_envs], a device pointer).  A negative entry leaves destination env e completely

@@ -32,7 +32,9 @@ SPACE_POLICY = "space_greedy"  # no policy id: an entry point of its own (msnake
 TERRITORY_POLICY = "territory_greedy"  # likewise (msnake_territory_actions)
 PATH_POLICY = "path_greedy"  # likewise (msnake_path_actions)
 SCRIPTED_POLICY_NAMES = ("safe_greedy", "hamiltonian", SPACE_POLICY, TERRITORY_POLICY)  # the opponents selfplay.SCRIPTED_POLICIES names
-SCRIPTED_OPPONENT_NAMES = SCRIPTED_POLICY_NAMES + (PATH_POLICY,)  # every scripted opponent there is
+TIMED_POLICY = "timed_greedy"  # likewise (msnake_timed_actions)
+SCRIPTED_OPPONENT_NAMES = SCRIPTED_POLICY_NAMES + (PATH_POLICY,)  # the scripted opponents with static bodies
+SCRIPTED_PLAYER_NAMES = SCRIPTED_OPPONENT_NAMES + (TIMED_POLICY,)  # every scripted opponent there is
 AGENT_ARM = 1  # MSNAKE_AGENT_ARM: msnake_agent_outcomes writes the tracker from the state
 AGENT_ALIVE, AGENT_WAS_ALIVE, AGENT_DIED, AGENT_ENDED = 1, 2, 4, 8  # MSNAKE_AGENT_*: the bits of its flags output
 # the words of a tracker row: grow_to, alive, then the totals of the env's current episode
@@ -96,6 +98,9 @@ PROTOTYPES = {
     # h, snake_mask, actions_dev, action_stride, safe_dev, path_dev (uint16 [num_envs][n_snakes][4]),
     # field_dev (uint16 [num_envs][dim][dim]), stream
     "msnake_path_actions": (_int, [_vp, _u32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    # h, snake_mask, actions_dev, action_stride, safe_dev, reach_dev (uint16 [num_envs][n_snakes][4]),
+    # life_dev (uint16 [num_envs][dim][dim]), stream
+    "msnake_timed_actions": (_int, [_vp, _u32, _vp, _i32, _vp, _vp, _vp, _vp]),
     # h, flags (AGENT_ARM or 0), track_dev (int32 [num_envs][n_snakes][8]), done_dev (uint8 [num_envs]), rew_dev (float32
     # [num_envs][n_snakes]), ate_dev, flags_dev (uint8 [num_envs][n_snakes]), info_dev (int32 [num_envs][n_snakes][4]), stream
     "msnake_agent_outcomes": (_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

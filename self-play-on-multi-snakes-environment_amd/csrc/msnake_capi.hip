@@ -113,7 +113,7 @@ void fill_call(msnake::StepParams& p, const int32_t* actions, int32_t action_str
     p.obs = obs; p.rest.rew = rew; p.rest.done = done; p.rest.info = info;
 }
 
-// the arguments of a call that may write actions (msnake_scripted_ / _space_ / _territory_ / _path_actions); the last two count only if it does
+// the arguments of a call that may write actions (msnake_scripted_ / _space_ / _territory_ / _path_ / _timed_actions); the last two count only if it does
 int check_action_writer(const char* fn, int ns, bool writes_actions, uint32_t snake_mask, const int32_t* actions_dev, int32_t action_stride) {
     if (snake_mask >> ns) return fail(MSNAKE_E_ARG, "%s: snake_mask 0x%x has a bit >= n_snakes=%d", fn, snake_mask, ns);
     if (!writes_actions) return MSNAKE_OK;
@@ -532,6 +532,19 @@ int msnake_path_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_d
     DeviceGuard guard(h->cfg.device);
     return launched(msnake::launch_path(h->p, h->cfg.rules, snake_mask, actions_dev, action_stride, safe_dev, path_dev, field_dev,
                                         static_cast<hipStream_t>(stream)));
+}
+
+int msnake_timed_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride, uint8_t* safe_dev,
+                         uint16_t* reach_dev, uint16_t* life_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    if (int rc = check_action_writer("msnake_timed_actions", h->p.n_snakes, snake_mask != 0, snake_mask, actions_dev, action_stride)) return rc;
+    if (!snake_mask && !safe_dev && !reach_dev && !life_dev)
+        return fail(MSNAKE_E_ARG, "msnake_timed_actions: nothing to write (snake_mask 0, safe_dev, reach_dev and life_dev are NULL)");
+    if ((uintptr_t)reach_dev & 1) return fail(MSNAKE_E_ALIGN, "reach_dev must be 2-byte aligned");
+    if ((uintptr_t)life_dev & 1) return fail(MSNAKE_E_ALIGN, "life_dev must be 2-byte aligned");
+    DeviceGuard guard(h->cfg.device);
+    return launched(msnake::launch_timed(h->p, h->cfg.rules, snake_mask, actions_dev, action_stride, safe_dev, reach_dev, life_dev,
+                                         static_cast<hipStream_t>(stream)));
 }
 
 int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_index_dev, void* stream) {

@@ -218,6 +218,9 @@ hipError_t launch_territory(const StepParams& p, int rules, uint32_t snake_mask,
 // BFS distances to the fruits, per move and as a field, and the path_greedy opponent (msnake_path.inc); reads the handle's state only
 hipError_t launch_path(const StepParams& p, int rules, uint32_t snake_mask, int32_t* actions, int32_t action_stride, uint8_t* safe,
                        uint16_t* path, uint16_t* field, hipStream_t stream);
+// cell lifetimes, the timed reach of every move and the timed_greedy opponent (msnake_timed.inc); reads the handle's state only
+hipError_t launch_timed(const StepParams& p, int rules, uint32_t snake_mask, int32_t* actions, int32_t action_stride, uint8_t* safe,
+                        uint16_t* reach, uint16_t* life, hipStream_t stream);
 // env state of `src` into `dst`, one wave per destination env (msnake_copy.inc); src_index NULL = the identity.  Reads `src` only
 hipError_t launch_copy_envs(const StepParams& dst, const StepParams& src, int rules, const int32_t* src_index, hipStream_t stream);
 // the observation as cell codes and the per-snake table (msnake_cells.inc); view_mask 0 / snakes NULL = that output is not

@@ -162,8 +162,10 @@ def relative_to_absolute(rel, heading):
 # name -> (the env's bound C function, its name, the keywords of those outputs in the order of the C arguments)
 COUNT_POLICIES = {_capi.SPACE_POLICY: ("_space_fn", "msnake_space_actions", ("space_out",)),
                   _capi.TERRITORY_POLICY: ("_territory_fn", "msnake_territory_actions", ("territory_out",)),
-                  _capi.PATH_POLICY: ("_path_fn", "msnake_path_actions", ("path_out", "field_out"))}
-# output keyword -> the policy that writes it; every one is [num_envs, n_snakes, 4] but the field, [num_envs, dim, dim]
+                  _capi.PATH_POLICY: ("_path_fn", "msnake_path_actions", ("path_out", "field_out")),
+                  _capi.TIMED_POLICY: ("_timed_fn", "msnake_timed_actions", ("reach_out", "life_out"))}
+# output keyword -> the policy that writes it; every one is [num_envs, n_snakes, 4] but the field and the lifetimes,
+# [num_envs, dim, dim]
 COUNT_OUTPUTS = {kw: name for name, (_, _, kws) in COUNT_POLICIES.items() for kw in kws}
 
 # constructor arguments that may differ between the two handles of a device-side copy (include/msnake.h,
@@ -313,6 +315,7 @@ class MultiSnakeVecEnv:
         self._space_fn = self._L.msnake_space_actions
         self._territory_fn = self._L.msnake_territory_actions
         self._path_fn = self._L.msnake_path_actions
+        self._timed_fn = self._L.msnake_timed_actions
         self._cells_fn = self._L.msnake_render_cells
         self._local_fn = self._L.msnake_render_local
         self._rays_fn = self._L.msnake_render_rays
@@ -397,13 +400,13 @@ class MultiSnakeVecEnv:
         return obs, self._rew, self._done, self._info
 
     def _count_shape(self, kw):
-        if kw == "field_out":
+        if kw in ("field_out", "life_out"):
             return (self.num_envs, int(self.cfg.dim), int(self.cfg.dim))
         return (self.num_envs, self.n_snakes, 4)
 
     def scripted_actions_device(self, policy, snakes=None, out=None, safe_out=None, space_out=None, territory_out=None,
-                                path_out=None, field_out=None):
-        """Actions of a scripted policy ("safe_greedy", "hamiltonian", "space_greedy", "territory_greedy", "path_greedy", or None for the mask alone) for the
+                                path_out=None, field_out=None, reach_out=None, life_out=None):
+        """Actions of a scripted policy ("safe_greedy", "hamiltonian", "space_greedy", "territory_greedy", "path_greedy", "timed_greedy", or None for the mask alone) for the
         snakes in `snakes` (indices; default every snake), computed on the device from the env's current state.  They go to
         columns `snakes` of `out`, an int32 [num_envs, >= n_snakes] device tensor as step_device() takes it; its other
         columns are left as they are (out=None: a cached, zero-initialised [num_envs, n_snakes] tensor of the env).
@@ -420,9 +423,15 @@ class MultiSnakeVecEnv:
         around the bodies instead of the L1 distance, and plays space_greedy's move when no fruit can be reached; only
         with it, `path_out`, a uint16 [num_envs, n_snakes, 4] device tensor, gets the path lengths (see path_device)
         and `field_out`, a uint16 [num_envs, dim, dim] device tensor, the whole distance field (see
-        fruit_field_device).  The return order is actions, safe, path, field for those asked for."""
+        fruit_field_device).  The return order is actions, safe, path, field for those asked for.
+        "timed_greedy" (msnake_timed_actions) is space_greedy with the timed reach in place of the space: a flood fill
+        that may enter a body cell once the piece lying there has moved on; only with it, `reach_out`, a uint16
+        [num_envs, n_snakes, 4] device tensor, gets those counts (see timed_reach_device) and `life_out`, a uint16
+        [num_envs, dim, dim] device tensor, the lifetime of every cell (see cell_lifetimes_device).  The return order
+        is actions, safe, reach, life for those asked for."""
         torch = self._torch
-        given = {"space_out": space_out, "territory_out": territory_out, "path_out": path_out, "field_out": field_out}
+        given = {"space_out": space_out, "territory_out": territory_out, "path_out": path_out, "field_out": field_out,
+                 "reach_out": reach_out, "life_out": life_out}
         for kw, t in given.items():
             if t is not None and policy != COUNT_OUTPUTS[kw]:
                 raise ValueError(f"{kw} is written by policy {COUNT_OUTPUTS[kw]!r} only, got policy {policy!r}")
@@ -517,6 +526,21 @@ class MultiSnakeVecEnv:
         under a body and for a free cell from which no such fruit can be reached.  On the device; nothing is
         synchronised."""
         return self._counts_device("field_out", out)
+
+    def timed_reach_device(self, out=None):
+        """uint16 [num_envs, n_snakes, 4]: entry m of a snake is its timed reach behind move m + 1: the number of cells a
+        level-by-level flood fill from that move's target takes when level t may also enter a body cell whose lifetime
+        (cell_lifetimes_device) is below t; 0 when the move is not open or the body is empty.  Never below
+        reachable_space_device(), and equal to it where no body ever recedes.  On the device; nothing is synchronised."""
+        return self._counts_device("reach_out", out)
+
+    def cell_lifetimes_device(self, out=None):
+        """uint16 [num_envs, dim, dim]: entry [c0, c1] is the lifetime of cell (c0, c1), the indexing of
+        render_cells_device(): after how many steps the last body piece lying there will have moved on if every snake
+        keeps moving and nobody eats or dies: (len - i) + max(0, grow_to - len) for piece i, capped at 0xFFFE, the
+        maximum over stacked pieces; 0 for a cell under no body; 0xFFFF (msnake_timed_actions: MSNAKE_LIFE_NEVER) for
+        every body cell of a new_world handle without fruits.  On the device; nothing is synchronised."""
+        return self._counts_device("life_out", out)
 
     @property
     def cells_shape(self):

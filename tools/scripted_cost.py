@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of msnake_scripted_actions, msnake_space_actions, msnake_territory_actions and msnake_path_actions next to msnake_step on the same handle.  19x19x3 snake_env at
+"""Cost of msnake_scripted_actions, msnake_space_actions, msnake_territory_actions, msnake_path_actions and msnake_timed_actions next to msnake_step on the same handle.  19x19x3 snake_env at
 4 096 and 32 768 envs, on a freshly reset batch and 500 steps into safe_greedy play (longer bodies).  The Hamiltonian
 cycle needs an even board: its legs run on a 20x20 handle of the same batch, in the same kind of state.  The "->step"
 legs are one scripted call and one step per call (the self-play loop on the device).  `worst_case_62x62`: the flood
@@ -8,6 +8,9 @@ columns, nine head positions each), copied over the whole batch; the territory r
 snake is the opponent), and on `two_ends`, where two snakes enter the corridor from its two ends.  The fruits of these
 states lie on the corridor's first cell, so the BFS of msnake_path_actions walks the corridor from that end up to the
 head: with the field it runs to the end (up to 1 951 levels), without it it stops at the head's open target.
+The wall snake of these states has its natural lifetimes (grow_to = its length), so under msnake_timed_actions the walls
+dissolve from the tail while the fill runs; `lasting_walls_on_rows` / `_columns` are the same mazes with the wall's
+grow_to at 2^31 - 1 (every lifetime clamped high), where the timed fill is the corridor, level by level.
 
 Two figures per leg, both from HIP events after a warm-up, legs alternating in one process:
   graph_us: CALLS back-to-back calls captured into one HIP graph (a linear chain) and replayed: the kernel's cadence,
@@ -16,16 +19,16 @@ Two figures per leg, both from HIP events after a warm-up, legs alternating in o
             Python caller pays when nothing else is queued; mostly the host's submission rate.
 The step leg plays the constant action 1 (with auto reset), so over its CALLS calls the batch leaves the state the run
 is labelled with; the scripted legs read the restored state every time.  The state is restored before every leg.
-    python tools/scripted_cost.py --out profiles/path_cost.json"""
+    python tools/scripted_cost.py --out profiles/timed_cost.json"""
 import argparse
 import sys
 
 import cost_harness as ch
 
 
-def serpentine_states(dim, transposed):
+def serpentine_states(dim, transposed, wall_grow=None):
     """Canonical states of a two-snake snake_env: snake 1 is a serpentine wall (the odd rows, each with one gap at
-    alternating ends), snake 0 a single cell at nine places of the corridor."""
+    alternating ends; grow_to = wall_grow, by default its length), snake 0 a single cell at nine places of the corridor."""
     walls, path, right = [], [], True
     for y in range(dim):
         if y % 2 == 0:
@@ -39,7 +42,7 @@ def serpentine_states(dim, transposed):
         walls, path = [(y, x) for x, y in walls], [(y, x) for x, y in path]
     L = len(path)
     return [{"t": 0, "ctr": 0, "spare_fruits": 0, "ep_len": 0, "ep_return": 0.0, "fruits": [[0, 0], [0, 0]],
-             "snakes": [[list(path[i])], [list(c) for c in walls]], "vels": [[1, 0]] * 2, "grow_to": [1, len(walls)],
+             "snakes": [[list(path[i])], [list(c) for c in walls]], "vels": [[1, 0]] * 2, "grow_to": [1, wall_grow or len(walls)],
              "alive": [True] * 2, "in_dead": [False] * 2} for i in (0, 1, L // 8, L // 4, L // 3, L // 2, 2 * L // 3, L - 2, L - 1)]
 
 
@@ -79,6 +82,8 @@ def main():
         terr = torch.zeros((n, 3, 4), dtype=torch.uint16, device=env.device)
         path = torch.zeros((n, 3, 4), dtype=torch.uint16, device=env.device)
         field = torch.zeros((n, 19, 19), dtype=torch.uint16, device=env.device)
+        reach = torch.zeros((n, 3, 4), dtype=torch.uint16, device=env.device)
+        life = torch.zeros((n, 19, 19), dtype=torch.uint16, device=env.device)
         legs = {
             "safe_greedy": lambda: env.scripted_actions_device("safe_greedy", out=acts),
             "safe_greedy+mask": lambda: env.scripted_actions_device("safe_greedy", out=acts, safe_out=safe),
@@ -97,11 +102,17 @@ def main():
                                                                                field_out=field),
             "path_only": lambda: env.path_device(out=path),
             "field_only": lambda: env.fruit_field_device(out=field),
+            "timed_greedy": lambda: env.scripted_actions_device("timed_greedy", out=acts),
+            "timed_greedy+mask+reach+life": lambda: env.scripted_actions_device("timed_greedy", out=acts, safe_out=safe, reach_out=reach,
+                                                                                life_out=life),
+            "reach_only": lambda: env.timed_reach_device(out=reach),
+            "life_only": lambda: env.cell_lifetimes_device(out=life),
             "msnake_step": lambda: env.step_device(ones),
             "safe_greedy->step": lambda: env.step_device(env.scripted_actions_device("safe_greedy", out=acts)),
             "space_greedy->step": lambda: env.step_device(env.scripted_actions_device("space_greedy", out=acts)),
             "territory_greedy->step": lambda: env.step_device(env.scripted_actions_device("territory_greedy", out=acts)),
             "path_greedy->step": lambda: env.step_device(env.scripted_actions_device("path_greedy", out=acts)),
+            "timed_greedy->step": lambda: env.step_device(env.scripted_actions_device("timed_greedy", out=acts)),
         }
         out = {}
         for state in ("fresh_reset", f"after_{args.play_steps}_greedy_steps"):
@@ -118,9 +129,11 @@ def main():
     res["worst_case_62x62"] = {}
     for n in args.envs:
         out = {}
-        for name, transposed, ends in (("walls_on_rows", False, False), ("walls_on_columns", True, False),
-                                       ("two_ends_rows", False, True), ("two_ends_columns", True, True)):
-            states = serpentine_states(62, transposed)
+        for name, transposed, ends, wall_grow in (("walls_on_rows", False, False, None), ("walls_on_columns", True, False, None),
+                                                  ("two_ends_rows", False, True, None), ("two_ends_columns", True, True, None),
+                                                  ("lasting_walls_on_rows", False, False, 2 ** 31 - 1),
+                                                  ("lasting_walls_on_columns", True, False, 2 ** 31 - 1)):
+            states = serpentine_states(62, transposed, wall_grow)
             if ends:
                 states = two_ends(states)
             src = msnake.MultiSnakeVecEnv(len(states), dim=62, n_snakes=2, rules="snake_env", seed=0)
@@ -136,7 +149,9 @@ def main():
             for leg, pol, kw in (("space_greedy", "space_greedy", {"space_out": space}),
                                  ("territory_greedy", "territory_greedy", {"territory_out": space}),
                                  ("path_greedy", "path_greedy", {"path_out": space}),
-                                 ("path_greedy+field", "path_greedy", {"path_out": space, "field_out": field})):
+                                 ("path_greedy+field", "path_greedy", {"path_out": space, "field_out": field}),
+                                 ("timed_greedy", "timed_greedy", {"reach_out": space}),
+                                 ("timed_greedy+life", "timed_greedy", {"reach_out": space, "life_out": field})):
                 fn = lambda: env.scripted_actions_device(pol, out=acts, **kw)
                 v = ch.graph_legs({leg: fn}, args.calls, args.rounds)[leg]["graph_us"]
                 count = space.view(torch.int16).to(torch.int32) & 0xFFFF
