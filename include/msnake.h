@@ -40,6 +40,8 @@
  *   msnake_timed_actions: no reference counterpart either; when each body cell frees up (from len, grow_to and the piece
  *                      order of the state), the flood fill that may pass through a cell once it has, and the opponent
  *                      that counts its room that way.
+ *   msnake_head_fields: no reference counterpart either; the same fronts seen from the cells' side, as whole-board planes:
+ *                      how far every cell is from each head and which snake gets there first.
  *   msnake_copy_envs <- no reference counterpart (a reference env can only be re-created and replayed); the analogue is
  *                      ALE's cloneState / restoreState, batched and on the device: snapshot, fork and restore of envs
  *                      between two handles without the host round trip of msnake_get_state / msnake_set_state.
@@ -402,6 +404,34 @@ int msnake_path_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_d
 #define MSNAKE_LIFE_NEVER 0xFFFFu
 int msnake_timed_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride,
                          uint8_t* safe_dev, uint16_t* reach_dev, uint16_t* life_dev, void* stream);
+
+/* Where the snakes stand relative to every cell: each snake's BFS distance to every cell, the Voronoi owner map, and the
+ * number of cells each snake owns, in the terms of the calls above (`used`, moves 1..4, free, open).  Bodies are static,
+ * and neither the velocity nor the alive bit plays a part.
+ * D_s(c), for snake s with a non-empty body: for a free cell c, 1 + the minimum over the open moves m of s of the
+ * 4-connected BFS distance through free cells from the target of m to c; MSNAKE_HEAD_NONE when s has no open move or c
+ * cannot be reached.  A head at -1 or dim with an open move into the grid is a source like any other.  D_s(head of s) = 0
+ * when the head lies in [0,dim)^2, although the head is in `used`, and even when another piece is stacked on it; every
+ * other cell of `used` holds MSNAKE_HEAD_NONE.  For an empty body the whole plane is MSNAKE_HEAD_NONE.  A finite value
+ * is at most dim^2 - 1.
+ * dist_dev (may be NULL): uint16 [num_envs][P][dim][dim], P = popcount(snake_mask), the planes of the selected snakes in
+ * ascending order; entry [c0][c1] = D_s((c0, c1)), the indexing of the msnake_render_cells planes.  2-byte aligned
+ * (MSNAKE_E_ALIGN otherwise).
+ * owner_dev (may be NULL): uint8 [num_envs][dim][dim], over ALL snakes whatever snake_mask is.  For a free cell c let
+ * d = min over s of D_s(c): MSNAKE_OWNER_NONE if d is MSNAKE_HEAD_NONE, the index of the snake that attains d if exactly
+ * one does, MSNAKE_OWNER_TIE if two or more do.  Every cell of `used`, heads included, holds MSNAKE_OWNER_NONE.
+ * counts_dev (may be NULL): uint16 [num_envs][n_snakes], entry s = the number of cells whose owner is s.  2-byte aligned
+ * (MSNAKE_E_ALIGN otherwise).
+ * Like its siblings the call only reads the handle's state, draws no random numbers, allocates nothing, does not
+ * synchronise and adds nothing to env_steps; asynchronous on `stream`, and it can be captured into a HIP graph in
+ * front of or behind the step.  MSNAKE_E_ARG, before any device work and in this order: a snake_mask bit >= n_snakes;
+ * dist_dev non-NULL with snake_mask == 0; nothing to write (all three pointers NULL, whatever snake_mask is).  Alignment
+ * errors come after these. */
+#define MSNAKE_HEAD_NONE  0xFFFFu
+#define MSNAKE_OWNER_TIE  0xFEu
+#define MSNAKE_OWNER_NONE 0xFFu
+int msnake_head_fields(msnake_handle h, uint32_t snake_mask, uint16_t* dist_dev, uint8_t* owner_dev,
+                       uint16_t* counts_dev, void* stream);
 
 /* Copy env state from `src` into `dst` on the device: destination env e receives the state of source env
  * src_index_dev[e] (int32 [dst.num_envs], a device pointer).  A negative entry leaves destination env e completely

@@ -35,6 +35,7 @@ SCRIPTED_POLICY_NAMES = ("safe_greedy", "hamiltonian", SPACE_POLICY, TERRITORY_P
 TIMED_POLICY = "timed_greedy"  # likewise (msnake_timed_actions)
 SCRIPTED_OPPONENT_NAMES = SCRIPTED_POLICY_NAMES + (PATH_POLICY,)  # the scripted opponents with static bodies
 SCRIPTED_PLAYER_NAMES = SCRIPTED_OPPONENT_NAMES + (TIMED_POLICY,)  # every scripted opponent there is
+HEAD_NONE, OWNER_TIE, OWNER_NONE = 0xFFFF, 0xFE, 0xFF  # MSNAKE_HEAD_NONE, MSNAKE_OWNER_TIE, MSNAKE_OWNER_NONE: msnake_head_fields
 AGENT_ARM = 1  # MSNAKE_AGENT_ARM: msnake_agent_outcomes writes the tracker from the state
 AGENT_ALIVE, AGENT_WAS_ALIVE, AGENT_DIED, AGENT_ENDED = 1, 2, 4, 8  # MSNAKE_AGENT_*: the bits of its flags output
 # the words of a tracker row: grow_to, alive, then the totals of the env's current episode
@@ -104,6 +105,9 @@ PROTOTYPES = {
     # h, flags (AGENT_ARM or 0), track_dev (int32 [num_envs][n_snakes][8]), done_dev (uint8 [num_envs]), rew_dev (float32
     # [num_envs][n_snakes]), ate_dev, flags_dev (uint8 [num_envs][n_snakes]), info_dev (int32 [num_envs][n_snakes][4]), stream
     "msnake_agent_outcomes": (_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # h, snake_mask, dist_dev (uint16 [num_envs][P][dim][dim]), owner_dev (uint8 [num_envs][dim][dim]),
+    # counts_dev (uint16 [num_envs][n_snakes]), stream
+    "msnake_head_fields": (_int, [_vp, _u32, _vp, _vp, _vp, _vp]),
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -547,6 +547,19 @@ int msnake_timed_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_
                                          static_cast<hipStream_t>(stream)));
 }
 
+int msnake_head_fields(msnake_handle h, uint32_t snake_mask, uint16_t* dist_dev, uint8_t* owner_dev, uint16_t* counts_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    const int ns = h->p.n_snakes;
+    if (snake_mask >> ns) return fail(MSNAKE_E_ARG, "msnake_head_fields: snake_mask 0x%x has a bit >= n_snakes=%d", snake_mask, ns);
+    if (dist_dev && !snake_mask) return fail(MSNAKE_E_ARG, "msnake_head_fields: dist_dev is given but snake_mask is 0 (no plane to write)");
+    if (!dist_dev && !owner_dev && !counts_dev)
+        return fail(MSNAKE_E_ARG, "msnake_head_fields: nothing to write (dist_dev, owner_dev and counts_dev are NULL)");
+    if ((uintptr_t)dist_dev & 1) return fail(MSNAKE_E_ALIGN, "dist_dev must be 2-byte aligned");
+    if ((uintptr_t)counts_dev & 1) return fail(MSNAKE_E_ALIGN, "counts_dev must be 2-byte aligned");
+    DeviceGuard guard(h->cfg.device);
+    return launched(msnake::launch_heads(h->p, h->cfg.rules, snake_mask, dist_dev, owner_dev, counts_dev, static_cast<hipStream_t>(stream)));
+}
+
 int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_index_dev, void* stream) {
     if (int rc = check(dst)) return rc;
     if (int rc = check(src)) return rc;

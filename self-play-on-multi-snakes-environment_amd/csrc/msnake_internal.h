@@ -218,6 +218,10 @@ hipError_t launch_territory(const StepParams& p, int rules, uint32_t snake_mask,
 // BFS distances to the fruits, per move and as a field, and the path_greedy opponent (msnake_path.inc); reads the handle's state only
 hipError_t launch_path(const StepParams& p, int rules, uint32_t snake_mask, int32_t* actions, int32_t action_stride, uint8_t* safe,
                        uint16_t* path, uint16_t* field, hipStream_t stream);
+// every snake's BFS distance to every cell, the Voronoi owner map and the owned-cell counts (msnake_heads.inc); any of the
+// three may be NULL, snake_mask selects the distance planes.  Reads the handle's state only
+hipError_t launch_heads(const StepParams& p, int rules, uint32_t snake_mask, uint16_t* dist, uint8_t* owner, uint16_t* counts,
+                        hipStream_t stream);
 // cell lifetimes, the timed reach of every move and the timed_greedy opponent (msnake_timed.inc); reads the handle's state only
 hipError_t launch_timed(const StepParams& p, int rules, uint32_t snake_mask, int32_t* actions, int32_t action_stride, uint8_t* safe,
                         uint16_t* reach, uint16_t* life, hipStream_t stream);

@@ -2019,6 +2019,7 @@ static hipError_t launch_by_flags(int flags, const F& f) {
 #include "msnake_space.inc"     // msnake_space_actions: reachable-space counts and the flood-fill opponent (off the step path)
 #include "msnake_territory.inc" // msnake_territory_actions: Voronoi territory counts and territory_greedy (off the step path)
 #include "msnake_path.inc"      // msnake_path_actions: BFS distances to the fruits, the field and path_greedy (off the step path)
+#include "msnake_heads.inc"     // msnake_head_fields: head distances, the Voronoi owner map and the owned counts (off the step path)
 #include "msnake_timed.inc"     // msnake_timed_actions: cell lifetimes, the timed reach and timed_greedy (off the step path)
 #include "msnake_copy.inc"      // msnake_copy_envs: env state copied between two handles on the device (off the step path)
 #include "msnake_cells.inc"     // msnake_render_cells: the observation as cell codes and the per-snake table (off the step path)

@@ -115,6 +115,9 @@ LOCAL_MAX_RADIUS = 31  # MSNAKE_LOCAL_MAX_RADIUS
 CELL_OUTSIDE = 6       # MSNAKE_CELL_OUTSIDE: a window entry of render_local_device() that lies outside the grid
 RAY_DIRS, RAY_CHANNELS = 8, 4                          # MSNAKE_RAY_DIRS, MSNAKE_RAY_CHANNELS: render_rays_device()
 RAY_WALL, RAY_FRUIT, RAY_OWN, RAY_OTHER = 0, 1, 2, 3   # MSNAKE_RAY_*: the channels
+# head_fields_device(): a distance no front reaches (MSNAKE_HEAD_NONE), a cell two snakes reach at once and a cell nobody
+# owns (MSNAKE_OWNER_TIE, MSNAKE_OWNER_NONE)
+HEAD_NONE, OWNER_TIE, OWNER_NONE = _capi.HEAD_NONE, _capi.OWNER_TIE, _capi.OWNER_NONE
 
 
 def normalize_snakes(snakes, n_snakes):
@@ -320,6 +323,7 @@ class MultiSnakeVecEnv:
         self._local_fn = self._L.msnake_render_local
         self._rays_fn = self._L.msnake_render_rays
         self._agents_fn = self._L.msnake_agent_outcomes
+        self._heads_fn = self._L.msnake_head_fields
         # msnake_agent_outcomes: the tracker and the env's own outputs, allocated on first use; stale = the tracker no
         # longer describes the state (a full reset, an installed or copied state, a tape): the next call arms it first
         self._track = self._agents_own = None
@@ -541,6 +545,60 @@ class MultiSnakeVecEnv:
         maximum over stacked pieces; 0 for a cell under no body; 0xFFFF (msnake_timed_actions: MSNAKE_LIFE_NEVER) for
         every body cell of a new_world handle without fruits.  On the device; nothing is synchronised."""
         return self._counts_device("life_out", out)
+
+    def head_fields_shape(self, snakes=None):
+        """(P, dim, dim): one env's distance planes of head_fields_device(snakes)."""
+        return (len(normalize_snakes(snakes, self.n_snakes)[1]), int(self.cfg.dim), int(self.cfg.dim))
+
+    def head_fields_device(self, snakes=None, dist_out=None, owner_out=None, counts_out=None, dist=True, owner=True, counts=True):
+        """Where the snakes stand relative to every cell (msnake_head_fields), in three outputs:
+        the distance planes, uint16 [num_envs, P, dim, dim], one per selected snake in ascending snake order: entry
+        [c0, c1] of snake s is 1 + the shortest 4-connected path through free cells from the target of one of its open
+        moves to cell (c0, c1), the indexing of render_cells_device(); 0 on the snake's own head; HEAD_NONE (0xFFFF) for a
+        cell under a body, a cell the snake cannot reach, and everywhere for an empty body or a snake without an open move;
+        the owner map, uint8 [num_envs, dim, dim]: the index of the one snake with the smallest distance to the cell,
+        OWNER_TIE (0xFE) where two or more share it, OWNER_NONE (0xFF) where no snake reaches and on every body cell;
+        always over all snakes;
+        the counts, uint16 [num_envs, n_snakes]: how many cells each snake owns.
+        `snakes` selects the planes: None = every snake, an int, or a strictly ascending sequence.  An output is written
+        when its tensor is given (`dist_out`, `owner_out`, `counts_out`: contiguous, of the shape and dtype above, on this
+        device) or, without one, when its flag `dist` / `owner` / `counts` is true: then into a fresh tensor.  Returns the
+        tensors it wrote, in that order (one tensor alone when only one was written); nothing is synchronised.  Draws no
+        random numbers and changes no env state."""
+        torch = self._torch
+        mask, sel = normalize_snakes(snakes, self.n_snakes)
+        dim = int(self.cfg.dim)
+        wants = (("dist_out", dist_out, dist, torch.uint16, (self.num_envs, len(sel), dim, dim)),
+                 ("owner_out", owner_out, owner, torch.uint8, (self.num_envs, dim, dim)),
+                 ("counts_out", counts_out, counts, torch.uint16, (self.num_envs, self.n_snakes)))
+        outs = []
+        for name, t, flag, dtype, want in wants:
+            if t is not None:
+                self._checked(t, name, dtype, want)
+            elif flag:
+                with torch.cuda.device(self.device):
+                    t = torch.empty(want, dtype=dtype, device=self.device)
+            outs.append(t)
+        if all(t is None for t in outs):
+            raise ValueError("nothing to write: dist, owner and counts are all false and no output tensor is given")
+        rc = self._heads_fn(self._h, mask if outs[0] is not None else 0, *[None if t is None else t.data_ptr() for t in outs],
+                            self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_head_fields")
+        res = tuple(t for t in outs if t is not None)
+        return res[0] if len(res) == 1 else res
+
+    def head_distances_device(self, snakes=None, out=None):
+        """uint16 [num_envs, P, dim, dim]: the distance planes of head_fields_device() alone."""
+        return self.head_fields_device(snakes, dist_out=out, owner=False, counts=False)
+
+    def owner_map_device(self, out=None):
+        """uint8 [num_envs, dim, dim]: the owner map of head_fields_device() alone."""
+        return self.head_fields_device(owner_out=out, dist=False, counts=False)
+
+    def owned_counts_device(self, out=None):
+        """uint16 [num_envs, n_snakes]: the counts of head_fields_device() alone."""
+        return self.head_fields_device(counts_out=out, dist=False, owner=False)
 
     @property
     def cells_shape(self):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill table from `make -C <pkg>/csrc report` (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python tools/resource_report.py [filter]   (e.g. step, space, territory, path, agents) -- prints name, SGPRs, VGPRs, scratch, SGPR spills, VGPR spills"""
+usage: python tools/resource_report.py [filter]   (e.g. step, space, territory, path, heads, agents) -- prints name, SGPRs, VGPRs, scratch, SGPR spills, VGPR spills"""
 import os
 import re
 import subprocess
