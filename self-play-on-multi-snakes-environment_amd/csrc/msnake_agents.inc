@@ -1,6 +1,6 @@
 // msnake_agents.inc -- per-snake outcomes of a step from two consecutive states (msnake_agent_outcomes).
-// Included behind msnake_rays.inc at the end of msnake_kernels.hip.  Off the step path: nothing here is referenced by
-// msnake_step_kernel, and the kernel only READS the handle's state.
+// Included behind msnake_cells.inc, last, by msnake_views.hip; it takes nothing from its siblings.  Off the step path:
+// nothing here is referenced by msnake_step_kernel, and the kernel only READS the handle's state.
 //
 // One lane per (env, snake): a group of four lanes per env (lane s of the group = snake s; lanes s >= n_snakes idle),
 // 16 envs per wave.  Everything the call needs of an env -- SN_A(s) for the length, SN_B(s) for grow_to, HDR_FLAGS for

@@ -1,6 +1,6 @@
 // msnake_cells.inc -- the observation as cell codes and the per-snake table (msnake_render_cells).
-// Included behind msnake_copy.inc at the end of msnake_kernels.hip: it uses that file's wave helpers and must stay in
-// its translation unit.  Off the step path: nothing here is referenced by msnake_step_kernel.
+// Included behind msnake_copy.inc by msnake_views.hip: it uses msnake_device.h's wave helpers and launch_by_flags.
+// Off the step path: nothing here is referenced by msnake_step_kernel.
 //
 // One wavefront per env; the wave only READS the handle's state (record by lane, 64-slot rings by lane, overflow rings
 // and the adversarial `flist` strided in whole waves), exactly as msnake_space_kernel does.

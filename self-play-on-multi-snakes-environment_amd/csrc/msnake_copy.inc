@@ -1,5 +1,5 @@
 // msnake_copy.inc -- env state copied between two handles on the device (msnake_copy_envs: snapshot, fork, restore).
-// Included at the end of msnake_kernels.hip: it uses that file's wave helpers and must stay in its translation unit.
+// Included behind msnake_state.inc by msnake_views.hip: it uses msnake_device.h's wave helpers.
 // Off the step path: nothing here is referenced by msnake_step_kernel.
 //
 // One wavefront per DESTINATION env.  Its source index is wave-uniform; a negative one ends the wave before any load.

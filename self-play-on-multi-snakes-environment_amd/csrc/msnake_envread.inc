@@ -1,6 +1,7 @@
 // msnake_envread.inc -- how a kernel off the step path reads one env's state out of HBM, written once.
-// Included by msnake_kernels.hip ahead of the state kernels: it uses that file's wave helpers and must stay in its
-// translation unit.  Nothing here is referenced by msnake_step_kernel.
+// Included at the end of msnake_device.h, and through it by all three kernel units: it uses that header's rdlane and
+// msnake_internal.h's cell codes.  Only inline functions and templates, so every unit may include it; nothing here is
+// referenced by msnake_step_kernel.
 //
 // One wavefront per env.  The layout (msnake_internal.h) as the reader sees it:
 //   * the 256-byte record, lane l <-> word l (one coalesced load); per-snake fields come out by v_readlane;

@@ -1,7 +1,6 @@
 // msnake_heads.inc -- every snake's BFS distance to every cell, the Voronoi owner map and the owned-cell counts
-// (msnake_head_fields).  Included behind msnake_path.inc at the end of msnake_kernels.hip: it uses msnake_space.inc's
-// Board / read_board and wave_sum and msnake_territory.inc's neighbours, and must stay in their translation unit.  Off the
-// step path.
+// (msnake_head_fields).  Included behind msnake_path.inc by msnake_opponents.hip: it uses msnake_space.inc's
+// Board / read_board and wave_sum and msnake_territory.inc's neighbours.  Off the step path.
 //
 // One wavefront per env; the wave only READS the handle's state, through EnvReader.  Occupancy and the 16 candidates
 // (lane 4 s + m <-> move m + 1 of snake s) are read_board's, exactly as msnake_space_kernel has them.

@@ -1,6 +1,6 @@
 // msnake_local.inc -- head-centred, heading-aligned cell-code windows per snake (msnake_render_local).
-// Included behind msnake_cells.inc at the end of msnake_kernels.hip: it uses that file's wave helpers and must stay in
-// its translation unit.  Off the step path: nothing here is referenced by msnake_step_kernel.
+// Included behind msnake_timed.inc by msnake_opponents.hip (why there: see that file): it uses msnake_device.h's wave
+// helpers and nothing of the opponents.  Off the step path: nothing here is referenced by msnake_step_kernel.
 //
 // One wavefront per env; the wave only READS the handle's state, through EnvReader (msnake_envread.inc).
 //   * Board: ONE plane of dim^2 bytes in the wave's own slice of dynamic LDS (4 waves x dim^2 bytes in whole dwords: 1.4 KB

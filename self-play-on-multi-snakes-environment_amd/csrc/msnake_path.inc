@@ -1,7 +1,7 @@
 // msnake_path.inc -- BFS distances to the fruits, the whole distance field, and the opponent path_greedy
-// (msnake_path_actions).  Included behind msnake_territory.inc at the end of msnake_kernels.hip: it uses msnake_space.inc's
-// Board / read_board, gather_row, region_sizes, eligible_moves and greedy_among and msnake_territory.inc's neighbours,
-// and must stay in their translation unit.  Off the step path.
+// (msnake_path_actions).  Included behind msnake_territory.inc by msnake_opponents.hip: it uses msnake_space.inc's
+// Board / read_board, gather_row, region_sizes, eligible_moves and greedy_among and msnake_territory.inc's neighbours.
+// Off the step path.
 //
 // One wavefront per env; the wave only READS the handle's state, through EnvReader.  Occupancy and the 16 candidates
 // (lane 4 s + m <-> move m + 1 of snake s) are read_board's, exactly as msnake_space_kernel has them.

@@ -1,7 +1,6 @@
 // msnake_rays.inc -- eight-direction ray observations per snake (msnake_render_rays).
-// Included behind msnake_local.inc at the end of msnake_kernels.hip: it uses that file's board painter
-// (paint_snake_board) and LOCAL_WAVES, and must stay in its translation unit.  Off the step path: nothing here is
-// referenced by msnake_step_kernel.
+// Included behind msnake_local.inc, last, by msnake_opponents.hip: it uses that file's board painter (paint_snake_board) and
+// LOCAL_WAVES, and msnake_device.h's wave helpers.  Off the step path: nothing here is referenced by msnake_step_kernel.
 //
 // One wavefront per env; the wave only READS the handle's state, through EnvReader (msnake_envread.inc).
 //   * Board: the snake-indexed plane of msnake_local_kernel, painted by the same function into the wave's own slice of

@@ -1,6 +1,6 @@
 // msnake_scripted.inc -- scripted opponents and safe-move masks computed from the env state in HBM
-// (msnake_scripted_actions).  Included at the end of msnake_kernels.hip: it uses that file's wave helpers and
-// must stay in its translation unit.  Off the step path: nothing here is referenced by msnake_step_kernel.
+// (msnake_scripted_actions).  Included first by msnake_opponents.hip: it uses msnake_device.h's wave helpers, and the
+// files behind it use its wave_reduce.  Off the step path: nothing here is referenced by msnake_step_kernel.
 //
 // One wavefront per env, like everywhere else.  The wave only READS the handle's state:
 //   * the 256-byte record, lane l <-> word l (one coalesced load); per-snake fields come out by v_readlane;

@@ -1,6 +1,6 @@
 // msnake_space.inc -- reachable-space counts and the flood-fill opponent space_greedy (msnake_space_actions).
-// Included behind msnake_scripted.inc at the end of msnake_kernels.hip: it uses that file's wave helpers and
-// wave_reduce, and must stay in its translation unit.  Off the step path.
+// Included behind msnake_scripted.inc by msnake_opponents.hip: it uses msnake_device.h's wave helpers, wave_scan_incl and
+// launch_by_flags and msnake_scripted.inc's wave_reduce.  Off the step path.
 //
 // One wavefront per env; the wave only READS the handle's state, through EnvReader (msnake_envread.inc).
 //   * Occupancy: lane y owns row y of the board as ONE 64-bit mask, bit x <-> cell (x, y) = (c0, c1).  The body
@@ -52,17 +52,8 @@ __device__ __forceinline__ uint64_t row_below(uint64_t r) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-// sum over the wave: an inclusive scan inside the rows of 16 (row_shr 1, 2, 4, 8; a lane without a source adds 0),
-// then row_bcast:15 into rows 1, 3 and row_bcast:31 into rows 2, 3.  The total is in lane 63.
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);
-    return rdlane(x, 63);
-}
+// sum over the wave: lane 63 of the inclusive prefix sum (msnake_device.h)
+__device__ __forceinline__ uint32_t wave_sum(uint32_t x) { return rdlane(wave_scan_incl(x), 63); }
 
 // lane l receives v of lane src(l) & 63
 __device__ __forceinline__ uint64_t gather_row(uint64_t v, int src) {

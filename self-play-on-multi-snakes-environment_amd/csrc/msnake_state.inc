@@ -1,7 +1,6 @@
 // msnake_state.inc -- the canonical state words (include/msnake.h) <-> the device layout (msnake_get_state[_all] /
-// msnake_set_state[_all]; checkpoint and test path).  Included behind msnake_envread.inc in msnake_kernels.hip: it uses
-// that file's wave helpers and HV_SET macros and must stay in its translation unit.  Off the step path: nothing here is
-// referenced by msnake_step_kernel.
+// msnake_set_state[_all]; checkpoint and test path).  Included first by msnake_views.hip: it uses msnake_device.h's wave
+// helpers and HV_SET macros.  Off the step path: nothing here is referenced by msnake_step_kernel.
 //
 // One wavefront per env (the sizes kernel: one thread).  Export reads through EnvReader (msnake_envread.inc); import
 // validates everything before it writes anything, and a rejected env is left untouched.

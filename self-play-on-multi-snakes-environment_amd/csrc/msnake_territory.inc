@@ -1,6 +1,6 @@
 // msnake_territory.inc -- Voronoi territory counts and the opponent territory_greedy (msnake_territory_actions).
-// Included behind msnake_space.inc at the end of msnake_kernels.hip: it uses that file's Board / read_board, row_above,
-// row_below, wave_sum and greedy_by_count, and must stay in its translation unit.  Off the step path.
+// Included behind msnake_space.inc by msnake_opponents.hip: it uses that file's Board / read_board, row_above,
+// row_below, wave_sum and greedy_by_count.  Off the step path.
 //
 // One wavefront per env; the wave only READS the handle's state, through EnvReader.  Occupancy and the 16 candidates
 // (lane 4 s + m <-> move m + 1 of snake s) are read_board's, exactly as msnake_space_kernel has them.

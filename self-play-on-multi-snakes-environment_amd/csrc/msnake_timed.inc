@@ -1,7 +1,7 @@
 // msnake_timed.inc -- cell lifetimes, the timed reach of every move and the opponent timed_greedy (msnake_timed_actions).
-// Included behind msnake_path.inc at the end of msnake_kernels.hip: it uses msnake_space.inc's Board / read_board,
-// gather_row, wave_sum and greedy_by_count, msnake_territory.inc's neighbours and msnake_scripted.inc's wave_reduce, and
-// must stay in their translation unit.  Off the step path.
+// Included behind msnake_heads.inc, last, by msnake_opponents.hip: it uses msnake_space.inc's Board / read_board,
+// gather_row, wave_sum and greedy_by_count, msnake_territory.inc's neighbours and msnake_scripted.inc's wave_reduce.
+// Off the step path.
 //
 // One wavefront per env; the wave only READS the handle's state, through EnvReader.  Occupancy and the 16 candidates
 // (lane 4 s + m <-> move m + 1 of snake s) are read_board's, exactly as msnake_space_kernel has them.

@@ -20,7 +20,7 @@ def test_capi_host_glue_is_clean_under_asan_ubsan(tmp_path):
     cmd = [HIPCC, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
            "-fno-omit-frame-pointer", "-Wno-everything", "-mllvm", "-amdgpu-kernarg-preload-count=16", "-o", exe,
            os.path.join(ROOT, "tests", "capi_asan_check.cpp"), os.path.join(CSRC, "msnake_kernels.hip"),
-           os.path.join(CSRC, "msnake_capi.hip")]
+           os.path.join(CSRC, "msnake_opponents.hip"), os.path.join(CSRC, "msnake_views.hip"), os.path.join(CSRC, "msnake_capi.hip")]
     build = subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
     if build.returncode != 0 and ("sanitize" in build.stderr or "asan" in build.stderr.lower()):
         pytest.skip("sanitizer runtime for clang not usable here: " + build.stderr[-300:])

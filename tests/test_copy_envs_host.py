@@ -5,18 +5,15 @@ cross-compiles, nothing runs."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import msnake
+from kernel_resources import unit_resources
 from msnake.vec_env import CLONE_OVERRIDES, normalize_copy_index
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "self-play-on-multi-snakes-environment_amd", "csrc", "msnake_kernels.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 # ------------------------------------------------------------------------------------------ the index
@@ -83,22 +80,7 @@ def test_methods_exist_on_the_env_class():
 def test_copy_kernel_does_not_spill():
     """msnake_copy_envs_kernel spills no register, uses no scratch and no LDS, and stays within 64 VGPRs (8 waves
     per SIMD)."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    r = subprocess.run([HIPCC, "-Os", "-std=c++17", "--offload-arch=gfx950", "-mllvm", "-amdgpu-kernarg-preload-count=16", "-S",
-                        "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, SRC], check=True,
-                       capture_output=True, text=True)
-    res, cur = {}, None
-    for line in r.stderr.split("\n"):
-        m = re.search(r"remark:\s+(Function Name|VGPRs|ScratchSize \[bytes/lane\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\S+)",
-                      line)
-        if not m:
-            continue
-        k, v = m.groups()
-        if k == "Function Name":
-            cur = res.setdefault(v, {})
-        else:
-            cur[k] = int(v)
+    res, _ = unit_resources("msnake_views")
     mine = [rr for name, rr in res.items() if "msnake_copy_envs_kernel" in name]
     assert len(mine) == 1, sorted(res)
     rr = mine[0]

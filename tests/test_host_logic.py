@@ -86,7 +86,13 @@ def test_shipped_library_reads_no_environment_knobs():
     src = open(os.path.join(ROOT, "self-play-on-multi-snakes-environment_amd", "csrc", "msnake_capi.hip")).read()
     outside = re.sub(r"#if(def MSNAKE_DBG_STAGES|\s+defined\(MSNAKE_DBG_STAGES\) \|\| defined\(MSNAKE_SPAN_LIGHT\)).*?#endif", "", src, flags=re.S)
     assert "getenv" not in outside
-    assert "getenv" not in open(os.path.join(ROOT, "self-play-on-multi-snakes-environment_amd", "csrc", "msnake_kernels.hip")).read()
+    # the three kernel units and everything they include: every other source file of csrc/
+    csrc = os.path.join(ROOT, "self-play-on-multi-snakes-environment_amd", "csrc")
+    rest = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".inc", ".h")) and f != "msnake_capi.hip")
+    assert {"msnake_kernels.hip", "msnake_opponents.hip", "msnake_views.hip", "msnake_device.h", "msnake_envread.inc"} <= set(rest)
+    assert len([f for f in rest if f.endswith(".inc")]) >= 13
+    for name in rest:
+        assert "getenv" not in open(os.path.join(csrc, name)).read(), name
 
 
 def test_normalize_actions_matches_reference_call_shapes():

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Diagnostic: highest VGPR index touched per source line of one step-kernel instantiation.
-usage: tools/vgpr_by_line.py [mangled-name-substring] [min-index]   (compiles csrc/msnake_kernels.hip -S)"""
+"""Diagnostic: highest VGPR index touched per source line of one kernel.
+usage: tools/vgpr_by_line.py [mangled-name-substring] [min-index] [unit]   (compiles csrc/<unit>.hip -S)
+unit: msnake_kernels (the default: the substring then follows _ZN6msnake18msnake_step_kernel), msnake_opponents or
+msnake_views (the first kernel whose mangled name contains the substring; lines of the .inc files are not told apart)"""
 import os
 import re
 import subprocess
@@ -8,7 +10,8 @@ import sys
 from collections import defaultdict
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(root, "self-play-on-multi-snakes-environment_amd", "csrc", "msnake_kernels.hip")
+unit = sys.argv[3] if len(sys.argv) > 3 else "msnake_kernels"
+src = os.path.join(root, "self-play-on-multi-snakes-environment_amd", "csrc", unit + ".hip")
 key = sys.argv[1] if len(sys.argv) > 1 else "ILi0ELi3ELi0ELi1E"
 lo = int(sys.argv[2]) if len(sys.argv) > 2 else 28
 out = "/tmp/msnake_vgpr.s"
@@ -16,7 +19,10 @@ subprocess.check_call(["/opt/rocm/bin/hipcc", "-Os", "-std=c++17", "--offload-ar
                        "-amdgpu-kernarg-preload-count=16", "-gline-tables-only", "-S", "--cuda-device-only",
                        "-o", out, src], stderr=subprocess.DEVNULL)
 s = open(out).read()
-i = s.index("\n_ZN6msnake18msnake_step_kernel" + key)
+if unit == "msnake_kernels":
+    i = s.index("\n_ZN6msnake18msnake_step_kernel" + key)
+else:
+    i = re.search(r"\n_ZN6msnake\w*" + re.escape(key) + r"\w*:", s).start()
 body = s[i:s.index("s_endpgm", i)]
 cur, hi, cnt = None, defaultdict(int), defaultdict(int)
 for l in body.split("\n"):
