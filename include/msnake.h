@@ -98,7 +98,8 @@ typedef struct msnake_config {
     int32_t n_snakes;      /* 1..3 for snake_env/adversarial (views fixed at 3), 1..4 new_world */
     int32_t n_fruits;      /* must equal n_snakes for snake_env/adversarial; 0..32 new_world */
     int32_t rules;         /* MSNAKE_RULES_*                                                */
-    int32_t max_steps;     /* episode cap, 2000 in the reference                            */
+    int32_t max_steps;     /* episode cap, 1..60000 (2000 in the reference; anything else is MSNAKE_E_ARG).  Under
+                            * new_world the body storage is sized from it: see cap at msnake_get_state */
     int32_t auto_reset;    /* 1 = vec-env semantics (reset on done, return reset obs)       */
     int32_t obs_scale;     /* integer pixel replication of the observation (1 = native)     */
     uint64_t seed;         /* Philox key                                                    */

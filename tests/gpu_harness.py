@@ -109,11 +109,12 @@ def action_buffers(env, stride=None):
 
 
 # ------------------------------------------------------------------------------------------ states in, states out
-def install(cfg, states, with_oracle=False, **kw):
+def install(cfg, states, with_oracle=False, max_steps=2000, **kw):
     """The state dicts into a fresh handle (set_state_words), one env per state, and into a fresh oracle when asked for
-    (Oracle.set_state); read back from the handle, they are what was built.  Returns env, or (env, oracle)."""
+    (Oracle.set_state); read back from the handle, they are what was built.  Both get the episode cap `max_steps`
+    (under new_world the body storage follows it).  Returns env, or (env, oracle)."""
     from oracle.snake_oracle import flat_to_state, state_to_flat
-    cfg = dict(cfg, num_envs=len(states), seed=1, env_id_base=0, max_steps=2000)
+    cfg = dict(cfg, num_envs=len(states), seed=1, env_id_base=0, max_steps=max_steps)
     env, ora = make_env(cfg, **kw), sp.make_oracle(cfg) if with_oracle else None
     env.reset()
     if ora is not None:
