@@ -54,6 +54,8 @@
  *   msnake_agent_outcomes <- the per-snake rewards that update_snake computes and SnakeEnv.step drops for every snake
  *                      but the main one (snake_multiple_test.py:97-145,166-197), plus which snake died and each snake's episode
  *                      totals, which the reference never forms: what self-play needs to learn from every column.
+ *   msnake_death_causes <- is_snake_alive (snake_multiple_test.py:147-164), whose verdict the reference reduces to one bit: whether
+ *                      the head left the grid, and whose body or head it lies on, for every snake that was judged.
  *   msnake_get_stats <- the epinfobuf aggregation in ppo_multi_agent.py:288,331,366-390
  *
  * RNG contract (shared with oracle/ and tests/golden): draw i of global env g is word (i & 3) of
@@ -458,6 +460,51 @@ int msnake_head_fields(msnake_handle h, uint32_t snake_mask, uint16_t* dist_dev,
  * through a second handle); dim, n_snakes, n_fruits or rules differ; the devices differ; src_index_dev NULL with
  * different env counts. */
 int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_index_dev, void* stream);
+
+/* Why each snake died in a step, and on whose body: snake_env and adversarial handles only.  `before` holds the state of
+ * every env in front of ONE msnake_step of `after` -- typically filled by msnake_copy_envs(before, after, NULL, stream)
+ * on the same stream just before the step -- and `after` is the stepped handle, read before any msnake_reset_envs.
+ * Under these two rule sets every snake moves, then every snake is judged against the same post-move bodies, then the
+ * dead bodies are cleared (snake_multiple_test.py:147-197); a cleared snake keeps its velocity and grow_to words.  So the
+ * bodies the snakes were judged with follow from the two canonical states alone, without actions or random numbers.
+ * With P = the snakes whose len before is > 0, for k in P:
+ *   len after(k) > 0:  B'_k = k's body in the after state;
+ *   otherwise, with v = k's velocity words in the after state:
+ *     v == (0, 0):     B'_k = k's body before;
+ *     else:            H = head before + v, popped = (len before >= grow_to after), and
+ *                      B'_k = [H] followed by pieces 0 .. len before - 1 - popped of the body before.
+ * H_s = piece 0 of B'_s.  Cells are compared as coordinate pairs, -1 and dim included.  S = n_snakes below.
+ * cause_dev (may be NULL): uint8 [num_envs][S].  For s in P any combination of
+ *   MSNAKE_CAUSE_WALL     H_s lies outside [0, dim)^2
+ *   MSNAKE_CAUSE_SELF     H_s equals a piece i >= 1 of B'_s
+ *   MSNAKE_CAUSE_HEAD_ON  H_s == H_k for some k in P, k != s
+ *   MSNAKE_CAUSE_BODY     H_s equals a piece i >= 1 of B'_k for some k in P, k != s
+ *   and 0 for s not in P.  There is no short-circuit: every bit that holds is set (two heads that meet on a third
+ *   snake's body give HEAD_ON | BODY).
+ * by_dev (may be NULL): uint8 [num_envs][S]: bit k (0..3) is set iff BODY holds against snake k, bit 4 + k iff HEAD_ON
+ *   holds against snake k.
+ * victims_dev (may be NULL): uint8 [num_envs][S]: the same relation from the other side, row-aligned with the killer's
+ *   reward: bit s of victims[k] is set iff bit k of by[s] is, bit 4 + s iff bit 4 + k of by[s] is.
+ * where_dev (may be NULL): int8 [num_envs][S][2]: H_s as (c0, c1) where cause[s] != 0 (values -1 .. dim), (-2, -2) where
+ *   cause[s] == 0.
+ * No output needs any alignment.  Guarantee: when `before` and `after` are one msnake_step apart, cause[s] != 0 <=>
+ * len before(s) > 0 && len after(s) == 0, which is MSNAKE_AGENT_DIED of msnake_agent_outcomes.  For any other pair of
+ * states the outputs are what the formulas give, and they mean nothing.
+ * Like its siblings the call only reads both handles, draws no random numbers, allocates nothing, does not synchronise
+ * and adds nothing to env_steps; asynchronous on `stream`, and [msnake_copy_envs, msnake_step, msnake_agent_outcomes,
+ * msnake_death_causes, msnake_reset_envs] can be captured into one HIP graph.  Refusals, before any device work and in
+ * this order: MSNAKE_E_HANDLE for a NULL or destroyed handle; MSNAKE_E_ARG for after == before; for dim, n_snakes,
+ * n_fruits, rules or device that differ; for num_envs that differ; for new_world rules (they judge the snakes one after
+ * the other, clear bodies as they go and pop inside the fruit loop, new_world.py:101-158: how often a cleared snake
+ * popped depends on which fruit it ate, which two states do not tell); for `after` created with auto_reset = 1 (the
+ * after-state of a done env is gone; `before` may have any auto_reset); for four NULL outputs.  record_policy,
+ * envs_per_block, obs_scale, max_steps and seed may differ between the two handles, as for msnake_copy_envs. */
+#define MSNAKE_CAUSE_WALL 1
+#define MSNAKE_CAUSE_SELF 2
+#define MSNAKE_CAUSE_HEAD_ON 4
+#define MSNAKE_CAUSE_BODY 8
+int msnake_death_causes(msnake_handle after, msnake_handle before, uint8_t* cause_dev, uint8_t* by_dev, uint8_t* victims_dev,
+                        int8_t* where_dev, void* stream);
 
 /* The observation as cell codes, computed on the device from the current state of every env: what the reference's
  * frame (get_ob_for_snake / get_multi_snake_ob, snake_multiple_test.py:35-58,93-95) shows before its colour table is

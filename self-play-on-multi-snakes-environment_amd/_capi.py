@@ -38,6 +38,7 @@ SCRIPTED_PLAYER_NAMES = SCRIPTED_OPPONENT_NAMES + (TIMED_POLICY,)  # every scrip
 HEAD_NONE, OWNER_TIE, OWNER_NONE = 0xFFFF, 0xFE, 0xFF  # MSNAKE_HEAD_NONE, MSNAKE_OWNER_TIE, MSNAKE_OWNER_NONE: msnake_head_fields
 AGENT_ARM = 1  # MSNAKE_AGENT_ARM: msnake_agent_outcomes writes the tracker from the state
 AGENT_ALIVE, AGENT_WAS_ALIVE, AGENT_DIED, AGENT_ENDED = 1, 2, 4, 8  # MSNAKE_AGENT_*: the bits of its flags output
+CAUSE_WALL, CAUSE_SELF, CAUSE_HEAD_ON, CAUSE_BODY = 1, 2, 4, 8  # MSNAKE_CAUSE_*: the bits of msnake_death_causes' cause output
 # the words of a tracker row: grow_to, alive, then the totals of the env's current episode
 AGENT_TRACK_WORDS = ("grow_to", "alive", "ep_fruit", "ep_alive_steps", "first_death", "ep_steps", "ep_return", "zero")
 
@@ -108,6 +109,8 @@ PROTOTYPES = {
     # h, snake_mask, dist_dev (uint16 [num_envs][P][dim][dim]), owner_dev (uint8 [num_envs][dim][dim]),
     # counts_dev (uint16 [num_envs][n_snakes]), stream
     "msnake_head_fields": (_int, [_vp, _u32, _vp, _vp, _vp, _vp]),
+    # after, before, cause_dev, by_dev, victims_dev (uint8 [num_envs][n_snakes]), where_dev (int8 [num_envs][n_snakes][2]), stream
+    "msnake_death_causes": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 SYMBOLS = list(PROTOTYPES)
 

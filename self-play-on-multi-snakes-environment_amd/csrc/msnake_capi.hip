@@ -132,6 +132,17 @@ int check_snake_view(const char* fn, const char* what, int ns, uint32_t snake_ma
     return MSNAKE_OK;
 }
 
+// two handles whose env state has the same layout on the same device (msnake_copy_envs, msnake_death_causes); `an` and
+// `bn` name the two arguments in the message
+int check_same_board(const char* fn, const char* an, const msnake_config& a, const char* bn, const msnake_config& b) {
+    if (a.dim != b.dim) return fail(MSNAKE_E_ARG, "%s: %s has dim %d, %s has dim %d", fn, an, a.dim, bn, b.dim);
+    if (a.n_snakes != b.n_snakes) return fail(MSNAKE_E_ARG, "%s: %s has n_snakes %d, %s has n_snakes %d", fn, an, a.n_snakes, bn, b.n_snakes);
+    if (a.n_fruits != b.n_fruits) return fail(MSNAKE_E_ARG, "%s: %s has n_fruits %d, %s has n_fruits %d", fn, an, a.n_fruits, bn, b.n_fruits);
+    if (a.rules != b.rules) return fail(MSNAKE_E_ARG, "%s: %s has rules %d, %s has rules %d", fn, an, a.rules, bn, b.rules);
+    if (a.device != b.device) return fail(MSNAKE_E_ARG, "%s: %s lives on device %d, %s on device %d", fn, an, a.device, bn, b.device);
+    return MSNAKE_OK;
+}
+
 int ensure_scratch(msnake_env* h, size_t bytes) {
     if (bytes <= h->scratch_bytes) return MSNAKE_OK;
     if (h->d_scratch) (void)hipFree(h->d_scratch);
@@ -567,14 +578,7 @@ int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_in
         return fail(MSNAKE_E_ARG, "msnake_copy_envs: src is the same handle as dst (copies within one handle are staged "
                                   "through a second handle)");
     const msnake_config &d = dst->cfg, &s = src->cfg;
-    if (s.dim != d.dim) return fail(MSNAKE_E_ARG, "msnake_copy_envs: src has dim %d, dst has dim %d", s.dim, d.dim);
-    if (s.n_snakes != d.n_snakes)
-        return fail(MSNAKE_E_ARG, "msnake_copy_envs: src has n_snakes %d, dst has n_snakes %d", s.n_snakes, d.n_snakes);
-    if (s.n_fruits != d.n_fruits)
-        return fail(MSNAKE_E_ARG, "msnake_copy_envs: src has n_fruits %d, dst has n_fruits %d", s.n_fruits, d.n_fruits);
-    if (s.rules != d.rules) return fail(MSNAKE_E_ARG, "msnake_copy_envs: src has rules %d, dst has rules %d", s.rules, d.rules);
-    if (s.device != d.device)
-        return fail(MSNAKE_E_ARG, "msnake_copy_envs: src lives on device %d, dst on device %d", s.device, d.device);
+    if (int rc = check_same_board("msnake_copy_envs", "src", s, "dst", d)) return rc;
     if (!src_index_dev && s.num_envs != d.num_envs)
         return fail(MSNAKE_E_ARG, "msnake_copy_envs: src_index_dev is NULL (the identity) but src has num_envs %d and dst has "
                                   "num_envs %d", s.num_envs, d.num_envs);
@@ -582,6 +586,30 @@ int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_in
     DeviceGuard guard(d.device);
     if (src->offgrid_head) note_offgrid_head(dst);
     return launched(msnake::launch_copy_envs(dst->p, src->p, d.rules, src_index_dev, static_cast<hipStream_t>(stream)));
+}
+
+int msnake_death_causes(msnake_handle after, msnake_handle before, uint8_t* cause_dev, uint8_t* by_dev, uint8_t* victims_dev,
+                        int8_t* where_dev, void* stream) {
+    if (int rc = check(after)) return rc;
+    if (int rc = check(before)) return rc;
+    if (after == before)
+        return fail(MSNAKE_E_ARG, "msnake_death_causes: before is the same handle as after (the state in front of the step is "
+                                  "kept in a second handle, msnake_copy_envs(before, after, NULL, stream))");
+    const msnake_config &a = after->cfg, &b = before->cfg;
+    if (int rc = check_same_board("msnake_death_causes", "before", b, "after", a)) return rc;
+    if (b.num_envs != a.num_envs)
+        return fail(MSNAKE_E_ARG, "msnake_death_causes: before has num_envs %d, after has num_envs %d", b.num_envs, a.num_envs);
+    if (a.rules == MSNAKE_RULES_NEW_WORLD)
+        return fail(MSNAKE_E_ARG, "msnake_death_causes: new_world judges its snakes one after the other and clears bodies as it "
+                                  "goes, so the bodies a snake was judged against cannot be rebuilt from two states");
+    if (after->p.auto_reset)
+        return fail(MSNAKE_E_ARG, "msnake_death_causes: the handle `after` resets done envs inside the step (auto_reset = 1), so "
+                                  "their after-state is gone; create it with auto_reset = 0 and follow the step with msnake_reset_envs");
+    if (!cause_dev && !by_dev && !victims_dev && !where_dev)
+        return fail(MSNAKE_E_ARG, "msnake_death_causes: nothing to write (cause_dev, by_dev, victims_dev and where_dev are NULL)");
+    DeviceGuard guard(a.device);
+    return launched(msnake::launch_death_causes(after->p, before->p, a.rules, cause_dev, by_dev, victims_dev, where_dev,
+                                                static_cast<hipStream_t>(stream)));
 }
 
 int msnake_render_cells(msnake_handle h, uint32_t view_mask, uint8_t* cells_dev, int32_t* snakes_dev, void* stream) {

@@ -227,6 +227,10 @@ hipError_t launch_timed(const StepParams& p, int rules, uint32_t snake_mask, int
                         uint16_t* reach, uint16_t* life, hipStream_t stream);
 // env state of `src` into `dst`, one wave per destination env (msnake_copy.inc); src_index NULL = the identity.  Reads `src` only
 hipError_t launch_copy_envs(const StepParams& dst, const StepParams& src, int rules, const int32_t* src_index, hipStream_t stream);
+// why each snake died in the step between `before` and `after`, and on whose body (msnake_causes.inc); any of the four
+// outputs may be NULL.  Reads both handles only
+hipError_t launch_death_causes(const StepParams& after, const StepParams& before, int rules, uint8_t* cause, uint8_t* by,
+                               uint8_t* victims, int8_t* where, hipStream_t stream);
 // the observation as cell codes and the per-snake table (msnake_cells.inc); view_mask 0 / snakes NULL = that output is not
 // written.  Reads the handle's state only
 hipError_t launch_cells(const StepParams& p, int rules, uint32_t view_mask, uint8_t* cells, int32_t* snakes, hipStream_t stream);

@@ -35,6 +35,7 @@ from ._capi import SCRIPTED_POLICY_NAMES as SCRIPTED_POLICIES
 from ._capi import SCRIPTED_OPPONENT_NAMES as SCRIPTED_OPPONENTS  # SCRIPTED_POLICIES and path_greedy
 from ._capi import SCRIPTED_PLAYER_NAMES as SCRIPTED_PLAYERS  # SCRIPTED_OPPONENTS and timed_greedy: what a ScriptedOpponent may play
 from ._capi import AGENT_ENDED, AGENT_WAS_ALIVE
+from ._capi import CAUSE_BODY, CAUSE_HEAD_ON, CAUSE_SELF, CAUSE_WALL
 from .vec_env import check_radius, relative_to_absolute
 
 
@@ -522,16 +523,33 @@ def refresh_scripted(opponents):
 
 
 # ----------------------------------------------------------------------------- rollouts
+# what a rollout with death causes adds to an update's log: snakes that died by each cause (a death may count under
+# more than one) and deaths on another snake's body, credited to that snake
+DEATH_KEYS = ("deaths_wall", "deaths_self", "deaths_head_on", "deaths_body", "kills")
+
+
+def body_kills(victims):
+    """How many snakes ran into this snake's body: the set bits among bits 0..3 of msnake_death_causes' victims bytes."""
+    v = victims.to(torch.int32)
+    return (v & 1) + ((v >> 1) & 1) + ((v >> 2) & 1) + ((v >> 3) & 1)
+
+
 class Runner:
     """ppo_multi_agent.py:145-216 with everything on the device."""
 
-    def __init__(self, env, model, opponents, nsteps, gamma, lam, local_radius=None, oriented=True, rays=False, all_snakes=False):
+    def __init__(self, env, model, opponents, nsteps, gamma, lam, local_radius=None, oriented=True, rays=False, all_snakes=False,
+                 kill_bonus=0.0):
         """all_snakes=True: every snake of every env is played by `model` on its own window or rays, and run() returns the
         samples of all of them (agent_targets over env.step_agents_device).  Needs rays=True or local_radius, no
-        opponents, and an env created with auto_reset=False."""
+        opponents, and an env created with auto_reset=False.
+        kill_bonus != 0 (all_snakes only; snake_env and adversarial): every step also asks why each snake died
+        (step_agents_device(causes=True)), and a snake's reward grows by kill_bonus for every snake that ran into its body
+        in that step.  With 0 the rollout is what it is without the argument."""
         if rays and local_radius is not None:
             raise ValueError("rays=True and local_radius are mutually exclusive: a run trains on rays or on windows")
-        self.all_snakes = bool(all_snakes)
+        self.all_snakes, self.kill_bonus = bool(all_snakes), float(kill_bonus)
+        if self.kill_bonus != 0.0 and not self.all_snakes:
+            raise ValueError("kill_bonus needs all_snakes=True: only there does every snake's reward reach the learner")
         if self.all_snakes:
             if not rays and local_radius is None:
                 raise ValueError("all_snakes=True needs rays=True or local_radius: one set of weights can play every column "
@@ -608,17 +626,32 @@ class Runner:
         mb_nlp = torch.empty((T, N, S), device=dev); mb_flags = torch.empty((T, N, S), dtype=torch.uint8, device=dev)
         mb_act = torch.empty((T, N, S), dtype=torch.long, device=dev)
         ep_r, ep_l = [], []
+        causes = self.kill_bonus != 0.0
+        if causes:
+            mb_cause = torch.empty((T, N, S), dtype=torch.uint8, device=dev); mb_victims = torch.empty_like(mb_cause)
         for t in range(T):
             a, v, nlp = self.model.step(self.win.flatten(0, 1))
             mb_obs[t] = self.win
             mb_act[t], mb_val[t], mb_nlp[t] = a.view(N, S), v.view(N, S), nlp.view(N, S)
             full = relative_to_absolute(a.view(N, S), self.heading) if self.oriented else a.view(N, S)
-            self.obs, rew, done, info, agents = self.env.step_agents_device(full.to(torch.int32))
+            if causes:
+                self.obs, rew, done, info, agents, why = self.env.step_agents_device(full.to(torch.int32), causes=True)
+                mb_cause[t], mb_victims[t] = why.cause, why.victims
+            else:
+                self.obs, rew, done, info, agents = self.env.step_agents_device(full.to(torch.int32))
             self.observe_local()
             mb_rew[t], mb_flags[t] = agents.rew, agents.flags  # (copies: the next step overwrites the env's tensors)
             self.dones = done.float()
             ep_r.append(torch.where(done.bool(), info[:, 0].view(torch.float32), torch.full_like(rew, float("nan"))))
             ep_l.append(info[:, 1].clone())  # `info` is the env's buffer: the next step overwrites it
+        if causes:  # the snakes that ran into this snake's body (head-on meetings, bits 4.., credit nobody)
+            kills = body_kills(mb_victims)
+            self.last_agent_rew, self.last_cause, self.last_victims = mb_rew.clone(), mb_cause, mb_victims  # (tests)
+            mb_rew += torch.where((mb_flags & AGENT_WAS_ALIVE) != 0, self.kill_bonus * kills.float(), torch.zeros_like(mb_rew))
+            counts = torch.stack([((mb_cause & bit) != 0).sum() for bit in (CAUSE_WALL, CAUSE_SELF, CAUSE_HEAD_ON, CAUSE_BODY)] +
+                                 [kills.sum()]).tolist()
+            self.last_deaths = dict(zip(DEATH_KEYS, counts))
+        self.last_rew = mb_rew
         last_values = self.model.value(self.win.flatten(0, 1)).view(N, S)
         returns, valid = agent_targets(mb_rew, mb_val, mb_flags, last_values, self.gamma, self.lam)
         self.last_flags = mb_flags  # (tests: the batch is exactly the WAS_ALIVE samples)
@@ -668,7 +701,7 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
           cliprange=lambda f: f * 0.1, opponent_save_interval=50, max_saved_opponents=1000, csv_path=None,
           monitor_path=None, seed=0, log_fn=print, amp_dtype=None, json_path=None, tb_dir=None,
           save_dir=None, save_interval=0, load_path=None, resume=False, scripted_opponents=None, local_radius=None,
-          oriented=True, rays=False, all_snakes=False):
+          oriented=True, rays=False, all_snakes=False, kill_bonus=0.0):
     """ppo_multi_agent.py:231-404 (hyper-parameters of test/ppo1_single_test.py:42-47 as defaults).
 
     Checkpoints (ppo_multi_agent.py:112-133, 296-306, 349-364, 392-404), weights only, under `save_dir`
@@ -692,7 +725,10 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
     snake is played by the learner's current weights and every snake's transitions are learned from
     (Runner.run_all_snakes): the batch of an update is the valid (t, env, snake) samples, split into `nminibatches`
     parts.  No opponent pool is kept.  The episode statistics stay the env's own (snake 0), so curves remain comparable;
-    the log gains agent_samples (the batch size) and sample_fps."""
+    the log gains agent_samples (the batch size) and sample_fps.
+    `kill_bonus` != 0 (all_snakes only): a snake's reward grows by that much for every snake that ran into its body in
+    the step (Runner, msnake_death_causes), and every update's log gains deaths_wall, deaths_self, deaths_head_on,
+    deaths_body and kills, counted over its rollout."""
     if rays and local_radius is not None:
         raise ValueError("rays=True and local_radius are mutually exclusive: a run trains on rays or on windows")
     if all_snakes and not rays and local_radius is None:
@@ -700,6 +736,8 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
                          "on per-snake observations")
     if all_snakes and scripted_opponents:
         raise ValueError("all_snakes=True plays every snake with the learner's weights: scripted_opponents must be empty")
+    if kill_bonus != 0.0 and not all_snakes:
+        raise ValueError("kill_bonus needs all_snakes=True: only there does every snake's reward reach the learner")
     torch.manual_seed(seed); random.seed(seed)
     dev = env.device
     n_snakes = env.n_snakes
@@ -761,7 +799,7 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
         if save_dir:  # from the first pool file on there is a state a resume can start from
             save_trainer_state(0)
     runner = Runner(env, model, opponents, nsteps, gamma, lam, local_radius=local_radius, oriented=oriented, rays=rays,
-                    all_snakes=all_snakes)
+                    all_snakes=all_snakes, kill_bonus=kill_bonus)
     nbatch = env.num_envs * nsteps
     nbatch_train = nbatch // nminibatches
     assert nbatch % nminibatches == 0
@@ -821,6 +859,8 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
                 kvs["num_opponents"] = pools[0].num
             if all_snakes:
                 kvs["agent_samples"], kvs["sample_fps"] = nsamples, int(nsamples / (tnow - tstart))
+            if kill_bonus != 0.0:
+                kvs.update(runner.last_deaths)
             kvs.update(dict(zip(("policy_loss", "value_loss", "policy_entropy", "approxkl", "clipfrac"), lossvals)))
             history.append(kvs)
             for sink in sinks:

@@ -178,6 +178,8 @@ CLONE_OVERRIDES = ("record_policy", "envs_per_block", "obs_scale", "auto_reset",
 
 # what agent_outcomes_device() / step_agents_device() return of msnake_agent_outcomes: device tensors, None = not written
 AgentOutcomes = collections.namedtuple("AgentOutcomes", ("rew", "ate", "flags", "info"))
+# what death_causes_device() / step_agents_device(causes=True) return of msnake_death_causes, likewise
+DeathCauses = collections.namedtuple("DeathCauses", ("cause", "by", "victims", "where"))
 
 
 class LazyInfos:
@@ -328,6 +330,9 @@ class MultiSnakeVecEnv:
         # longer describes the state (a full reset, an installed or copied state, a tape): the next call arms it first
         self._track = self._agents_own = None
         self._track_stale = True
+        # msnake_death_causes: the env's own outputs and the snapshot env of step_agents_device(causes=True), on first use
+        self._causes_fn = self._L.msnake_death_causes
+        self._causes_own = self._snapshot = None
 
     # ------------------------------------------------------------------ device-side API
     def _stream(self):
@@ -782,23 +787,66 @@ class MultiSnakeVecEnv:
             _capi.check(rc, "msnake_agent_outcomes")
         return res
 
-    def step_agents_device(self, actions, out=None):
+    def death_causes_device(self, before, cause_out=None, by_out=None, victims_out=None, where_out=None):
+        """Why each snake died in the step just taken, and on whose body (msnake_death_causes; snake_env and adversarial).
+        `before` is another MultiSnakeVecEnv that holds this env's state in front of that step -- before.copy_envs_device(
+        self) ahead of step_device() -- and this env, created with auto_reset=False, has not been reset since.
+        cause_out uint8 [num_envs, n_snakes]: _capi.CAUSE_WALL | CAUSE_SELF | CAUSE_HEAD_ON | CAUSE_BODY, 0 for a snake
+        that did not die; by_out uint8 [num_envs, n_snakes]: bit k = on snake k's body, bit 4 + k = head-on with snake k;
+        victims_out uint8 [num_envs, n_snakes]: the same from the killer's side (bit s of row k = snake s died on k's
+        body, bit 4 + s = head-on); where_out int8 [num_envs, n_snakes, 2]: the cell the head died on, (-2, -2) for a
+        snake that did not die.  Only the outputs given are written; with none given all four go to tensors of the env's
+        own, overwritten by the next such call.  Returns a DeathCauses (cause, by, victims, where), None for what was
+        not written; nothing is synchronised."""
+        torch = self._torch
+        if not isinstance(before, MultiSnakeVecEnv):
+            raise TypeError(f"before must be a MultiSnakeVecEnv, got {type(before).__name__}")
+        n = (self.num_envs, self.n_snakes)
+        if cause_out is None and by_out is None and victims_out is None and where_out is None:
+            if self._causes_own is None:
+                with torch.cuda.device(self.device):
+                    self._causes_own = DeathCauses(*[torch.zeros(n, dtype=torch.uint8, device=self.device) for _ in range(3)],
+                                                   torch.zeros(n + (2,), dtype=torch.int8, device=self.device))
+            res = self._causes_own
+        else:
+            res = DeathCauses(None if cause_out is None else self._checked(cause_out, "cause_out", torch.uint8, n),
+                              None if by_out is None else self._checked(by_out, "by_out", torch.uint8, n),
+                              None if victims_out is None else self._checked(victims_out, "victims_out", torch.uint8, n),
+                              None if where_out is None else self._checked(where_out, "where_out", torch.int8, n + (2,)))
+        rc = self._causes_fn(self._h, before._h, *[None if t is None else t.data_ptr() for t in res],
+                             self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_death_causes")
+        return res
+
+    def step_agents_device(self, actions, out=None, causes=False):
         """step_device(), every snake's outcome of that step, and the reset of the envs it finished, on one stream:
         msnake_step -> msnake_agent_outcomes -> msnake_reset_envs(done).  Only on an env created with auto_reset=False.
         Returns (obs, rew, done, info, agents): the first four are exactly what an auto_reset=True env returns from
         step_device() (done envs show their reset observation), `agents` is the AgentOutcomes of
-        agent_outcomes_device() in tensors of the env's own.  Nothing is synchronised."""
+        agent_outcomes_device() in tensors of the env's own.  Nothing is synchronised.
+        causes=True (snake_env and adversarial): the chain becomes msnake_copy_envs (into a snapshot env of this env's
+        own, a clone() made on first use and closed with it) -> msnake_step -> msnake_agent_outcomes ->
+        msnake_death_causes -> msnake_reset_envs(done), and the DeathCauses of death_causes_device(), in tensors of the
+        env's own, is returned as a sixth element."""
         if self._ctor["auto_reset"]:
             raise ValueError("step_agents_device() needs an env created with auto_reset=False: the in-kernel auto reset "
                              "overwrites the terminal state that the other snakes' outcomes are read from")
         if self._track_stale:  # (before the step: the tracker holds the state the step starts from)
             self.arm_agents_device()
+        if causes:
+            if self._snapshot is None:
+                self._snapshot = self.clone()
+            rc = self._L.msnake_copy_envs(self._snapshot._h, self._h, None, self._cur_stream(self.device).cuda_stream)
+            if rc < 0:
+                _capi.check(rc, "msnake_copy_envs")
         obs, rew, done, info = self.step_device(actions, out)
         agents = self.agent_outcomes_device(done)
+        why = self.death_causes_device(self._snapshot) if causes else None
         rc = self._reset_envs_fn(self._h, self._p_done, obs.data_ptr(), None, None, self._cur_stream(self.device).cuda_stream)
         if rc < 0:
             _capi.check(rc, "msnake_reset_envs")
-        return obs, rew, done, info, agents
+        return (obs, rew, done, info, agents, why) if causes else (obs, rew, done, info, agents)
 
     def rollout_device(self, tape, persistent=True, keep_obs=True):
         """T lockstep steps from an action tape int32 cuda [T, num_envs, >= n_snakes] in ONE call.
@@ -936,6 +984,9 @@ class MultiSnakeVecEnv:
         return self.render_device().cpu().numpy()
 
     def close(self):
+        snapshot, self._snapshot = getattr(self, "_snapshot", None), None
+        if snapshot is not None:
+            snapshot.close()
         if not self.closed and self._h:
             self._L.msnake_destroy(self._h)
             self._h = ctypes.c_void_p()

@@ -39,6 +39,9 @@ def main():
     ap.add_argument("--all-snakes", action="store_true",
                     help="with --local-radius / --rays: the learner plays every snake and learns from every snake's transitions "
                          "(per-snake rewards and deaths from the device), instead of from snake 0 against opponents")
+    ap.add_argument("--kill-bonus", type=float, default=0.0, metavar="B",
+                    help="with --all-snakes (snake_env, adversarial): add B to a snake's reward for every snake that ran into its "
+                         "body in the step, and log the deaths of every update by cause")
     args = ap.parse_args()
     if args.rays and args.local_radius is not None:
         ap.error("--rays and --local-radius are mutually exclusive")
@@ -46,6 +49,8 @@ def main():
         ap.error("--no-orient needs --local-radius or --rays")
     if args.all_snakes and (args.local_radius is None and not args.rays or args.opponent != "pool"):
         ap.error("--all-snakes needs --local-radius or --rays, and no --opponent")
+    if args.kill_bonus != 0.0 and not args.all_snakes:
+        ap.error("--kill-bonus needs --all-snakes")
     import torch
     from msnake import selfplay
 
@@ -56,7 +61,7 @@ def main():
                    monitor_path=args.monitor, json_path=args.json, tb_dir=args.tensorboard,
                    amp_dtype=torch.bfloat16 if args.bf16 else None, save_dir=args.save, save_interval=args.save_interval,
                    load_path=args.load, resume=args.resume, local_radius=args.local_radius, oriented=not args.no_orient, rays=args.rays,
-                   all_snakes=args.all_snakes, scripted_opponents=None if args.opponent == "pool" else {s: args.opponent for s in range(1, args.snakes)})
+                   all_snakes=args.all_snakes, kill_bonus=args.kill_bonus, scripted_opponents=None if args.opponent == "pool" else {s: args.opponent for s in range(1, args.snakes)})
     print(env.stats())
     env.close()
 
