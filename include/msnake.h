@@ -29,6 +29,10 @@
  *                      counterpart (env state is never checkpointed there); used by
  *                      the parity tests to install hand-built states and by callers to checkpoint.
  *   msnake_state_blob_info: no reference counterpart either; validates such a checkpoint on the host.
+ *   msnake_export_states / msnake_import_states / msnake_hash_states / msnake_state_words_max: no reference
+ *                      counterpart either; the same words as a device tensor that torch code can read, edit and archive,
+ *                      and a 64-bit key per env (transpositions in a search over forks, archives keyed by position,
+ *                      lockstep checks between shards) -- asynchronous and graph-capturable, unlike the four above.
  *   msnake_scripted_actions: no reference counterpart (its opponents are always networks: evaluate_snake.py,
  *                      ppo_multi_agent.py:28-50 MultiModel.multi_step); a fixed, deterministic opponent and the
  *                      safe-move mask, computed on the device from the state the handle already owns.
@@ -259,6 +263,71 @@ typedef struct msnake_blob_info {
     int64_t total_words;
 } msnake_blob_info;
 int msnake_state_blob_info(const void* buf, size_t bytes, msnake_blob_info* out);
+
+/* ---- The canonical words as a device tensor: export, import and 64-bit hashes of EVERY env, asynchronous on `stream`.
+ * The words are exactly those documented at msnake_get_state.  The three calls below allocate nothing, never
+ * synchronise, draw no random numbers, add nothing to env_steps, and can be captured into a HIP graph in front of or
+ * behind a step; export and hash only read the handle.  MSNAKE_E_HANDLE for a NULL or destroyed handle. */
+
+/* The largest word count any state the handle accepts can have: 8 + 2 * F + n_snakes * (6 + 2 * (cap - 2)), F being
+ * n_fruits under snake_env and new_world and fcap under adversarial (cap, fcap: see msnake_get_state).  A row of that
+ * many words holds every env of the handle, whatever is played or installed.  Host only, no device work; negative
+ * MSNAKE_E_HANDLE for a NULL handle. */
+int32_t msnake_state_words_max(msnake_handle h);
+
+/* Every env's words into row e of words_dev, int32 [num_envs][stride], and their number into count_dev, int32
+ * [num_envs]; either may be NULL, not both.  count_dev[e] is the number of words env e's state has, whatever stride
+ * is.  If that number is <= stride, words [0, n) of row e are exactly what msnake_get_state returns and words
+ * [n, stride) are not written; if it is larger, NO word of row e is written, and count_dev is how the caller learns of
+ * it.  Both pointers 4-byte aligned (MSNAKE_E_ALIGN otherwise).  MSNAKE_E_ARG, before any device work: stride < 0;
+ * words_dev given with stride 0; both outputs NULL (nothing to write). */
+int msnake_export_states(msnake_handle h, int32_t* words_dev, int32_t stride, int32_t* count_dev, void* stream);
+
+/* What msnake_import_states writes to status_dev[e]: SKIPPED where the mask is 0, OK where the row was installed, else
+ * why it was refused -- the six reasons of msnake_set_state, in the order their checks are listed at msnake_get_state
+ * ("too short", "snake count", "fruit count", "cell", "length", "scalar"). */
+#define MSNAKE_STATE_OK 0
+#define MSNAKE_STATE_TOO_SHORT 1
+#define MSNAKE_STATE_SNAKE_COUNT 2
+#define MSNAKE_STATE_FRUIT_COUNT 3
+#define MSNAKE_STATE_CELL 4
+#define MSNAKE_STATE_LENGTH 5
+#define MSNAKE_STATE_SCALAR 6
+#define MSNAKE_STATE_SKIPPED 0xFF
+
+/* Row e of words_dev, int32 [num_envs][stride], into env e, for the envs mask_dev selects: uint8 [num_envs], non-zero =
+ * selected, NULL = every env.  count_dev, int32 [num_envs], is the number of words of each row; NULL = every row has
+ * `stride` words, and words behind the last snake are ignored as msnake_set_state ignores them.  A count_dev[e] below 0
+ * or above stride is reason "too short".  status_dev, uint8 [num_envs], is required and written for EVERY env:
+ * MSNAKE_STATE_SKIPPED where the mask is 0 -- such an env is untouched, byte for byte --, MSNAKE_STATE_OK where the row
+ * was installed, otherwise one of the six reasons above -- such an env is left untouched as well.  The checks, their
+ * order and the first-failing-reason rule are items 1-7 at msnake_get_state; a row is validated as a whole before any
+ * word of the env is written, and no word past its count is read.  An accepted env ends up exactly as
+ * msnake_set_state(h, e, row, n) leaves it: the logging totals are kept, parked random draws are cleared, the
+ * `finished` bit is restored, an episode in progress is abandoned, not counted.
+ * One deliberate difference: the host cannot learn of a head outside the grid without a synchronisation, so
+ *   - a handle that currently runs a step kernel compiled for its shape (msnake_kernel_name) REFUSES such a head with
+ *     MSNAKE_STATE_CELL (install it with msnake_set_state, which moves the handle to the generic kernels, if needed);
+ *   - a handle on the generic kernels accepts it, as msnake_set_state does, and counts from then on as one that may hold
+ *     such a head (msnake_copy_envs from it moves the destination to the generic kernels too).
+ * Refusals are data, not errors: the call returns MSNAKE_OK when the launch was issued.  MSNAKE_E_ARG, before any device
+ * work: words_dev or status_dev NULL; stride < 8.  MSNAKE_E_ALIGN: words_dev or count_dev not 4-byte aligned. */
+int msnake_import_states(msnake_handle h, const uint8_t* mask_dev, const int32_t* words_dev, int32_t stride,
+                         const int32_t* count_dev, uint8_t* status_dev, void* stream);
+
+/* A 64-bit hash of every env's words into hash_dev, uint64 [num_envs], 8-byte aligned (MSNAKE_E_ALIGN otherwise).  With
+ * w[0..n) env e's canonical words,
+ *     H = sum over the selected i of mix64(((uint64)(i + 1) << 32) | (uint32)w[i])   mod 2^64,
+ * mix64 the splitmix64 finaliser: z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ * z ^= z >> 31.  Any holder of the words computes the same key on the host.
+ *   MSNAKE_HASH_FULL:  every word.
+ *   MSNAKE_HASH_BOARD: the position only -- words 0, 1, 2, 4, 5 (t, the draw counter, ep_len, ep_return) are left out
+ *     and bit 8 of word 7 (`finished`) is cleared; spare_fruits stays, because it changes adversarial play.  Two envs
+ *     with equal BOARD hashes render the same frame.
+ * Any other `what` is MSNAKE_E_ARG; so is a NULL hash_dev. */
+#define MSNAKE_HASH_FULL 0u
+#define MSNAKE_HASH_BOARD 1u
+int msnake_hash_states(msnake_handle h, uint32_t what, uint64_t* hash_dev, void* stream);
 
 /* Render the current state of every env without stepping (asynchronous). */
 int msnake_render(msnake_handle h, uint8_t* obs_dev, void* stream);

@@ -39,6 +39,9 @@ HEAD_NONE, OWNER_TIE, OWNER_NONE = 0xFFFF, 0xFE, 0xFF  # MSNAKE_HEAD_NONE, MSNAK
 AGENT_ARM = 1  # MSNAKE_AGENT_ARM: msnake_agent_outcomes writes the tracker from the state
 AGENT_ALIVE, AGENT_WAS_ALIVE, AGENT_DIED, AGENT_ENDED = 1, 2, 4, 8  # MSNAKE_AGENT_*: the bits of its flags output
 CAUSE_WALL, CAUSE_SELF, CAUSE_HEAD_ON, CAUSE_BODY = 1, 2, 4, 8  # MSNAKE_CAUSE_*: the bits of msnake_death_causes' cause output
+HASH_WHAT = {"full": 0, "board": 1}  # MSNAKE_HASH_FULL, MSNAKE_HASH_BOARD: msnake_hash_states
+# MSNAKE_STATE_*: the status bytes of msnake_import_states
+STATE_OK, STATE_TOO_SHORT, STATE_SNAKE_COUNT, STATE_FRUIT_COUNT, STATE_CELL, STATE_LENGTH, STATE_SCALAR, STATE_SKIPPED = 0, 1, 2, 3, 4, 5, 6, 0xFF
 # the words of a tracker row: grow_to, alive, then the totals of the env's current episode
 AGENT_TRACK_WORDS = ("grow_to", "alive", "ep_fruit", "ep_alive_steps", "first_death", "ep_steps", "ep_return", "zero")
 
@@ -111,6 +114,12 @@ PROTOTYPES = {
     "msnake_head_fields": (_int, [_vp, _u32, _vp, _vp, _vp, _vp]),
     # after, before, cause_dev, by_dev, victims_dev (uint8 [num_envs][n_snakes]), where_dev (int8 [num_envs][n_snakes][2]), stream
     "msnake_death_causes": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msnake_state_words_max": (_i32, [_vp]),  # h
+    # h, words_dev (int32 [num_envs][stride] or NULL), stride, count_dev (int32 [num_envs] or NULL), stream
+    "msnake_export_states": (_int, [_vp, _vp, _i32, _vp, _vp]),
+    # h, mask_dev (uint8 [num_envs] or NULL), words_dev, stride, count_dev (or NULL), status_dev (uint8 [num_envs]), stream
+    "msnake_import_states": (_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "msnake_hash_states": (_int, [_vp, _u32, _vp, _vp]),  # h, what (HASH_WHAT), hash_dev (uint64 [num_envs]), stream
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -815,6 +815,50 @@ int msnake_set_state_all(msnake_handle h, const void* buf, size_t bytes) {
                         reinterpret_cast<const int32_t*>(static_cast<const uint8_t*>(buf) + head));
 }
 
+// ---- the same words as a device tensor: one launch each, nothing allocated, nothing synchronised ----
+int32_t msnake_state_words_max(msnake_handle h) {
+    if (int rc = check(h)) return rc;
+    const msnake::StepParams& p = h->p;
+    const int F = h->cfg.rules == MSNAKE_RULES_ADVERSARIAL ? p.fcap : p.n_fruits;
+    return 8 + 2 * F + p.n_snakes * (6 + 2 * (p.rest.cap - 2));
+}
+
+int msnake_export_states(msnake_handle h, int32_t* words_dev, int32_t stride, int32_t* count_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    if (stride < 0) return fail(MSNAKE_E_ARG, "msnake_export_states: stride %d < 0", stride);
+    if (words_dev && stride == 0) return fail(MSNAKE_E_ARG, "msnake_export_states: words_dev is given but stride is 0");
+    if (!words_dev && !count_dev) return fail(MSNAKE_E_ARG, "msnake_export_states: nothing to write (words_dev and count_dev are NULL)");
+    if (((uintptr_t)words_dev | (uintptr_t)count_dev) & 3) return fail(MSNAKE_E_ALIGN, "words_dev and count_dev must be 4-byte aligned");
+    DeviceGuard guard(h->cfg.device);
+    return launched(msnake::launch_state_export(h->p, h->cfg.rules, words_dev, stride, count_dev, static_cast<hipStream_t>(stream)));
+}
+
+int msnake_import_states(msnake_handle h, const uint8_t* mask_dev, const int32_t* words_dev, int32_t stride,
+                         const int32_t* count_dev, uint8_t* status_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    if (!words_dev || !status_dev) return fail(MSNAKE_E_ARG, "msnake_import_states: words_dev and status_dev must not be NULL");
+    if (stride < 8) return fail(MSNAKE_E_ARG, "msnake_import_states: stride %d < 8 (no state has fewer words)", stride);
+    if (((uintptr_t)words_dev | (uintptr_t)count_dev) & 3) return fail(MSNAKE_E_ALIGN, "words_dev and count_dev must be 4-byte aligned");
+    DeviceGuard guard(h->cfg.device);
+    // a head outside the grid: the kernels compiled for a shape cannot follow it (note_offgrid_head) and the host will not
+    // hear of it, so such a handle refuses the row; a handle on the generic kernels takes it and counts as holding one
+    const bool refuse = h->p.spec_dim != 0;
+    int rc = launched(msnake::launch_state_import(h->p, h->cfg.rules, mask_dev, words_dev, stride, count_dev, status_dev, refuse,
+                                                  static_cast<hipStream_t>(stream)));
+    if (rc == MSNAKE_OK && !refuse) h->offgrid_head = 1;
+    return rc;
+}
+
+int msnake_hash_states(msnake_handle h, uint32_t what, uint64_t* hash_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    if (what != MSNAKE_HASH_FULL && what != MSNAKE_HASH_BOARD)
+        return fail(MSNAKE_E_ARG, "msnake_hash_states: what %u is neither MSNAKE_HASH_FULL nor MSNAKE_HASH_BOARD", what);
+    if (!hash_dev) return fail(MSNAKE_E_ARG, "msnake_hash_states: hash_dev is NULL");
+    if ((uintptr_t)hash_dev & 7) return fail(MSNAKE_E_ALIGN, "hash_dev must be 8-byte aligned");
+    DeviceGuard guard(h->cfg.device);
+    return launched(msnake::launch_state_hash(h->p, h->cfg.rules, what == MSNAKE_HASH_BOARD, hash_dev, static_cast<hipStream_t>(stream)));
+}
+
 int msnake_get_stats(msnake_handle h, msnake_stats* out, int32_t reset) {
     if (int rc = check(h)) return rc;
     if (!out) return fail(MSNAKE_E_ARG, "msnake_get_stats: out is NULL");

@@ -67,6 +67,10 @@ enum {
     MSNAKE_ST_LEN = 5,     // a body length outside [0, cap - 2]
     MSNAKE_ST_SCALAR = 6   // a scalar field out of range: t, spare_fruits, ep_len, grow_to, a velocity, alive / in_dead
 };
+// msnake_import_states publishes them as they are (its status bytes)
+static_assert(MSNAKE_ST_SHORT == MSNAKE_STATE_TOO_SHORT && MSNAKE_ST_SNAKES == MSNAKE_STATE_SNAKE_COUNT &&
+              MSNAKE_ST_FRUITS == MSNAKE_STATE_FRUIT_COUNT && MSNAKE_ST_CELL == MSNAKE_STATE_CELL &&
+              MSNAKE_ST_LEN == MSNAKE_STATE_LENGTH && MSNAKE_ST_SCALAR == MSNAKE_STATE_SCALAR && MSNAKE_STATE_OK == 0, "public reason codes");
 
 #define MSNAKE_HD __host__ __device__ __forceinline__ constexpr
 
@@ -206,6 +210,14 @@ hipError_t launch_state_pack(const StepParams& p, int rules, int env0, int count
                              hipStream_t stream);
 hipError_t launch_state_unpack(const StepParams& p, int rules, int env0, int count, const uint64_t* offsets,
                                const int32_t* words, uint32_t* status, hipStream_t stream);
+// the same words of EVERY env as rows of a device tensor (msnake_export_states / msnake_import_states): row e at e * stride;
+// export: words or count may be NULL; import: mask NULL = every env, count NULL = every row has `stride` words, status
+// gets one byte per env, and a head outside the grid is refused when refuse_offgrid_head
+hipError_t launch_state_export(const StepParams& p, int rules, int32_t* words, int32_t stride, int32_t* count, hipStream_t stream);
+hipError_t launch_state_import(const StepParams& p, int rules, const uint8_t* mask, const int32_t* words, int32_t stride,
+                               const int32_t* count, uint8_t* status, bool refuse_offgrid_head, hipStream_t stream);
+// MSNAKE_HASH_FULL / MSNAKE_HASH_BOARD of every env's canonical words (msnake_hash.inc); reads the handle's state only
+hipError_t launch_state_hash(const StepParams& p, int rules, bool board, uint64_t* hash, hipStream_t stream);
 // scripted opponents / safe-move masks from the state in HBM (msnake_scripted.inc); reads the handle's state only
 hipError_t launch_scripted(const StepParams& p, int rules, int policy, uint32_t snake_mask, int32_t* actions, int32_t action_stride,
                            uint8_t* safe, hipStream_t stream);

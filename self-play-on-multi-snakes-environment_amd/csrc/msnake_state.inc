@@ -4,6 +4,9 @@
 //
 // One wavefront per env (the sizes kernel: one thread).  Export reads through EnvReader (msnake_envread.inc); import
 // validates everything before it writes anything, and a rejected env is left untouched.
+// Each direction is ONE body with two kernels around it: the blocking entry points find a row through a host-built
+// offset table and report through one global status triple; msnake_export_states / msnake_import_states (asynchronous,
+// every env of the handle) find it at e * stride and report one count and one status byte per env.
 namespace msnake {
 
 __global__ __launch_bounds__(256) void msnake_state_sizes_kernel(StateView v, int env0, int count, uint32_t* __restrict__ need) {
@@ -15,13 +18,33 @@ __global__ __launch_bounds__(256) void msnake_state_sizes_kernel(StateView v, in
     need[w] = n;
 }
 
-__global__ __launch_bounds__(256) void msnake_state_pack_kernel(StateView v, int env0, int count,
-                                                                const uint64_t* __restrict__ offsets, int32_t* __restrict__ words) {
-    const int lane = (int)(threadIdx.x & 63u);
-    const int w = (int)uni(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-    if (w >= count) return;
-    const EnvReader rd(v, env0 + w, lane);
-    int32_t* out = words + offsets[w];
+// Where a packed env's words go.  A row source answers row(rd): the first word of the env's row, or -- only a source
+// with kMayDecline -- NULL for "write no word of this env".  The blocking entry points address rows through a host-built
+// table of word offsets; msnake_export_states through e * stride, and says how many words the env has on the way.
+struct RowsByOffset {
+    static constexpr bool kMayDecline = false;
+    const uint64_t* __restrict__ offsets; int32_t* __restrict__ words; int w;
+    __device__ __forceinline__ int32_t* row(const EnvReader&) const { return words + offsets[w]; }
+};
+struct RowsByStride {
+    static constexpr bool kMayDecline = true;
+    int32_t* __restrict__ words; int32_t* __restrict__ count; int32_t stride;
+    __device__ __forceinline__ int32_t* row(const EnvReader& rd) const {
+        uint32_t n = 8u + 2u * (uint32_t)rd.n_fruits();  // (what msnake_state_sizes_kernel counts)
+#pragma unroll
+        for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s)
+            if (s < rd.v.ns) n += 6u + 2u * (rd.word(SN_A(s)) >> 16);
+        if (count && rd.lane == 0) count[rd.e] = (int32_t)n;
+        return words && n <= (uint32_t)stride ? words + (size_t)rd.e * (size_t)stride : nullptr;
+    }
+};
+
+// env e's canonical words, by the wave that reads it
+template <typename Rows>
+__device__ __forceinline__ void state_pack_env(const StateView& v, int e, int lane, const Rows& rows) {
+    const EnvReader rd(v, e, lane);
+    int32_t* out = rows.row(rd);
+    if (Rows::kMayDecline && !out) return;
     const bool nw = v.rules == MSNAKE_RULES_NEW_WORLD;
     const int nfr = rd.n_fruits();
     const uint32_t flags = rd.flags();
@@ -61,18 +84,60 @@ __global__ __launch_bounds__(256) void msnake_state_pack_kernel(StateView v, int
     }
 }
 
+__global__ __launch_bounds__(256) void msnake_state_pack_kernel(StateView v, int env0, int count,
+                                                                const uint64_t* __restrict__ offsets, int32_t* __restrict__ words) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int w = (int)uni(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    if (w >= count) return;
+    state_pack_env(v, env0 + w, lane, RowsByOffset{offsets, words, w});
+}
+
+// msnake_export_states: row e of words[nenv][stride] and count[e]; either of the two may be NULL
+__global__ __launch_bounds__(256) void msnake_state_export_kernel(StateView v, int32_t* __restrict__ words, int32_t stride,
+                                                                  int32_t* __restrict__ count) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int e = (int)uni(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    if (e >= v.nenv) return;
+    state_pack_env(v, e, lane, RowsByStride{words, count, stride});
+}
+
 // status[0]: number of rejected envs, status[1]: min over them of status_pack(local index, MSNAKE_ST_* reason) (ONE
 // atomicMin on ~0u: index and reason of the first rejected env cannot come from two different waves), status[2]: != 0 if
 // an accepted env has a head outside the grid
-__global__ __launch_bounds__(256) void msnake_state_unpack_kernel(StateView v, int env0, int count,
-                                                                  const uint64_t* __restrict__ offsets,
-                                                                  const int32_t* __restrict__ words, uint32_t* __restrict__ status) {
-    const int lane = (int)(threadIdx.x & 63u);
-    const int w = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-    if (w >= count) return;
-    const int e = env0 + w;
-    const int32_t* in = words + offsets[w];
-    const long long n = (long long)(offsets[w + 1] - offsets[w]);
+struct StatusGlobal {
+    // (the blocking entry points learn of a head outside the grid from status[2] and move the handle to the generic kernels)
+    static constexpr bool kRefusesOffgridHead = false;
+    uint32_t* __restrict__ status; int w;
+    __device__ __forceinline__ bool refuses_offgrid_head() const { return false; }
+    __device__ __forceinline__ void reject(int lane, int reason) const {
+        if (lane == 0) {
+            atomicAdd(&status[0], 1u);
+            atomicMin(&status[1], status_pack(w, reason));
+        }
+    }
+    __device__ __forceinline__ void accept(int, bool off_head) const {
+        if (off_head) atomicOr(&status[2], 1u);
+    }
+};
+// msnake_import_states: one status byte per env, MSNAKE_STATE_OK or the MSNAKE_ST_* reason.  `refuse` (wave-uniform): a
+// head outside the grid is reason "cell" -- the host cannot learn of one without a sync, and the step kernels compiled
+// for a shape cannot draw what such a head leaves behind (note_offgrid_head in msnake_capi.hip)
+struct StatusPerEnv {
+    static constexpr bool kRefusesOffgridHead = true;
+    uint8_t* __restrict__ status; int e; bool refuse;
+    __device__ __forceinline__ bool refuses_offgrid_head() const { return refuse; }
+    __device__ __forceinline__ void reject(int lane, int reason) const {
+        if (lane == 0) status[e] = (uint8_t)reason;
+    }
+    __device__ __forceinline__ void accept(int lane, bool) const {
+        if (lane == 0) status[e] = (uint8_t)MSNAKE_STATE_OK;
+    }
+};
+
+// the n words at `in` into env e, by one wave: validated as a whole, then written; the verdict goes to `sink`
+template <typename Sink>
+__device__ __forceinline__ void state_unpack_env(const StateView& v, int e, int lane, const int32_t* __restrict__ in, long long n,
+                                                 const Sink& sink) {
     const bool adv = v.rules == MSNAKE_RULES_ADVERSARIAL, nw = v.rules == MSNAKE_RULES_NEW_WORLD;
     auto cell_ok = [&](int c0, int c1) { return c0 >= -1 && c0 <= v.dim && c1 >= -1 && c1 <= v.dim; };
     // ---- pass 1: validate everything before anything is written
@@ -117,7 +182,11 @@ __global__ __launch_bounds__(256) void msnake_state_unpack_kernel(StateView v, i
         for (int i = lane; i < len; i += 64) {
             const int c0 = in[k + 6 + 2LL * i], c1 = in[k + 6 + 2LL * i + 1];
             okc = okc && cell_ok(c0, c1);
-            if (i == 0) off_head = off_head || !(c0 >= 0 && c0 < v.dim && c1 >= 0 && c1 < v.dim);
+            if (i == 0) {
+                const bool off = !(c0 >= 0 && c0 < v.dim && c1 >= 0 && c1 < v.dim);
+                off_head = off_head || off;
+                if (Sink::kRefusesOffgridHead && sink.refuses_offgrid_head()) okc = okc && !off;
+            }
             // only a head may be one step outside the grid (where a reference snake can be, for one step)
             if (i > 0) okc = okc && c0 >= 0 && c0 < v.dim && c1 >= 0 && c1 < v.dim;
         }
@@ -125,13 +194,10 @@ __global__ __launch_bounds__(256) void msnake_state_unpack_kernel(StateView v, i
         k += 6 + 2LL * len;
     }
     if (bad) {
-        if (lane == 0) {
-            atomicAdd(&status[0], 1u);
-            atomicMin(&status[1], status_pack(w, bad));
-        }
+        sink.reject(lane, bad);
         return;
     }
-    if (off_head) atomicOr(&status[2], 1u);
+    sink.accept(lane, off_head);
     // ---- pass 2: the record (lane l builds word l; logging totals are not part of the canonical
     //      state and stay; every other word, the parked Philox draws included, is cleared)
     uint32_t* h = v.hdr + (size_t)e * MSNAKE_HDR_WORDS;
@@ -175,6 +241,36 @@ __global__ __launch_bounds__(256) void msnake_state_unpack_kernel(StateView v, i
     h[lane] = hv;
 }
 
+__global__ __launch_bounds__(256) void msnake_state_unpack_kernel(StateView v, int env0, int count,
+                                                                  const uint64_t* __restrict__ offsets,
+                                                                  const int32_t* __restrict__ words, uint32_t* __restrict__ status) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int w = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    if (w >= count) return;
+    state_unpack_env(v, env0 + w, lane, words + offsets[w], (long long)(offsets[w + 1] - offsets[w]), StatusGlobal{status, w});
+}
+
+// msnake_import_states: row e of words[nenv][stride] into env e where mask[e] != 0 (mask NULL: every env); count NULL:
+// every row has `stride` words.  A count outside [0, stride] reads as -1 words: "too short", before any word is read
+__global__ __launch_bounds__(256) void msnake_state_import_kernel(StateView v, const uint8_t* __restrict__ mask,
+                                                                  const int32_t* __restrict__ words, int32_t stride,
+                                                                  const int32_t* __restrict__ count, uint8_t* __restrict__ status,
+                                                                  int refuse_offgrid_head) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int e = (int)uni(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    if (e >= v.nenv) return;
+    if (mask && !mask[e]) {
+        if (lane == 0) status[e] = (uint8_t)MSNAKE_STATE_SKIPPED;
+        return;
+    }
+    long long n = stride;
+    if (count) {
+        const int32_t c = (int32_t)uni((uint32_t)count[e]);
+        n = c < 0 || c > stride ? -1 : c;
+    }
+    state_unpack_env(v, e, lane, words + (size_t)e * (size_t)stride, n, StatusPerEnv{status, e, refuse_offgrid_head != 0});
+}
+
 hipError_t launch_state_sizes(const StepParams& p, int rules, int env0, int count, uint32_t* need_words, hipStream_t stream) {
     hipLaunchKernelGGL(msnake_state_sizes_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream,
                        state_view(p, rules), env0, count, need_words);
@@ -192,6 +288,19 @@ hipError_t launch_state_unpack(const StepParams& p, int rules, int env0, int cou
                                const int32_t* words, uint32_t* status, hipStream_t stream) {
     hipLaunchKernelGGL(msnake_state_unpack_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, stream,
                        state_view(p, rules), env0, count, offsets, words, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_state_export(const StepParams& p, int rules, int32_t* words, int32_t stride, int32_t* count, hipStream_t stream) {
+    hipLaunchKernelGGL(msnake_state_export_kernel, dim3((unsigned)((p.nenv + 3) / 4)), dim3(256), 0, stream,
+                       state_view(p, rules), words, stride, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_state_import(const StepParams& p, int rules, const uint8_t* mask, const int32_t* words, int32_t stride,
+                               const int32_t* count, uint8_t* status, bool refuse_offgrid_head, hipStream_t stream) {
+    hipLaunchKernelGGL(msnake_state_import_kernel, dim3((unsigned)((p.nenv + 3) / 4)), dim3(256), 0, stream,
+                       state_view(p, rules), mask, words, stride, count, status, refuse_offgrid_head ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -52,6 +52,59 @@ def gather_stats(local, device=None, group=None):
     return per_rank, total
 
 
+_M64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _i64(x):
+    """The 64 bits of x as the int64 that holds them."""
+    x &= _M64
+    return x - (1 << 64) if x >> 63 else x
+
+
+def _mix64_i64(z):
+    """The splitmix64 finaliser on a torch int64 tensor holding 64-bit patterns (products wrap; shifts made logical)."""
+    z = (z ^ ((z >> 30) & ((1 << 34) - 1))) * _i64(0xBF58476D1CE4E5B9)
+    z = (z ^ ((z >> 27) & ((1 << 37) - 1))) * _i64(0x94D049BB133111EB)
+    return z ^ ((z >> 31) & ((1 << 33) - 1))
+
+
+def fingerprint(hashes, env_id_base=0):
+    """One order-independent 64-bit number (a Python int in [0, 2^64)) for the per-env hashes of a shard whose first
+    env has the global id `env_id_base`: sum_e mix64(hash_e + (env_id_base + e) * 0x9E3779B97F4A7C15) mod 2^64.
+
+    `hashes` is the int64 [n] tensor of MultiSnakeVecEnv.hash_states_device(), on any device; the sum is formed there.
+    The fingerprints of the shards of a run add up (mod 2^64) to the fingerprint of the unsharded run, however the envs
+    are split, and swapping the hashes of two envs changes it."""
+    import torch
+
+    if not isinstance(hashes, torch.Tensor) or hashes.dtype != torch.int64 or hashes.dim() != 1:
+        raise ValueError("hashes must be a 1-d int64 tensor (hash_states_device())")
+    if isinstance(env_id_base, bool) or not isinstance(env_id_base, int) or env_id_base < 0:
+        raise ValueError(f"env_id_base must be a non-negative int, got {env_id_base!r}")
+    ids = torch.arange(hashes.shape[0], dtype=torch.int64, device=hashes.device) + _i64(env_id_base)
+    return int(_mix64_i64(hashes + ids * _i64(_GOLDEN)).sum().item()) & _M64
+
+
+def all_fingerprint(env, what="full", device=None, group=None):
+    """The fingerprint of a sharded run, the same on every rank and equal to the unsharded run's: every rank forms
+    fingerprint(env.hash_states_device(what), env's env_id_base) and the ranks' numbers -- 8 bytes each -- are gathered
+    like gather_stats' record and summed mod 2^64.  Without an initialised process group: the single-rank identity."""
+    import torch
+    import torch.distributed as dist
+
+    local = fingerprint(env.hash_states_device(what), int(env.cfg.env_id_base))
+    if not (dist.is_available() and dist.is_initialized()):
+        return local
+    if device is None:
+        on_gpu = "nccl" in str(dist.get_backend(group)) and torch.cuda.is_available()
+        device = torch.device("cuda", torch.cuda.current_device()) if on_gpu else torch.device("cpu")
+    rec = torch.tensor([_i64(local)], dtype=torch.int64, device=device)
+    out = [torch.zeros_like(rec) for _ in range(dist.get_world_size(group))]
+    dist.all_gather(out, rec, group=group)
+    return sum(int(o.item()) for o in out) & _M64
+
+
 def make_sharded(total_envs, rank=None, world=None, device=None, **kw):
     """MultiSnakeVecEnv for this rank's shard of `total_envs` global envs (env ids stay global).
 

@@ -88,6 +88,55 @@ def normalize_copy_index(index, num_envs):
     return out
 
 
+def normalize_hash_what(what):
+    """"full" / "board" (or MSNAKE_HASH_FULL / MSNAKE_HASH_BOARD) -> the `what` of msnake_hash_states."""
+    if isinstance(what, str) and what in _capi.HASH_WHAT:
+        return _capi.HASH_WHAT[what]
+    if isinstance(what, (int, np.integer)) and not isinstance(what, (bool, np.bool_)) and int(what) in _capi.HASH_WHAT.values():
+        return int(what)
+    raise ValueError(f"what must be one of {', '.join(map(repr, _capi.HASH_WHAT))}, got {what!r}")
+
+
+def check_state_stride(stride, need_words=False):
+    """The row length of a canonical-words tensor -> int: >= 0 for an export without words, >= 1 with them, >= 8 for an
+    import (no state has fewer words; checked there)."""
+    if isinstance(stride, (bool, np.bool_)) or not isinstance(stride, (int, np.integer)):
+        raise ValueError(f"stride must be an int, got {stride!r}")
+    if stride < (1 if need_words else 0) or stride > 2**31 - 1:
+        raise ValueError(f"stride must lie in [{1 if need_words else 0}, 2**31 - 1], got {stride}")
+    return int(stride)
+
+
+_MIX_C1, _MIX_C2 = np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB)
+HASH_BOARD_SKIPS = (0, 1, 2, 4, 5)  # t, ctr_lo, ctr_hi, ep_len, ep_return: the words MSNAKE_HASH_BOARD leaves out
+
+
+def mix64(z):
+    """The splitmix64 finaliser on a NumPy uint64 array (mod 2^64)."""
+    z = np.asarray(z, np.uint64)
+    z = (z ^ (z >> np.uint64(30))) * _MIX_C1
+    z = (z ^ (z >> np.uint64(27))) * _MIX_C2
+    return z ^ (z >> np.uint64(31))
+
+
+def state_hash(words, what="full"):
+    """msnake_hash_states on the host: the 64-bit hash (a Python int in [0, 2^64)) of one env's canonical words -- a
+    row of export_states_device() cut to its count, get_state_words(), a slice of a get_state_all() blob, the oracle's
+    state_to_flat().  H = sum_i mix64((i + 1) << 32 | uint32(w[i])) mod 2^64; "board" leaves out words 0, 1, 2, 4, 5 and
+    clears bit 8 of word 7."""
+    board = normalize_hash_what(what) == _capi.HASH_WHAT["board"]
+    w = np.asarray(words)
+    if w.ndim != 1 or w.shape[0] < 8 or not np.issubdtype(w.dtype, np.integer):
+        raise ValueError(f"words must be a 1-d integer array of at least 8 canonical words, got {w.dtype} {w.shape}")
+    w = (w.astype(np.int64) & 0xFFFFFFFF).astype(np.uint64)
+    keep = np.ones(len(w), bool)
+    if board:
+        keep[list(HASH_BOARD_SKIPS)] = False
+        w[7] &= np.uint64(0xFFFFFFFF & ~0x100)
+    terms = mix64((np.arange(1, len(w) + 1, dtype=np.uint64) << np.uint64(32)) | w)
+    return int(np.add.reduce(terms[keep], dtype=np.uint64))
+
+
 def normalize_views(views, n_views):
     """Selection of observation views for render_cells_device -> (view_mask, list of the selected views).
 
@@ -742,7 +791,8 @@ class MultiSnakeVecEnv:
     def arm_agents_device(self):
         """Write the tracker of agent_outcomes_device() from the env's current state, with every episode total zero
         (msnake_agent_outcomes with MSNAKE_AGENT_ARM).  The env does this itself before the next outcomes call after
-        reset_device() without a mask, set_state_words(), set_state_all(), copy_envs_device() and rollout_device(); a
+        reset_device() without a mask, set_state_words(), set_state_all(), copy_envs_device(), import_states_device() and
+        rollout_device(); a
         caller arms after anything else that moves the state without an outcomes call behind it (a step_device() whose
         outcomes were skipped, a masked reset of an env that was not done).  Returns the tracker; nothing is synchronised."""
         track = self.agent_tracker
@@ -909,6 +959,104 @@ class MultiSnakeVecEnv:
         if rc < 0:
             _capi.check(rc, "msnake_copy_envs")
         self._track_stale = True
+
+    @property
+    def state_words_max(self):
+        """The largest word count any state this env accepts can have (msnake_state_words_max): a row of that many int32
+        words holds every env, whatever is played or installed."""
+        return _capi.check(self._L.msnake_state_words_max(self._h), "msnake_state_words_max")
+
+    def _state_words(self, words, name):
+        """A canonical-words tensor: contiguous int32 [num_envs, stride] on this device.  Returns (tensor, stride)."""
+        torch = self._torch
+        if (not isinstance(words, torch.Tensor) or words.dtype != torch.int32 or words.device != self.device or words.dim() != 2 or
+                words.shape[0] != self.num_envs or not words.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int32 tensor of shape ({self.num_envs}, stride) on {self.device}")
+        return words, int(words.shape[1])
+
+    def export_states_device(self, out=None, count_out=None, stride=None, words=True, count=True):
+        """Every env's canonical words (the words of get_state_words) as rows of a device tensor, and how many each env
+        has (msnake_export_states: one launch, no host round trip).  out int32 [num_envs, stride]: row e holds env e's
+        words [0, count[e]); the words behind them are not written, and a row whose env needs more than `stride` words
+        is not written at all -- its count says so.  count_out int32 [num_envs].  Without `out` a tensor of `stride`
+        columns is allocated, state_words_max by default, which holds every env; words=False / count=False (without
+        out / count_out): that output is skipped.  Returns (words, count), None for what was not written; nothing is
+        synchronised."""
+        torch = self._torch
+        if out is not None:
+            out, have = self._state_words(out, "out")
+            if stride is not None and check_state_stride(stride, True) != have:
+                raise ValueError(f"stride {stride} differs from out's row length {have}")
+            stride = have
+        elif words:
+            stride = self.state_words_max if stride is None else check_state_stride(stride, True)
+            with torch.cuda.device(self.device):
+                out = torch.zeros((self.num_envs, stride), dtype=torch.int32, device=self.device)
+        else:
+            stride = 0 if stride is None else check_state_stride(stride)
+        if count_out is not None:
+            count_out = self._checked(count_out, "count_out", torch.int32, (self.num_envs,))
+        elif count:
+            with torch.cuda.device(self.device):
+                count_out = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        if out is None and count_out is None:
+            raise ValueError("export_states_device(): nothing to write (words=False and count=False)")
+        if out is not None and stride < 1:
+            raise ValueError("out must have at least one column")
+        rc = self._L.msnake_export_states(self._h, None if out is None else out.data_ptr(), stride,
+                                          None if count_out is None else count_out.data_ptr(),
+                                          self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_export_states")
+        return out, count_out
+
+    def import_states_device(self, words, mask=None, count=None, status_out=None):
+        """Install rows of canonical words into the envs `mask` selects (msnake_import_states: one launch, no host round
+        trip).  words int32 [num_envs, stride >= 8]; mask as for reset_device(), None = every env; count int32
+        [num_envs]: the words of each row, None = every row has `stride` words (words behind the last snake are
+        ignored).  Returns status uint8 [num_envs] (status_out if given): _capi.STATE_SKIPPED where the mask is 0,
+        _capi.STATE_OK where the row was installed exactly as set_state_words() installs it, otherwise the reason
+        (_capi.STATE_TOO_SHORT ... STATE_SCALAR) -- a refused env is left untouched, and a refusal raises nothing.  An env
+        that runs a step kernel compiled for its shape refuses a head outside the grid (STATE_CELL); one on the generic
+        kernels accepts it, as set_state_words() does.  Nothing is synchronised."""
+        torch = self._torch
+        if self._pending is not None:
+            raise RuntimeError("import_states_device() between step_async() and step_wait(): the pending step's results "
+                               "would no longer belong to the state")
+        words, stride = self._state_words(words, "words")
+        if stride < 8:
+            raise ValueError(f"words must have at least 8 columns (no state has fewer words), got {stride}")
+        p_mask = None if mask is None else self._mask(mask)
+        p_count = None if count is None else self._checked(count, "count", torch.int32, (self.num_envs,))
+        if status_out is None:
+            with torch.cuda.device(self.device):
+                status_out = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
+        else:
+            status_out = self._checked(status_out, "status_out", torch.uint8, (self.num_envs,))
+        self._track_stale = True
+        rc = self._L.msnake_import_states(self._h, None if p_mask is None else p_mask.data_ptr(), words.data_ptr(), stride,
+                                          None if p_count is None else p_count.data_ptr(), status_out.data_ptr(),
+                                          self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_import_states")
+        return status_out
+
+    def hash_states_device(self, what="full", out=None):
+        """A 64-bit hash of every env's canonical words (msnake_hash_states): int64 [num_envs] holding the 64 bits, equal
+        to msnake.state_hash(get_state_words(e), what) for every env.  what "full": every word; "board": the position
+        only (t, the draw counter, ep_len, ep_return and the finished bit left out) -- equal board hashes render the
+        same frame.  Nothing is synchronised."""
+        torch = self._torch
+        code = normalize_hash_what(what)
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.zeros(self.num_envs, dtype=torch.int64, device=self.device)
+        else:
+            out = self._checked(out, "out", torch.int64, (self.num_envs,))
+        rc = self._L.msnake_hash_states(self._h, code, out.data_ptr(), self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_hash_states")
+        return out
 
     def clone(self, num_envs=None, **overrides):
         """A new MultiSnakeVecEnv with this env's configuration; `overrides` may change what a device-side copy lets
