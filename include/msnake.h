@@ -60,6 +60,9 @@
  *                      totals, which the reference never forms: what self-play needs to learn from every column.
  *   msnake_death_causes <- is_snake_alive (snake_multiple_test.py:147-164), whose verdict the reference reduces to one bit: whether
  *                      the head left the grid, and whose body or head it lies on, for every snake that was judged.
+ *   msnake_fate_actions <- update_snake and is_snake_alive (snake_multiple_test.py:97-164) asked BEFORE the step: what each
+ *                      of a snake's five actions leads to for certain, which risks remain, the two action masks that
+ *                      follow, and the opponent that plays by them.
  *   msnake_get_stats <- the epinfobuf aggregation in ppo_multi_agent.py:288,331,366-390
  *
  * RNG contract (shared with oracle/ and tests/golden): draw i of global env g is word (i & 3) of
@@ -574,6 +577,72 @@ int msnake_copy_envs(msnake_handle dst, msnake_handle src, const int32_t* src_in
 #define MSNAKE_CAUSE_BODY 8
 int msnake_death_causes(msnake_handle after, msnake_handle before, uint8_t* cause_dev, uint8_t* by_dev, uint8_t* victims_dev,
                         int8_t* where_dev, void* stream);
+
+/* The one-step fate of every move, the two action masks that follow from it, and the opponent wary_greedy: snake_env and
+ * adversarial handles only.  Under these two rule sets every snake moves (update_snake pops, then inserts the new head,
+ * snake_multiple_test.py:97-145), then every snake is judged against the same post-move bodies (is_snake_alive,
+ * :147-164), and whether a piece stays depends only on len, grow_to and the fruit list.  So what happens to snake s if it
+ * plays action a now follows from the state, but for what the others play and for where a fruit eaten earlier in the same
+ * step respawns; those two are named as risks.  S = n_snakes, P = the snakes with len > 0.
+ *   Effective direction d(k, a) of action a in 0..4 for snake k with velocity v_k: what turn() leaves
+ *     (snake_multiple_test.py:108-115): a = 0 keeps v_k; a in 1..4 gives the move vector (+1,0), (0,+1), (-1,0), (0,-1)
+ *     unless that is the reverse of v_k, then v_k.
+ *   Standing: d == (0, 0), the state after a reset.  The snake stands: no move, no pop, no eating.
+ *   Target: T(k, a) = head_k + d(k, a); for a standing snake it is the head.
+ *   Fruit count: fruits(c) = the number of entries of the state's fruit list equal to c (adversarial: the complete list).
+ *   Pop: a moving snake s with target T pops iff len_s >= grow_to_s + 2 * fruits(T), formed without 32-bit overflow
+ *     (grow_to of an installed state may be 2^31 - 1).
+ *   Own post-move body: moving, B'_s = [T] followed by pieces 0 .. len_s - 1 - pop of the current body; standing, B'_s =
+ *     the current body.
+ *   Head-on set of another snake k in P: R_k = { head_k + d(k, b) : b in 0..4, d(k, b) != (0, 0) }, three cells for a
+ *     snake in motion and four for a standing one.
+ * fate_dev (may be NULL): uint8 [num_envs][S][5], entry [s][a], written for every snake whatever snake_mask is; a snake
+ * not in P gets 0.  For s in P any combination of
+ *   MSNAKE_FATE_WALL     T lies outside [0, dim)^2
+ *   MSNAKE_FATE_SELF     T equals a piece i >= 1 of B'_s
+ *   MSNAKE_FATE_BODY     T equals piece i of another k in P with i < len_k - 1, or with i == len_k - 1 and len_k < grow_to_k
+ *   MSNAKE_FATE_HEAD_ON  T lies in R_k for some other k in P
+ *   MSNAKE_FATE_TAIL     T equals the last piece of another k in P with len_k >= grow_to_k: a piece that goes only if k
+ *                        moves and does not eat
+ *   MSNAKE_FATE_EATS     the snake moves and fruits(T) > 0
+ *   Cells are compared as coordinate pairs, -1 and dim included; duplicates count by piece index; there is no
+ *   short-circuit: every bit that holds is set.  MSNAKE_FATE_CERTAIN = WALL | SELF | BODY, MSNAKE_FATE_RISK = HEAD_ON | TAIL.
+ * by_dev (may be NULL): uint8 [num_envs][S][5]: bit k (0..3) is set iff HEAD_ON holds against snake k, bit 4 + k iff TAIL
+ *   holds against snake k.
+ * eat_dev (may be NULL): uint8 [num_envs][S][5]: min(255, fruits(T)) for a moving snake, else 0.
+ * mask_dev (may be NULL): uint8 [num_envs][S][2]: [0] has bit a (0..4) set iff fate[s][a] & CERTAIN == 0 (the move can be
+ *   survived), [1] iff fate[s][a] & (CERTAIN | RISK) == 0 (the move is survived whatever the others do); both are 0 for a
+ *   snake not in P.
+ * No output needs any alignment.
+ * actions_dev: int32 [num_envs][action_stride]; entry s of every row is written for each s with bit s of snake_mask set,
+ * all other entries are left untouched.  The policy wary_greedy: the action is 0 for a snake not in P; otherwise the
+ * candidates are the a in 1..4 with bit a of mask[1] set, if there are none those with bit a of mask[0] set, and if there
+ * are still none the action is 0; the action is the first candidate, in the order 1, 2, 3, 4, whose T(s, a) has the
+ * strictly smallest L1 distance to any fruit of the state's fruit list (distance 0 when the list is empty): safe_greedy's
+ * rule.
+ * Guarantees, for one msnake_step from the state with snake s playing a, and for every choice of the other snakes' actions:
+ *   1. fate & CERTAIN != 0  =>  s is dead after the step;
+ *   2. fate & (CERTAIN | RISK) == 0  =>  s is alive after the step;
+ *   3. HEAD_ON against k without a CERTAIN bit  =>  there is an action of k under which s dies;
+ *   4. for snake 0, which moves first: whenever it survives, the step's reward equals fruits(T).
+ * TAIL carries no such converse: a fruit that an earlier snake ate may respawn under k's head, so the bit is a named risk
+ * and not a prediction.
+ * Like its scripted siblings the call only reads the handle's state, draws no random numbers, allocates nothing, does not
+ * synchronise and adds nothing to env_steps; asynchronous on `stream`, and it can be captured into a HIP graph in front of
+ * the step.  Refusals, before any device work and in this order: MSNAKE_E_HANDLE for a NULL or destroyed handle;
+ * MSNAKE_E_ARG for new_world rules (they judge one snake after the other and clear bodies as they go, see
+ * msnake_death_causes); for a snake_mask bit >= n_snakes; for actions_dev NULL or action_stride < n_snakes when snake_mask
+ * != 0; for nothing to write (snake_mask 0 and all four outputs NULL). */
+#define MSNAKE_FATE_WALL 1
+#define MSNAKE_FATE_SELF 2
+#define MSNAKE_FATE_BODY 4
+#define MSNAKE_FATE_HEAD_ON 8
+#define MSNAKE_FATE_TAIL 16
+#define MSNAKE_FATE_EATS 32
+#define MSNAKE_FATE_CERTAIN (MSNAKE_FATE_WALL | MSNAKE_FATE_SELF | MSNAKE_FATE_BODY)
+#define MSNAKE_FATE_RISK (MSNAKE_FATE_HEAD_ON | MSNAKE_FATE_TAIL)
+int msnake_fate_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride,
+                        uint8_t* fate_dev, uint8_t* by_dev, uint8_t* eat_dev, uint8_t* mask_dev, void* stream);
 
 /* The observation as cell codes, computed on the device from the current state of every env: what the reference's
  * frame (get_ob_for_snake / get_multi_snake_ob, snake_multiple_test.py:35-58,93-95) shows before its colour table is

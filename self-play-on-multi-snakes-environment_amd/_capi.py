@@ -35,6 +35,11 @@ SCRIPTED_POLICY_NAMES = ("safe_greedy", "hamiltonian", SPACE_POLICY, TERRITORY_P
 TIMED_POLICY = "timed_greedy"  # likewise (msnake_timed_actions)
 SCRIPTED_OPPONENT_NAMES = SCRIPTED_POLICY_NAMES + (PATH_POLICY,)  # the scripted opponents with static bodies
 SCRIPTED_PLAYER_NAMES = SCRIPTED_OPPONENT_NAMES + (TIMED_POLICY,)  # every scripted opponent there is
+WARY_POLICY = "wary_greedy"  # likewise (msnake_fate_actions)
+SCRIPTED_NAMES = SCRIPTED_PLAYER_NAMES + (WARY_POLICY,)  # ... and the one that plays by the fates of its moves
+# MSNAKE_FATE_*: the bits of msnake_fate_actions' fate output, and the two groups its masks are made of
+FATE_WALL, FATE_SELF, FATE_BODY, FATE_HEAD_ON, FATE_TAIL, FATE_EATS = 1, 2, 4, 8, 16, 32
+FATE_CERTAIN, FATE_RISK = FATE_WALL | FATE_SELF | FATE_BODY, FATE_HEAD_ON | FATE_TAIL
 HEAD_NONE, OWNER_TIE, OWNER_NONE = 0xFFFF, 0xFE, 0xFF  # MSNAKE_HEAD_NONE, MSNAKE_OWNER_TIE, MSNAKE_OWNER_NONE: msnake_head_fields
 AGENT_ARM = 1  # MSNAKE_AGENT_ARM: msnake_agent_outcomes writes the tracker from the state
 AGENT_ALIVE, AGENT_WAS_ALIVE, AGENT_DIED, AGENT_ENDED = 1, 2, 4, 8  # MSNAKE_AGENT_*: the bits of its flags output
@@ -114,6 +119,9 @@ PROTOTYPES = {
     "msnake_head_fields": (_int, [_vp, _u32, _vp, _vp, _vp, _vp]),
     # after, before, cause_dev, by_dev, victims_dev (uint8 [num_envs][n_snakes]), where_dev (int8 [num_envs][n_snakes][2]), stream
     "msnake_death_causes": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # h, snake_mask, actions_dev, action_stride, fate_dev, by_dev, eat_dev (uint8 [num_envs][n_snakes][5]),
+    # mask_dev (uint8 [num_envs][n_snakes][2]), stream
+    "msnake_fate_actions": (_int, [_vp, _u32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "msnake_state_words_max": (_i32, [_vp]),  # h
     # h, words_dev (int32 [num_envs][stride] or NULL), stride, count_dev (int32 [num_envs] or NULL), stream
     "msnake_export_states": (_int, [_vp, _vp, _i32, _vp, _vp]),

@@ -113,7 +113,7 @@ void fill_call(msnake::StepParams& p, const int32_t* actions, int32_t action_str
     p.obs = obs; p.rest.rew = rew; p.rest.done = done; p.rest.info = info;
 }
 
-// the arguments of a call that may write actions (msnake_scripted_ / _space_ / _territory_ / _path_ / _timed_actions); the last two count only if it does
+// the arguments of a call that may write actions (msnake_scripted_ / _space_ / _territory_ / _path_ / _timed_ / _fate_actions); the last two count only if it does
 int check_action_writer(const char* fn, int ns, bool writes_actions, uint32_t snake_mask, const int32_t* actions_dev, int32_t action_stride) {
     if (snake_mask >> ns) return fail(MSNAKE_E_ARG, "%s: snake_mask 0x%x has a bit >= n_snakes=%d", fn, snake_mask, ns);
     if (!writes_actions) return MSNAKE_OK;
@@ -555,6 +555,20 @@ int msnake_timed_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_
     if ((uintptr_t)life_dev & 1) return fail(MSNAKE_E_ALIGN, "life_dev must be 2-byte aligned");
     DeviceGuard guard(h->cfg.device);
     return launched(msnake::launch_timed(h->p, h->cfg.rules, snake_mask, actions_dev, action_stride, safe_dev, reach_dev, life_dev,
+                                         static_cast<hipStream_t>(stream)));
+}
+
+int msnake_fate_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride, uint8_t* fate_dev,
+                        uint8_t* by_dev, uint8_t* eat_dev, uint8_t* mask_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    if (h->cfg.rules == MSNAKE_RULES_NEW_WORLD)
+        return fail(MSNAKE_E_ARG, "msnake_fate_actions: new_world judges its snakes one after the other and clears bodies as it "
+                                  "goes, so the fate of a move does not follow from the state");
+    if (int rc = check_action_writer("msnake_fate_actions", h->p.n_snakes, snake_mask != 0, snake_mask, actions_dev, action_stride)) return rc;
+    if (!snake_mask && !fate_dev && !by_dev && !eat_dev && !mask_dev)
+        return fail(MSNAKE_E_ARG, "msnake_fate_actions: nothing to write (snake_mask 0, fate_dev, by_dev, eat_dev and mask_dev are NULL)");
+    DeviceGuard guard(h->cfg.device);
+    return launched(msnake::launch_fates(h->p, h->cfg.rules, snake_mask, actions_dev, action_stride, fate_dev, by_dev, eat_dev, mask_dev,
                                          static_cast<hipStream_t>(stream)));
 }
 

@@ -237,6 +237,10 @@ hipError_t launch_heads(const StepParams& p, int rules, uint32_t snake_mask, uin
 // cell lifetimes, the timed reach of every move and the timed_greedy opponent (msnake_timed.inc); reads the handle's state only
 hipError_t launch_timed(const StepParams& p, int rules, uint32_t snake_mask, int32_t* actions, int32_t action_stride, uint8_t* safe,
                         uint16_t* reach, uint16_t* life, hipStream_t stream);
+// the fate of every move, the two action masks and the wary_greedy opponent (msnake_fates.inc); any of the four outputs may be
+// NULL.  Reads the handle's state only
+hipError_t launch_fates(const StepParams& p, int rules, uint32_t snake_mask, int32_t* actions, int32_t action_stride, uint8_t* fate,
+                        uint8_t* by, uint8_t* eat, uint8_t* mask, hipStream_t stream);
 // env state of `src` into `dst`, one wave per destination env (msnake_copy.inc); src_index NULL = the identity.  Reads `src` only
 hipError_t launch_copy_envs(const StepParams& dst, const StepParams& src, int rules, const int32_t* src_index, hipStream_t stream);
 // why each snake died in the step between `before` and `after`, and on whose body (msnake_causes.inc); any of the four

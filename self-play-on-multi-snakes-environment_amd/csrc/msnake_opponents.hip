@@ -21,3 +21,4 @@
 #include "msnake_timed.inc"      // msnake_timed_actions: cell lifetimes, the timed reach and timed_greedy
 #include "msnake_local.inc"      // msnake_render_local: head-centred cell-code windows per snake
 #include "msnake_rays.inc"       // msnake_render_rays: eight-direction ray observations per snake
+#include "msnake_fates.inc"      // msnake_fate_actions: the fate of every move, the masks and wary_greedy

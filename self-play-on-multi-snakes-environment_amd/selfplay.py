@@ -33,7 +33,8 @@ import torch.nn.functional as F
 
 from ._capi import SCRIPTED_POLICY_NAMES as SCRIPTED_POLICIES
 from ._capi import SCRIPTED_OPPONENT_NAMES as SCRIPTED_OPPONENTS  # SCRIPTED_POLICIES and path_greedy
-from ._capi import SCRIPTED_PLAYER_NAMES as SCRIPTED_PLAYERS  # SCRIPTED_OPPONENTS and timed_greedy: what a ScriptedOpponent may play
+from ._capi import SCRIPTED_PLAYER_NAMES as SCRIPTED_PLAYERS  # SCRIPTED_OPPONENTS and timed_greedy
+from ._capi import SCRIPTED_NAMES  # SCRIPTED_PLAYERS and wary_greedy: what a ScriptedOpponent may play
 from ._capi import AGENT_ENDED, AGENT_WAS_ALIVE
 from ._capi import CAUSE_BODY, CAUSE_HEAD_ON, CAUSE_SELF, CAUSE_WALL
 from .vec_env import check_radius, relative_to_absolute
@@ -485,7 +486,7 @@ class ScriptedColumns:
 
 class ScriptedOpponent:
     """A fixed, deterministic opponent in the place of a CnnPolicy: snake `snake` plays the env's on-device scripted
-    `policy` (one of SCRIPTED_PLAYERS, MultiSnakeVecEnv.scripted_actions_device).  step(obs) has the shape
+    `policy` (one of SCRIPTED_NAMES, MultiSnakeVecEnv.scripted_actions_device).  step(obs) has the shape
     Runner.multi_step calls; the observation is ignored, the env's state is asked.  eps > 0: with probability eps
     the action is replaced by randint(0, 5), drawn with torch on the env's device from `generator` (the env's own
     random numbers are never used).  On its own (columns=None) every step() is one env call.  Several opponents of one
@@ -493,8 +494,8 @@ class ScriptedOpponent:
     columns.refresh(), which the driver calls before the members' step()."""
 
     def __init__(self, env, policy, snake, eps=0.0, generator=None, columns=None):
-        if policy not in SCRIPTED_PLAYERS:
-            raise ValueError(f"policy must be one of {', '.join(map(repr, SCRIPTED_PLAYERS))}, got {policy!r}")
+        if policy not in SCRIPTED_NAMES:
+            raise ValueError(f"policy must be one of {', '.join(map(repr, SCRIPTED_NAMES))}, got {policy!r}")
         if not 0 <= int(snake) < env.n_snakes:
             raise ValueError(f"snake must lie in [0, {env.n_snakes}), got {snake!r}")
         self.env, self.policy, self.snake, self.eps, self.generator = env, policy, int(snake), float(eps), generator

@@ -229,6 +229,9 @@ CLONE_OVERRIDES = ("record_policy", "envs_per_block", "obs_scale", "auto_reset",
 AgentOutcomes = collections.namedtuple("AgentOutcomes", ("rew", "ate", "flags", "info"))
 # what death_causes_device() / step_agents_device(causes=True) return of msnake_death_causes, likewise
 DeathCauses = collections.namedtuple("DeathCauses", ("cause", "by", "victims", "where"))
+# what move_fates_device() returns of msnake_fate_actions, likewise: fate, by and eat are uint8 [num_envs, n_snakes, 5],
+# mask is uint8 [num_envs, n_snakes, 2]
+MoveFates = collections.namedtuple("MoveFates", ("fate", "by", "eat", "mask"))
 
 
 class LazyInfos:
@@ -382,6 +385,7 @@ class MultiSnakeVecEnv:
         # msnake_death_causes: the env's own outputs and the snapshot env of step_agents_device(causes=True), on first use
         self._causes_fn = self._L.msnake_death_causes
         self._causes_own = self._snapshot = None
+        self._fates_fn = self._L.msnake_fate_actions
 
     # ------------------------------------------------------------------ device-side API
     def _stream(self):
@@ -463,7 +467,7 @@ class MultiSnakeVecEnv:
         return (self.num_envs, self.n_snakes, 4)
 
     def scripted_actions_device(self, policy, snakes=None, out=None, safe_out=None, space_out=None, territory_out=None,
-                                path_out=None, field_out=None, reach_out=None, life_out=None):
+                                path_out=None, field_out=None, reach_out=None, life_out=None, fates_out=None):
         """Actions of a scripted policy ("safe_greedy", "hamiltonian", "space_greedy", "territory_greedy", "path_greedy", "timed_greedy", or None for the mask alone) for the
         snakes in `snakes` (indices; default every snake), computed on the device from the env's current state.  They go to
         columns `snakes` of `out`, an int32 [num_envs, >= n_snakes] device tensor as step_device() takes it; its other
@@ -486,15 +490,24 @@ class MultiSnakeVecEnv:
         that may enter a body cell once the piece lying there has moved on; only with it, `reach_out`, a uint16
         [num_envs, n_snakes, 4] device tensor, gets those counts (see timed_reach_device) and `life_out`, a uint16
         [num_envs, dim, dim] device tensor, the lifetime of every cell (see cell_lifetimes_device).  The return order
-        is actions, safe, reach, life for those asked for."""
+        is actions, safe, reach, life for those asked for.
+        "wary_greedy" (msnake_fate_actions; snake_env and adversarial) plays by the fate of its moves: among the moves
+        that are survived whatever the others do -- if there is none, among those that can be survived -- the one closest
+        to a fruit; a move onto a tail that goes is open to it, a cell another head can enter is not.  It writes no
+        safe-move mask (safe_out is refused); only with it, `fates_out`, a MoveFates of tensors (or None) as
+        move_fates_device() takes them, is written in the same call.  Returns `out`, or (out, fates_out)."""
         torch = self._torch
         given = {"space_out": space_out, "territory_out": territory_out, "path_out": path_out, "field_out": field_out,
                  "reach_out": reach_out, "life_out": life_out}
         for kw, t in given.items():
             if t is not None and policy != COUNT_OUTPUTS[kw]:
                 raise ValueError(f"{kw} is written by policy {COUNT_OUTPUTS[kw]!r} only, got policy {policy!r}")
+        if fates_out is not None and policy != _capi.WARY_POLICY:
+            raise ValueError(f"fates_out is written by policy {_capi.WARY_POLICY!r} only, got policy {policy!r}")
+        if policy == _capi.WARY_POLICY and safe_out is not None:
+            raise ValueError(f"policy {_capi.WARY_POLICY!r} writes no safe-move mask: ask fate_masks_device() or pass fates_out")
         count = COUNT_POLICIES.get(policy)
-        if count is None and policy not in _capi.SCRIPTED_POLICY:
+        if count is None and policy != _capi.WARY_POLICY and policy not in _capi.SCRIPTED_POLICY:
             raise ValueError(f"policy must be 'safe_greedy', 'hamiltonian' or None, got {policy!r}")
         if snakes is None:
             bits = (1 << self.n_snakes) - 1
@@ -515,6 +528,14 @@ class MultiSnakeVecEnv:
         p_safe = None
         if safe_out is not None:
             p_safe = self._checked(safe_out, "safe_out", torch.uint8, (self.num_envs, self.n_snakes)).data_ptr()
+        if policy == _capi.WARY_POLICY:
+            fates = None if fates_out is None else self._fates_checked(fates_out)
+            rc = self._fates_fn(self._h, bits, out.data_ptr(), int(out.shape[1]),
+                                *([None] * 4 if fates is None else [None if t is None else t.data_ptr() for t in fates]),
+                                self._cur_stream(self.device).cuda_stream)
+            if rc < 0:
+                _capi.check(rc, "msnake_fate_actions")
+            return out if fates is None else (out, fates)
         if count is not None:
             fn, c_name, kws = count
             p_counts = [None if given[kw] is None else
@@ -599,6 +620,52 @@ class MultiSnakeVecEnv:
         maximum over stacked pieces; 0 for a cell under no body; 0xFFFF (msnake_timed_actions: MSNAKE_LIFE_NEVER) for
         every body cell of a new_world handle without fruits.  On the device; nothing is synchronised."""
         return self._counts_device("life_out", out)
+
+    def _fates_checked(self, out):
+        """A MoveFates (or any four-entry sequence) of caller-supplied tensors, None for what is not written."""
+        if len(out) != 4:
+            raise ValueError(f"a MoveFates has four entries (fate, by, eat, mask), got {len(out)}")
+        n, ns, u8 = self.num_envs, self.n_snakes, self._torch.uint8
+        return MoveFates(*[None if t is None else self._checked(t, f"{name}_out", u8, (n, ns, 2 if name == "mask" else 5))
+                           for name, t in zip(MoveFates._fields, out)])
+
+    def move_fates_device(self, fate=True, by=False, eat=False, mask=True, out=None):
+        """What each of a snake's five actions leads to in the next step (msnake_fate_actions; snake_env and
+        adversarial), as a MoveFates of uint8 device tensors, None for what was not asked for:
+        fate [num_envs, n_snakes, 5]: entry [s, a] holds the FATE_* bits (_capi) of snake s playing action a: FATE_WALL,
+        FATE_SELF, FATE_BODY (together FATE_CERTAIN: the snake dies whatever the others do), FATE_HEAD_ON, FATE_TAIL
+        (together FATE_RISK: another head can enter the cell / another snake's last piece lies there and goes only if
+        that snake moves and does not eat) and FATE_EATS;
+        by [num_envs, n_snakes, 5]: bit k: HEAD_ON holds against snake k, bit 4 + k: TAIL holds against snake k;
+        eat [num_envs, n_snakes, 5]: how many fruits the move eats (at most 255);
+        mask [num_envs, n_snakes, 2]: [.., 0] has bit a set iff action a can be survived (no CERTAIN bit), [.., 1] iff it is
+        survived whatever the others do (no CERTAIN and no RISK bit): the action masks of masked PPO.
+        An empty body gives 0 everywhere.  `out`: a MoveFates of tensors to write into (None entries are not written;
+        the flags are ignored); without it the flags choose, and the tensors are fresh.  One launch; nothing is
+        synchronised, no random numbers are drawn and no env state changes."""
+        torch = self._torch
+        if out is None:
+            n, ns = self.num_envs, self.n_snakes
+            with torch.cuda.device(self.device):
+                out = MoveFates(*[torch.empty((n, ns, 2 if name == "mask" else 5), dtype=torch.uint8, device=self.device) if want else None
+                                  for name, want in zip(MoveFates._fields, (fate, by, eat, mask))])
+        res = self._fates_checked(out)
+        if all(t is None for t in res):
+            raise ValueError("move_fates_device: nothing to write (fate, by, eat and mask are all off)")
+        rc = self._fates_fn(self._h, 0, None, 0, *[None if t is None else t.data_ptr() for t in res],
+                            self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_fate_actions")
+        return res
+
+    def fate_masks_device(self, out=None):
+        """uint8 [num_envs, n_snakes, 2]: the two action masks of move_fates_device() alone: bit a (0..4) of [.., 0] is set
+        iff action a can be survived, of [.., 1] iff it is survived whatever the other snakes do.  Unlike
+        safe_moves_device() a move onto a tail that goes is open and a cell another head can enter is not.  Nothing is
+        synchronised."""
+        if out is None:
+            return self.move_fates_device(fate=False, mask=True).mask
+        return self.move_fates_device(out=MoveFates(None, None, None, out)).mask
 
     def head_fields_shape(self, snakes=None):
         """(P, dim, dim): one env's distance planes of head_fields_device(snakes)."""

@@ -19,7 +19,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--weights", default=None, help="weights file written by selfplay.save_weights")
     ap.add_argument("--random", action="store_true", help="a freshly initialised policy instead of --weights")
-    ap.add_argument("--opponent", choices=msnake._capi.SCRIPTED_OPPONENT_NAMES + (msnake._capi.TIMED_POLICY,), default="safe_greedy")
+    ap.add_argument("--opponent", choices=msnake._capi.SCRIPTED_OPPONENT_NAMES + (msnake._capi.TIMED_POLICY,) + (msnake._capi.WARY_POLICY,), default="safe_greedy")
     ap.add_argument("--eps", type=float, default=0.0, help="share of opponent actions replaced by a random one")
     ap.add_argument("--episodes", type=int, default=1000)
     ap.add_argument("--envs", type=int, default=1024)

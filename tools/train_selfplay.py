@@ -28,7 +28,7 @@ def main():
     ap.add_argument("--save-interval", type=int, default=0, help="also save snake_model_num<N>_<k>.pt every this many updates")
     ap.add_argument("--load", default=None, metavar="FILE", help="initialise learner and opponents from a weights file")
     ap.add_argument("--resume", action="store_true", help="continue from <--save DIR>/trainer_state.pt")
-    ap.add_argument("--opponent", choices=("pool",) + msnake._capi.SCRIPTED_OPPONENT_NAMES + (msnake._capi.TIMED_POLICY,), default="pool",
+    ap.add_argument("--opponent", choices=("pool",) + msnake._capi.SCRIPTED_OPPONENT_NAMES + (msnake._capi.TIMED_POLICY,) + (msnake._capi.WARY_POLICY,), default="pool",
                     help="who plays the other snakes: past selves from the pool, or a fixed on-device scripted policy")
     ap.add_argument("--local-radius", type=int, default=None, metavar="R",
                     help="train window policies on each snake's head-centred (2R+1)x(2R+1) cell-code window instead of the frame")
