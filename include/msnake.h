@@ -790,6 +790,58 @@ int msnake_render_rays(msnake_handle h, uint32_t snake_mask, int32_t oriented, u
 int msnake_agent_outcomes(msnake_handle h, int32_t flags, int32_t* track_dev, const uint8_t* done_dev, float* rew_dev,
                           uint8_t* ate_dev, uint8_t* flags_dev, int32_t* info_dev, void* stream);
 
+/* Scripted playouts: play every env on for up to n_steps steps with a fixed policy per snake, in ONE launch, and report
+ * who ate, who died and where it ended -- the value of a position for a search over forks.  The call stands for
+ * n_steps x [msnake_scripted_actions / msnake_fate_actions -> msnake_step -> msnake_agent_outcomes] on a scratch copy of
+ * the handle, without the copy: the handle is only read.  It restates update_snake, is_snake_alive and step of the
+ * reference (snake_multiple_test.py:97-197), iterated.  S = n_snakes in every shape below.
+ * Rule set: snake_env handles only.  adversarial and new_world are MSNAKE_E_ARG (new_world judges its snakes one after
+ * the other, as for msnake_death_causes; the adversarial fruit list can grow to fcap entries).
+ * Per env, with s_0 its canonical state (the words of msnake_get_state):
+ *   - if bit 8 of word 7 (`finished`) is set: steps = 0, end = MSNAKE_PLAYOUT_FINISHED, ret = 0, info = 0, and the end
+ *     state is s_0;
+ *   - otherwise, for k = 1, 2, ..., n_steps: the action of snake s in step 1 is first_dev[env][s] (row stride
+ *     first_stride) if bit s of first_mask is set, taken exactly as msnake_step takes an action word, invalid codes
+ *     included.  In any other step, or without that bit, it is policies[s] applied to s_(k-1), the very word the
+ *     policy's own entry point would write: MSNAKE_POLICY_NONE the constant 0, MSNAKE_POLICY_SAFE_GREEDY and
+ *     MSNAKE_POLICY_HAMILTONIAN what msnake_scripted_actions writes, MSNAKE_POLICY_WARY_GREEDY what msnake_fate_actions
+ *     writes.  s_k is what one msnake_step makes of s_(k-1) on a handle with the same seed, the same global env id
+ *     (env_id_base + index) and the same max_steps, with auto_reset = 0: the same Philox draws at the same counter, the
+ *     same respawns, t, ep_len, ep_return, and `finished` once done.  The playout of an env stops behind the first step
+ *     whose done is set.  The handle's own auto_reset plays no part: nothing is ever reset.
+ * Per snake and played step, as msnake_agent_outcomes counts: was = len before > 0, died = was && len after == 0,
+ * ate = max(0, grow_to after - grow_to before) >> 1, rew = died ? -1 : ate.
+ * Outputs, each may be NULL but not all six:
+ *   steps_dev int32 [num_envs]: the steps played.
+ *   end_dev   uint8 [num_envs]: MSNAKE_PLAYOUT_HORIZON (n_steps played, the last one not done), _DEAD (the main snake
+ *             died; it wins over _CAP when both hold), _CAP (t reached max_steps) or _FINISHED.
+ *   ret_dev   float32 [num_envs][S]: the sum of rew; column 0 equals the sum of the steps' own rew_dev bit for bit.
+ *   info_dev  int32 [num_envs][S][4]: the sum of ate (the death step's included, as ep_fruit), the number of steps at
+ *             whose end the snake was alive, the 1-based playout step of its death (0 = none), and the action word it
+ *             played in step 1 (0 when no step was played).
+ *   words_dev int32 [num_envs][words_stride] and count_dev int32 [num_envs]: the end state, under exactly the contract
+ *             of msnake_export_states: the count is always written, and no word of a row that does not fit is.  So
+ *             msnake_import_states(scratch, ..., words_dev, ...) continues the game where the playout ended.
+ * The handle is only read: record, rings, parked draws and draw counter stay byte for byte, env_steps and errors do not
+ * move.  The call allocates nothing, never synchronises and can be captured into a HIP graph.  It works on any snake_env
+ * handle, also one on a step kernel compiled for its shape, one holding a head outside the grid, and bodies in the
+ * overflow ring.  The capacity rule of msnake_set_state holds inside the playout as in the step: a body that would pass
+ * cap - 1 pieces drops its oldest piece; here it is not counted.
+ * Refusals, before any device work, in this order: MSNAKE_E_HANDLE; MSNAKE_E_ARG for rules other than snake_env, n_steps
+ * outside [1, MSNAKE_PLAYOUT_MAX_STEPS], policies NULL or policies[s] outside 0..3 for an s < S (entries s >= S are not
+ * looked at), MSNAKE_POLICY_HAMILTONIAN on an odd board, a first_mask bit >= S, first_mask != 0 with first_dev NULL or
+ * first_stride < S, words_dev with words_stride <= 0, all six outputs NULL; MSNAKE_E_ALIGN for an int32 or float pointer
+ * that is not 4-byte aligned. */
+#define MSNAKE_POLICY_WARY_GREEDY 3 /* msnake_playout only; msnake_scripted_actions keeps refusing it */
+#define MSNAKE_PLAYOUT_MAX_STEPS 4096
+#define MSNAKE_PLAYOUT_HORIZON 0  /* n_steps played, episode still running       */
+#define MSNAKE_PLAYOUT_DEAD 1     /* the main snake died                         */
+#define MSNAKE_PLAYOUT_CAP 2      /* t reached max_steps, main snake alive       */
+#define MSNAKE_PLAYOUT_FINISHED 3 /* the start state had `finished` set: 0 steps */
+int msnake_playout(msnake_handle h, const int32_t policies[MSNAKE_MAX_SNAKES], int32_t n_steps, const int32_t* first_dev,
+                   int32_t first_stride, uint32_t first_mask, int32_t* steps_dev, uint8_t* end_dev, float* ret_dev,
+                   int32_t* info_dev, int32_t* words_dev, int32_t words_stride, int32_t* count_dev, void* stream);
+
 /* Copy the aggregate statistics to the host.  Blocking: waits for the device (every step issued so
  * far, on any stream) before it sums the per-env totals.  episodes / ep_len_sum / ep_return_sum /
  * errors are accumulated on the device; env_steps is counted on the host per API call, so replays

@@ -9,9 +9,9 @@ imported from here.
 from . import _capi
 from .spaces import Box, Discrete
 from .dist import all_fingerprint, fingerprint, gather_stats, make_sharded, shard_range
-from .vec_env import (GYM_IDS, HEAD_NONE, OWNER_NONE, OWNER_TIE, AgentOutcomes, DeathCauses, LazyInfos, MoveFates, MultiSnakeVecEnv, make, normalize_actions, normalize_copy_index, normalize_mask,
+from .vec_env import (GYM_IDS, HEAD_NONE, OWNER_NONE, OWNER_TIE, AgentOutcomes, DeathCauses, LazyInfos, MoveFates, MultiSnakeVecEnv, Playout, make, normalize_actions, normalize_copy_index, normalize_mask,
                       normalize_snakes, relative_to_absolute, state_hash)
 
-__all__ = ["state_hash", "fingerprint", "all_fingerprint","MultiSnakeVecEnv", "make", "GYM_IDS", "LazyInfos", "AgentOutcomes", "DeathCauses", "MoveFates", "normalize_actions", "normalize_mask", "normalize_copy_index", "normalize_snakes", "relative_to_absolute", "Box", "Discrete", "_capi",
+__all__ = ["state_hash", "fingerprint", "all_fingerprint","MultiSnakeVecEnv", "make", "GYM_IDS", "LazyInfos", "AgentOutcomes", "DeathCauses", "MoveFates", "Playout", "normalize_actions", "normalize_mask", "normalize_copy_index", "normalize_snakes", "relative_to_absolute", "Box", "Discrete", "_capi",
            "shard_range", "gather_stats", "make_sharded", "HEAD_NONE", "OWNER_TIE", "OWNER_NONE"]
 # msnake.selfplay (PyTorch self-play PPO driver, ScriptedOpponent) is imported on demand: `from msnake import selfplay`

@@ -37,6 +37,11 @@ SCRIPTED_OPPONENT_NAMES = SCRIPTED_POLICY_NAMES + (PATH_POLICY,)  # the scripted
 SCRIPTED_PLAYER_NAMES = SCRIPTED_OPPONENT_NAMES + (TIMED_POLICY,)  # every scripted opponent there is
 WARY_POLICY = "wary_greedy"  # likewise (msnake_fate_actions)
 SCRIPTED_NAMES = SCRIPTED_PLAYER_NAMES + (WARY_POLICY,)  # ... and the one that plays by the fates of its moves
+# MSNAKE_POLICY_* as msnake_playout takes them: the scripted ids and wary_greedy (msnake_scripted_actions keeps refusing 3)
+PLAYOUT_POLICY = {None: 0, "safe_greedy": 1, "hamiltonian": 2, "wary_greedy": 3}
+PLAYOUT_MAX_STEPS = 4096  # MSNAKE_PLAYOUT_MAX_STEPS
+PLAYOUT_HORIZON, PLAYOUT_DEAD, PLAYOUT_CAP, PLAYOUT_FINISHED = 0, 1, 2, 3  # MSNAKE_PLAYOUT_*: msnake_playout's end codes
+MAX_SNAKES = 4  # MSNAKE_MAX_SNAKES
 # MSNAKE_FATE_*: the bits of msnake_fate_actions' fate output, and the two groups its masks are made of
 FATE_WALL, FATE_SELF, FATE_BODY, FATE_HEAD_ON, FATE_TAIL, FATE_EATS = 1, 2, 4, 8, 16, 32
 FATE_CERTAIN, FATE_RISK = FATE_WALL | FATE_SELF | FATE_BODY, FATE_HEAD_ON | FATE_TAIL
@@ -122,6 +127,10 @@ PROTOTYPES = {
     # h, snake_mask, actions_dev, action_stride, fate_dev, by_dev, eat_dev (uint8 [num_envs][n_snakes][5]),
     # mask_dev (uint8 [num_envs][n_snakes][2]), stream
     "msnake_fate_actions": (_int, [_vp, _u32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    # h, policies (int32 [MSNAKE_MAX_SNAKES], host), n_steps, first_dev (int32 [num_envs][first_stride] or NULL), first_stride,
+    # first_mask, steps_dev (int32 [num_envs]), end_dev (uint8 [num_envs]), ret_dev (float32 [num_envs][n_snakes]),
+    # info_dev (int32 [num_envs][n_snakes][4]), words_dev (int32 [num_envs][words_stride]), words_stride, count_dev, stream
+    "msnake_playout": (_int, [_vp, ctypes.POINTER(_i32), _i32, _vp, _i32, _u32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "msnake_state_words_max": (_i32, [_vp]),  # h
     # h, words_dev (int32 [num_envs][stride] or NULL), stride, count_dev (int32 [num_envs] or NULL), stream
     "msnake_export_states": (_int, [_vp, _vp, _i32, _vp, _vp]),

@@ -572,6 +572,39 @@ int msnake_fate_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_d
                                          static_cast<hipStream_t>(stream)));
 }
 
+int msnake_playout(msnake_handle h, const int32_t policies[MSNAKE_MAX_SNAKES], int32_t n_steps, const int32_t* first_dev,
+                   int32_t first_stride, uint32_t first_mask, int32_t* steps_dev, uint8_t* end_dev, float* ret_dev, int32_t* info_dev,
+                   int32_t* words_dev, int32_t words_stride, int32_t* count_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    const int ns = h->p.n_snakes;
+    if (h->cfg.rules != MSNAKE_RULES_SNAKE_ENV)
+        return fail(MSNAKE_E_ARG, "msnake_playout: snake_env handles only (rules %d): new_world judges its snakes one after the other, "
+                                  "and the adversarial fruit list can grow to fcap entries", h->cfg.rules);
+    if (n_steps < 1 || n_steps > MSNAKE_PLAYOUT_MAX_STEPS)
+        return fail(MSNAKE_E_ARG, "msnake_playout: n_steps %d must lie in [1, %d]", n_steps, MSNAKE_PLAYOUT_MAX_STEPS);
+    if (!policies) return fail(MSNAKE_E_ARG, "msnake_playout: policies is NULL");
+    for (int s = 0; s < ns; ++s)
+        if (policies[s] < MSNAKE_POLICY_NONE || policies[s] > MSNAKE_POLICY_WARY_GREEDY)
+            return fail(MSNAKE_E_ARG, "msnake_playout: policies[%d] = %d is not one of MSNAKE_POLICY_*", s, policies[s]);
+    for (int s = 0; s < ns; ++s)
+        if (policies[s] == MSNAKE_POLICY_HAMILTONIAN && (h->p.dim & 1))
+            return fail(MSNAKE_E_ARG, "msnake_playout: policy HAMILTONIAN needs an even dim (the cycle), got dim %d", h->p.dim);
+    if (first_mask >> ns) return fail(MSNAKE_E_ARG, "msnake_playout: first_mask 0x%x has a bit >= n_snakes=%d", first_mask, ns);
+    if (first_mask && !first_dev) return fail(MSNAKE_E_ARG, "msnake_playout: first_mask is 0x%x but first_dev is NULL", first_mask);
+    if (first_mask && first_stride < ns)
+        return fail(MSNAKE_E_ARG, "msnake_playout: first_stride %d must be >= n_snakes=%d", first_stride, ns);
+    if (words_dev && words_stride <= 0) return fail(MSNAKE_E_ARG, "msnake_playout: words_dev is given but words_stride is %d", words_stride);
+    if (!steps_dev && !end_dev && !ret_dev && !info_dev && !words_dev && !count_dev)
+        return fail(MSNAKE_E_ARG, "msnake_playout: nothing to write (steps_dev, end_dev, ret_dev, info_dev, words_dev and count_dev are NULL)");
+    if (((uintptr_t)first_dev & 3) || ((uintptr_t)steps_dev & 3) || ((uintptr_t)ret_dev & 3) || ((uintptr_t)info_dev & 3) ||
+        ((uintptr_t)words_dev & 3) || ((uintptr_t)count_dev & 3))
+        return fail(MSNAKE_E_ALIGN, "first_dev, steps_dev, ret_dev, info_dev, words_dev and count_dev must be 4-byte aligned");
+    DeviceGuard guard(h->cfg.device);
+    return launched(msnake::launch_playout(h->p, h->cfg.rules, policies, n_steps, first_mask ? first_dev : nullptr, first_stride, first_mask,
+                                           steps_dev, end_dev, ret_dev, info_dev, words_dev, words_stride, count_dev,
+                                           static_cast<hipStream_t>(stream)));
+}
+
 int msnake_head_fields(msnake_handle h, uint32_t snake_mask, uint16_t* dist_dev, uint8_t* owner_dev, uint16_t* counts_dev, void* stream) {
     if (int rc = check(h)) return rc;
     const int ns = h->p.n_snakes;

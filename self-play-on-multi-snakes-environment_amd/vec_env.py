@@ -232,6 +232,8 @@ DeathCauses = collections.namedtuple("DeathCauses", ("cause", "by", "victims", "
 # what move_fates_device() returns of msnake_fate_actions, likewise: fate, by and eat are uint8 [num_envs, n_snakes, 5],
 # mask is uint8 [num_envs, n_snakes, 2]
 MoveFates = collections.namedtuple("MoveFates", ("fate", "by", "eat", "mask"))
+# what playout_device() returns: device tensors, None for what was not written
+Playout = collections.namedtuple("Playout", ("steps", "end", "ret", "info", "words", "count"))
 
 
 class LazyInfos:
@@ -1124,6 +1126,118 @@ class MultiSnakeVecEnv:
         if rc < 0:
             _capi.check(rc, "msnake_hash_states")
         return out
+
+    def _playout_policies(self, policies):
+        """One policy name for every snake, or one per snake -> (ctypes int32 [MAX_SNAKES], the ids)."""
+        if policies is None or isinstance(policies, str):
+            policies = [policies] * self.n_snakes
+        policies = list(policies)
+        if len(policies) != self.n_snakes:
+            raise ValueError(f"policies must be one name or one per snake ({self.n_snakes}), got {len(policies)}")
+        ids = []
+        for name in policies:
+            if name not in _capi.PLAYOUT_POLICY:
+                raise ValueError(f"policies must be 'safe_greedy', 'hamiltonian', 'wary_greedy' or None, got {name!r}")
+            if name == "hamiltonian" and int(self.cfg.dim) % 2:
+                raise ValueError(f"policies: 'hamiltonian' needs an even dim (the cycle), got dim {int(self.cfg.dim)}")
+            ids.append(_capi.PLAYOUT_POLICY[name])
+        return (ctypes.c_int32 * _capi.MAX_SNAKES)(*ids), ids
+
+    def playout_device(self, n_steps, policies="safe_greedy", first_actions=None, first_snakes=None, end_state=False, out=None):
+        """Play every env on for up to `n_steps` steps with a scripted policy per snake, in one launch, without touching
+        the env (msnake_playout; snake_env): the value of a position.  `policies`: one of "safe_greedy", "hamiltonian",
+        "wary_greedy" or None (the constant action 0) for all snakes, or one per snake.  `first_actions`, an int32
+        [num_envs, >= n_snakes] device tensor as step_device() takes it, forces the first action of the snakes in
+        `first_snakes` (indices; default every snake); the other snakes, and every later step, follow their policy.
+        Returns a Playout of device tensors: steps int32 [num_envs] (steps played; an env stops behind its first done
+        step), end uint8 [num_envs] (_capi.PLAYOUT_HORIZON / _DEAD / _CAP / _FINISHED), ret float32 [num_envs, n_snakes]
+        (every snake's summed reward, -1 for its death and +1 per fruit), info int32 [num_envs, n_snakes, 4] (fruits
+        eaten, steps survived, the 1-based step of its death or 0, the action word of step 1); with `end_state` also
+        words int32 [num_envs, state_words_max] and count int32 [num_envs], the state each playout ended in, as
+        export_states_device() writes them and import_states_device() takes them -- else None.  `out`: a Playout (or
+        six-entry sequence) of tensors to write into, None for what is not wanted; `end_state` is then ignored and
+        words may have any stride.  Nothing is synchronised; no random number of the env is consumed."""
+        torch = self._torch
+        n, ns, dev = self.num_envs, self.n_snakes, self.device
+        if int(n_steps) != n_steps or not 1 <= int(n_steps) <= _capi.PLAYOUT_MAX_STEPS:
+            raise ValueError(f"n_steps must lie in [1, {_capi.PLAYOUT_MAX_STEPS}], got {n_steps!r}")
+        if self.cfg.rules != _capi.RULES["snake_env"]:
+            raise ValueError(f"playout_device() needs a snake_env env, got rules {_capi.RULE_NAMES[int(self.cfg.rules)]!r}")
+        pol, _ = self._playout_policies(policies)
+        bits, p_first, stride = 0, None, 0
+        if first_actions is None:
+            if first_snakes is not None:
+                raise ValueError("first_snakes needs first_actions")
+        else:
+            if (not isinstance(first_actions, torch.Tensor) or first_actions.dtype != torch.int32 or first_actions.device != dev or
+                    first_actions.dim() != 2 or first_actions.shape[0] != n or first_actions.shape[1] < ns or
+                    not first_actions.is_contiguous()):
+                raise ValueError(f"first_actions must be a contiguous int32 tensor of shape ({n}, >= {ns}) on {dev}")
+            if first_snakes is None:
+                bits = (1 << ns) - 1
+            else:
+                for s in first_snakes:
+                    if int(s) != s or not 0 <= int(s) < ns:
+                        raise ValueError(f"first_snakes: snake indices must lie in [0, {ns}), got {s!r}")
+                    bits |= 1 << int(s)
+            if bits:
+                p_first, stride = first_actions.data_ptr(), int(first_actions.shape[1])
+        if out is None:
+            out = Playout(torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev),
+                          torch.zeros((n, ns), dtype=torch.float32, device=dev),
+                          torch.zeros((n, ns, 4), dtype=torch.int32, device=dev),
+                          torch.zeros((n, self.state_words_max), dtype=torch.int32, device=dev) if end_state else None,
+                          torch.zeros(n, dtype=torch.int32, device=dev) if end_state else None)
+        elif len(out) != 6:
+            raise ValueError(f"out: a Playout has six entries (steps, end, ret, info, words, count), got {len(out)}")
+        want = (("steps", torch.int32, (n,)), ("end", torch.uint8, (n,)), ("ret", torch.float32, (n, ns)),
+                ("info", torch.int32, (n, ns, 4)))
+        res = [None if t is None else self._checked(t, f"out.{name}", dt, shape) for t, (name, dt, shape) in zip(out[:4], want)]
+        words, wstride = (None, 0) if out[4] is None else self._state_words(out[4], "out.words")
+        if words is not None and wstride < 1:
+            raise ValueError("out.words must have at least one column")
+        count = None if out[5] is None else self._checked(out[5], "out.count", torch.int32, (n,))
+        res = Playout(*res, words, count)
+        if all(t is None for t in res):
+            raise ValueError("out: nothing to write (all six entries are None)")
+        rc = self._L.msnake_playout(self._h, pol, int(n_steps), p_first, stride, bits,
+                                    *[None if t is None else t.data_ptr() for t in res[:5]], wstride,
+                                    None if count is None else count.data_ptr(), self._cur_stream(dev).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_playout")
+        return res
+
+    def playout_values_device(self, scratch, n_steps, snake=0, reps=1, policies="safe_greedy"):
+        """The value of each of `snake`'s four moves in every env, by playouts on forks: (value, survive), both float32
+        [num_envs, 4].  `scratch`: an env of the same board with num_envs * 4 * reps envs; env e is copied into its slots
+        (e * 4 + m) * reps + r (copy_envs_device), and one playout_device() of n_steps steps there forces `snake`'s first
+        action to m + 1, everything else following `policies`.  value[e, m] is the mean over r of the snake's summed
+        reward, survive[e, m] the share of the reps in which it did not die.  The slots draw from their own random
+        streams at the copied counter, which is what makes the reps differ.  Two launches and a few torch reductions;
+        nothing is synchronised and this env is only read."""
+        torch = self._torch
+        n, ns = self.num_envs, self.n_snakes
+        if int(snake) != snake or not 0 <= int(snake) < ns:
+            raise ValueError(f"snake must lie in [0, {ns}), got {snake!r}")
+        if int(reps) != reps or int(reps) < 1:
+            raise ValueError(f"reps must be >= 1, got {reps!r}")
+        snake, reps = int(snake), int(reps)
+        if not isinstance(scratch, MultiSnakeVecEnv):
+            raise TypeError(f"scratch must be a MultiSnakeVecEnv, got {type(scratch).__name__}")
+        if scratch.num_envs != n * 4 * reps:
+            raise ValueError(f"scratch must have num_envs * 4 * reps = {n * 4 * reps} envs, got {scratch.num_envs}")
+        key = (scratch.num_envs, snake, reps)
+        if getattr(self, "_playout_plan", (None,))[0] != key:
+            slot = torch.arange(n * 4 * reps, device=self.device)
+            first = torch.zeros((n * 4 * reps, ns), dtype=torch.int32, device=self.device)
+            first[:, snake] = ((slot // reps) % 4 + 1).to(torch.int32)
+            self._playout_plan = (key, (slot // (4 * reps)).to(torch.int32), first)
+        _, index, first = self._playout_plan
+        scratch.copy_envs_device(self, index)
+        res = scratch.playout_device(n_steps, policies, first_actions=first, first_snakes=[snake])
+        value = res.ret[:, snake].reshape(n, 4, reps).mean(dim=2)
+        survive = (res.info[:, snake, 2] == 0).to(torch.float32).reshape(n, 4, reps).mean(dim=2)
+        return value, survive
 
     def clone(self, num_envs=None, **overrides):
         """A new MultiSnakeVecEnv with this env's configuration; `overrides` may change what a device-side copy lets
