@@ -489,3 +489,29 @@ def assert_words(got, want, what=None):
     assert len(got) == len(want)
     bad = [e for e, (g, w) in enumerate(zip(got, want)) if not np.array_equal(g, w)]
     assert not bad, (what, bad[:8], got[bad[0]][:16], want[bad[0]][:16])
+
+
+# ------------------------------------------------------------------------------------------ the header's hash, on plain ints
+_M64 = (1 << 64) - 1
+HASH_BOARD_SKIPS = (0, 1, 2, 4, 5)   # t, the draw counter, ep_len, ep_return
+
+
+def _mix64(z):
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def header_hash(words, board=False, clear_finished=True):
+    """include/msnake.h, msnake_hash_states, restated on Python integers: the sum over the selected i of
+    mix64((i + 1) << 32 | uint32(w[i])) mod 2^64, as the int64 the device tensor holds.  board: words 0, 1, 2, 4, 5 are
+    left out and bit 8 of word 7 is cleared (clear_finished=False: the defect of a BOARD hash that keeps it)."""
+    h = 0
+    for i, w in enumerate(words):
+        w = int(w) & 0xFFFFFFFF
+        if board and i in HASH_BOARD_SKIPS:
+            continue
+        if board and i == 7 and clear_finished:
+            w &= ~0x100
+        h = (h + _mix64((i + 1) << 32 | w)) & _M64
+    return h - (1 << 64) if h >> 63 else h

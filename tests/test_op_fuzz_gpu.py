@@ -13,13 +13,21 @@ padded stride falls back to the generic kernel for the call, a migration or a sw
 handle and back.  The adapter asserts at open that the full-record handle of these reports a kernel name that carries
 the board size.  Every call goes through the C entry points on the adapter's one stream.
 
+The entry points added since run in the same sequences: `local`, `rays`, `territory`, `path`, `timed`, `heads`, `fates`,
+`export` and `hash` (readers, each also in a `sweep` directly behind every writer of state: the copy kernel and the swap
+onto what it wrote, an import, a migration, a rollout with its parked draws, a masked reset, the set_state of a body
+over 64 cells), `causes` (the main handle against the twin), `playout` (the handle's blob and stats() unchanged; its end
+words imported into the twin, which is then stepped), `outcomes` (a tracker per handle, compared whole after every
+call) and `import` (msnake_import_states: rows from the twin's device-side export, permuted, the handle's own with
+edited counters, and rows to be refused; every env's status, the full blob and stats() afterwards).
+
 Not fuzzed, host-only and tested elsewhere: msnake_state_blob_info, msnake_kernel_name_for_config (and
-msnake_kernel_name beyond the assertion above).
+msnake_kernel_name beyond the assertion above; msnake_state_words_max is held against the header's formula).
 
 The sequences are the ones tests/test_op_fuzz_host.py runs on the oracle alone, where their coverage is counted and
-asserted, and where each of the nine silent defects OracleAdapter can inject (among them fork_row_shifted,
-fork_touched_unselected, fork_totals_copied, space_off_by_one, cells_head_as_body) is shown to be caught.  Only calls
-that include/msnake.h documents as valid are issued.
+asserted, and where each of the twenty-three silent defects OracleAdapter can inject (among them fork_row_shifted,
+space_off_by_one, import_refused_row_written, import_parked_kept, playout_counts_steps, outcomes_tracker_not_updated)
+is shown to be caught.  Only calls that include/msnake.h documents as valid are issued.
 
 Regression cases (a (configuration, seed, op index) that once exposed a product bug, kept by name): none so far."""
 import numpy as np

@@ -1,8 +1,8 @@
 """tests/op_fuzz.py on the CPU: the driver, its stats models and its guards against further Oracles (the null test), the
 coverage the generated sequences reach (counted on the oracle alone, for every (configuration, seed) the GPU file runs:
 op kinds, class pairs, the copies between the handle and its twin, the compiled-shape step kernels and the hand-overs
-to and from the generic ones), the nine injected silent defects (each must be caught), and the generator's
-determinism."""
+to and from the generic ones, the entry points added since: readers behind every writer of state, imports, playouts, death
+causes, outcomes), the injected silent defects (each must be caught), and the generator's determinism."""
 import ctypes
 import hashlib
 import re
@@ -25,8 +25,28 @@ def _null(cfg, seed):
     return _COV[key]
 
 
+SNAKE_ENV, NEW_WORLD, ADVERSARIAL = 0, 1, 2
+# kind -> (the rule sets whose handles take the call, it needs a handle created with auto_reset off, its reference is a
+# Python search per env and it is left out above 8 192 envs); a kind not listed applies everywhere ([N] migrates over
+# envs_per_block; odd boards script safe_greedy)
+TABLE = {
+    "fates": ((SNAKE_ENV, ADVERSARIAL), False, True),
+    "causes": ((SNAKE_ENV, ADVERSARIAL), True, True),
+    "playout": ((SNAKE_ENV,), False, True),
+    "outcomes": ((SNAKE_ENV, NEW_WORLD, ADVERSARIAL), True, False),
+    "territory": ((SNAKE_ENV, NEW_WORLD, ADVERSARIAL), False, True),
+    "path": ((SNAKE_ENV, NEW_WORLD, ADVERSARIAL), False, True),
+    "timed": ((SNAKE_ENV, NEW_WORLD, ADVERSARIAL), False, True),
+    "heads": ((SNAKE_ENV, NEW_WORLD, ADVERSARIAL), False, True),
+    "sweep": ((SNAKE_ENV, NEW_WORLD, ADVERSARIAL), False, True),
+}
+QUIET_NEW = of.READERS + ("causes", "playout", "outcomes")
+
+
 def _applicable(cfg):
-    return set(of.KINDS)     # every kind applies everywhere ([N] migrates over envs_per_block; odd boards script safe_greedy)
+    big = cfg["num_envs"] > 8192
+    return {k for k in of.KINDS if k not in TABLE or (cfg["rules"] in TABLE[k][0] and not (TABLE[k][1] and cfg["auto_reset"])
+                                                      and not (TABLE[k][2] and big))}
 
 
 @pytest.mark.parametrize("cfg,seed", CASES, ids=IDS)
@@ -34,9 +54,32 @@ def test_null_run_and_coverage_of_every_case(cfg, seed):
     cov, ops = _null(cfg, seed)
     print(cfg["name"], seed, {k: (sorted(v) if isinstance(v, set) else v) for k, v in cov.items()})
     assert len(ops) == cfg["n_ops"]
-    # 1. every op kind at least 3 times (above 8 192 envs: space, cells and fork at least once; swap follows fork)
-    few = ("space", "cells", "fork", "swap") if cfg["num_envs"] > 8192 else ("swap",)
-    assert all(cov["kinds"][k] >= (1 if k in few else 3) for k in _applicable(cfg)), cov["kinds"]
+    # 1. every op kind at least 3 times (above 8 192 envs: space, cells and fork at least once; swap follows fork); of the
+    # kinds added since, every applicable one at least 2 times (above 8 192 envs: once), import at least 3 times, and
+    # none that does not apply
+    app, big = _applicable(cfg), cfg["num_envs"] > 8192
+    assert app == of.applicable(cfg) and all(cov["kinds"][k] == 0 for k in set(of.KINDS) - app), (app, cov["kinds"])
+    few = ("space", "cells", "fork", "swap") if big else ("swap",)
+    newer = QUIET_NEW + ("sweep", "import")       # (import: condition 14)
+    assert all(cov["kinds"][k] >= (1 if k in few else 3) for k in app if k not in newer), cov["kinds"]
+    assert all(cov["kinds"][k] >= (1 if big else 2) for k in app if k in newer and k != "import"), cov["kinds"]
+    # 14. imports: rows that are skipped, installed and refused for at least 3 of the six reasons; an import directly in
+    # front of each of step, rollout and reset_mask
+    # (above 8 192 envs the sequence stays the minimum: imports at all, one of them plain and one with a sparse mask)
+    st = cov["import_status"]
+    assert {of.STATE_SKIPPED, of.STATE_OK} <= st and (big or len(st & {1, 2, 3, 4, 5, 6}) >= 3), st
+    assert cov["kinds"]["import"] >= (1 if big else 3) and (big or all(v >= 1 for v in cov["import_after"].values())), cov
+    # 15. the blocks: death causes one step behind a copy, with the header's guarantee checked against the outcomes
+    # (asserted by the driver); a playout whose end words go into the twin, which is then stepped
+    assert cov["causes_blocks"] == ("causes" in app) and cov["playout_blocks"] == ("playout" in app), cov
+    # 16. every reader directly behind each writer of state: the copy kernel (and the swap onto what it wrote), the
+    # import, a migration, a rollout, a masked reset, the set_state of a body over 64 cells
+    if "sweep" in app:
+        want = {w: 1 for w in of.SWEEP_AFTER if w != "set_long" or of.long_body_allowed(cfg)}
+        assert {w: v for w, v in cov["sweep_after"].items() if w in want} == want, cov["sweep_after"]
+        for op in ops:
+            if op["kind"] == "sweep":
+                assert [o["kind"] for o in op["ops"]] == [k for k in of.READERS if k in app], op
     # 2. at least 2 migrations in each direction ([N] has no short record: envs_per_block only)
     if cfg["rules"] != 1:
         assert cov["migrate_dirs"].get("full>short", 0) >= 2 and cov["migrate_dirs"].get("short>full", 0) >= 2, cov["migrate_dirs"]
@@ -83,6 +126,43 @@ def test_coverage_over_the_seeds_of_a_configuration(cfg):
     # 13. a copy of a body over 64 cells (the overflow ring), where the board has room for one
     if of.long_body_allowed(cfg):
         assert total["fork_src_long"] >= 1, total
+    # 17. imports: all six refusal reasons; onto a finished env without auto reset; of a body over 64 cells
+    more = {k: sum(c[k] for c in covs) for k in ("import_onto_finished", "import_long", "causes_nonzero", "outcomes_armed_died",
+                                                  "outcomes_armed_ended", "outcomes_stale", "export_short", "board_twins")}
+    status = set().union(*[c["import_status"] for c in covs])
+    ends = set().union(*[c["playout_ends"] for c in covs])
+    print(cfg["name"], more, sorted(status), sorted(ends))
+    big = cfg["num_envs"] > 8192           # (the minimal sequence: see condition 14)
+    assert big or {1, 2, 3, 4, 5, 6} <= status, status
+    if not cfg["auto_reset"]:
+        assert more["import_onto_finished"] >= 1, more
+    if of.long_body_allowed(cfg):
+        assert more["import_long"] >= 1, more
+    app = _applicable(cfg)
+    # 18. a death in a causes block; playouts that end in every way the configuration can reach
+    if "causes" in app:
+        assert more["causes_nonzero"] >= 1, more
+    if "playout" in app:
+        assert ends == {0, 1, 2} | ({3} if not cfg["auto_reset"] else set()), ends      # HORIZON, DEAD, CAP, FINISHED
+    # 19. outcomes on an armed tracker with a death and with an ended snake, and on a stale tracker
+    if "outcomes" in app:
+        assert more["outcomes_armed_died"] >= 1 and more["outcomes_armed_ended"] >= 1 and more["outcomes_stale"] >= 1, more
+    # 20. an export where a row does not fit the stride; two envs with equal BOARD and different FULL hashes (it takes two envs)
+    assert big or more["export_short"] >= 1, more
+    if cfg["num_envs"] > 1 and not big:
+        assert more["board_twins"] >= 1, more
+
+
+def test_every_reader_has_run_on_every_kind_of_handle():
+    """Across all cases: each of the newer quiet kinds on the short record, on a handle that steps with the kernels compiled
+    for its shape, and on handles with 1, 2, 4 and 8 envs per workgroup."""
+    seen = set().union(*[_null(c, s)[0]["reader_on"] for c, s in CASES])
+    for kind in QUIET_NEW:
+        mine = {x[1:] for x in seen if x[0] == kind}
+        assert any(rec == "short" for rec, _, _ in mine), (kind, "short record")
+        assert {epb for _, _, epb in mine} >= {1, 2, 4, 8}, (kind, "envs_per_block", mine)
+        if kind not in ("causes", "outcomes"):      # (a handle with auto_reset off never runs the compiled kernels)
+            assert any(spec for _, spec, _ in mine), (kind, "compiled shape")
 
 
 SPEC = ("S10x1", "S19x3_spec", "S19x2_spec")
@@ -129,7 +209,13 @@ def test_the_table_covers_what_it_is_there_for():
 # ---------------------------------------------------------------------------------------------- sensitivity
 FAULTS = [("ctr_lag", "S12x3", 1, 15), ("fruit_moved", "A10x2", 2, 15), ("fin_dropped", "A6x3", 1, 15), ("double_count", "N6x4", 3, 15),
           ("fork_row_shifted", "S19x2_spec", 1, 15), ("fork_touched_unselected", "A6x3", 2, 15), ("fork_totals_copied", "N10x2_x4", 1, 15),
-          ("space_off_by_one", "S12x3", 3, 15), ("cells_head_as_body", "N6x4", 2, 15)]
+          ("space_off_by_one", "S12x3", 3, 15), ("cells_head_as_body", "N6x4", 2, 15),
+          ("local_shifted", "S3x2", 1, 15), ("rays_wrong_channel", "S3x2", 2, 15), ("territory_off_by_one", "S3x2", 1, 15),
+          ("path_off_by_one", "S3x2", 3, 15), ("timed_life_off_by_one", "S3x2", 2, 15), ("heads_owner_tie_as_owner", "S3x2", 1, 15),
+          ("fates_tail_as_body", "A6x3", 1, 15), ("export_row_written_when_short", "S3x2", 3, 15),
+          ("hash_board_keeps_finished", "S3x2", 1, 15), ("import_refused_row_written", "N10x2_x4", 2, 15),
+          ("import_parked_kept", "S3x2", 2, 15), ("causes_by_transposed", "S3x2", 3, 15), ("playout_counts_steps", "S3x2", 2, 15),
+          ("outcomes_tracker_not_updated", "N10x2_x4", 1, 15)]
 
 
 @pytest.mark.parametrize("kind,name,seed,after", FAULTS, ids=[f[0] for f in FAULTS])
@@ -153,7 +239,7 @@ def test_an_injected_silent_defect_is_caught(kind, name, seed, after):
 def test_a_guard_band_and_an_unselected_row_are_watched():
     """The whole-buffer comparison itself: a byte in a guard band, and a row of an env a masked reset did not select."""
     cfg = of.BY_NAME["S3x2"]
-    ops = of.gen_ops(cfg, 1, cfg["n_ops"])
+    ops = of.gen_ops(cfg, 2, cfg["n_ops"])     # (a seed whose sequence holds a masked reset with obs that leaves an env out)
 
     class Scribbler(of.OracleAdapter):
         def __init__(self, where):
@@ -184,4 +270,4 @@ def test_the_generator_is_deterministic_and_pinned():
     assert hashlib.sha256(repr(a).encode()).hexdigest() == PINNED
 
 
-PINNED = "ebe9a9959e16d3a1448f86efa607091cc1896e28df13cdc0ac708ed95ff36d8c"
+PINNED = "efb132d3a0cbad70d2ab41fad2d04e09b7621b5dfc6d2989074cdb3f19855ba4"
