@@ -63,6 +63,8 @@
  *   msnake_fate_actions <- update_snake and is_snake_alive (snake_multiple_test.py:97-164) asked BEFORE the step: what each
  *                      of a snake's five actions leads to for certain, which risks remain, the two action masks that
  *                      follow, and the opponent that plays by them.
+ *   msnake_generate_states: no reference counterpart (a reference env starts from its reset and nowhere else); random legal
+ *                      positions with the body lengths the caller asks for, built on the device -- exploring starts.
  *   msnake_get_stats <- the epinfobuf aggregation in ppo_multi_agent.py:288,331,366-390
  *
  * RNG contract (shared with oracle/ and tests/golden): draw i of global env g is word (i & 3) of
@@ -841,6 +843,52 @@ int msnake_agent_outcomes(msnake_handle h, int32_t flags, int32_t* track_dev, co
 int msnake_playout(msnake_handle h, const int32_t policies[MSNAKE_MAX_SNAKES], int32_t n_steps, const int32_t* first_dev,
                    int32_t first_stride, uint32_t first_mask, int32_t* steps_dev, uint8_t* end_dev, float* ret_dev,
                    int32_t* info_dev, int32_t* words_dev, int32_t words_stride, int32_t* count_dev, void* stream);
+
+/* Random legal positions, built on the device: for the envs a mask selects, non-overlapping snakes of the body lengths the
+ * caller asks for and fruits off the bodies, as canonical words (see msnake_get_state) that msnake_import_states installs
+ * or an archive tensor keeps.  Exploring starts in the sense of ALE, batched: the late game as a place to start from.
+ * snake_env and adversarial handles; new_world is MSNAKE_E_ARG (its alive and in_dead bookkeeping and its init draws are
+ * another contract).  S = n_snakes, F = the handle's n_fruits.
+ * The handle is only read -- its configuration and, per env, the draw counter and word 3: record, rings, parked draws,
+ * draw counter, env_steps and errors stay byte for byte.  The call allocates nothing, never synchronises and can be
+ * captured into a HIP graph.
+ * mask_dev: uint8 [num_envs], non-zero = selected, NULL = every env.  For an unselected env nothing is written: not a byte
+ *   of its row, its count or its got.
+ * len_dev: int32 [num_envs][len_stride], required, len_stride >= S: the requested body length of each snake.  A request
+ *   below 0 counts as 0; snake 0's request is raised to 1; a request of 0 gives an empty (dead) snake.
+ * words_dev int32 [num_envs][stride] and count_dev int32 [num_envs]: the contract of msnake_export_states.  The count of a
+ *   selected env is always written; if it exceeds stride, no word of that row is.
+ * got_dev (may be NULL): int32 [num_envs][S], the lengths actually reached.
+ * The generator's random stream never touches the env's own.  gseed = mix64(seed ^ mix64(salt ^ 0x67656E6572617465)), mix64
+ * the splitmix64 finaliser (see msnake_hash_states), seed the handle's.  Draw j = 0, 1, 2, ... of the env with global id
+ * G = env_id_base + e is word (j & 3) of Philox4x32-10(counter = {j >> 2, G}, key = gseed) -- the RNG contract at the top
+ * of this file under another key -- and randint(n) = (u32 * n) >> 32.  So a shard generates exactly the rows the unsharded
+ * handle generates for the same global ids.
+ * The position of one selected env: start with an empty occupancy; draws are consumed in this order.
+ *   For snake s = 0 .. S-1 with request L > 0:
+ *     Head: let nfree be the number of unoccupied cells.  nfree == 0: the snake gets length 0, no draw.  Otherwise k =
+ *       randint(nfree), one draw, and the head is the k-th unoccupied cell in the order x = c1 * dim + c0 (the respawn's).
+ *       Occupy it.
+ *     Body: it grows behind the head; `end` is the last piece laid.  While len < L: the candidates are the unoccupied
+ *       in-grid neighbours of `end`, in the order of actions 1..4: (+1,0), (0,+1), (-1,0), (0,-1).  None: stop, the snake
+ *       stays shorter and got says so.  With MSNAKE_GEN_COMPACT, keep only the candidates with the fewest unoccupied
+ *       in-grid neighbours of their own, in the same order (Warnsdorff's rule: what makes long bodies reachable).  With n
+ *       candidates left, take candidate n == 1 ? 0 : randint(n) -- a draw only when n > 1 --, occupy it, append it.
+ *   Then for fruit f = 0 .. F-1: count the cells occupied by no body and no earlier fruit.  None: the fruit is (0, 0), no
+ *     draw.  Otherwise it is the k-th such cell by one draw.
+ *   Words: [0] t = 0; [1], [2] the env's current draw counter; [3] the env's current word 3 (adversarial keeps
+ *     spare_fruits across a reset; so does this); [4] 0; [5] 0; [6] F; [7] n_snakes, `finished` clear; the fruits; then per
+ *     snake len, v0, v1, grow_to = max(len, 3), alive = 1, in_dead = 0 and the cells head first, (v0, v1) = head - piece 1,
+ *     (0, 0) for len <= 1.
+ * Every generated row lies in the acceptance domain of msnake_set_state; the heads are inside the grid, so handles on a
+ * step kernel compiled for their shape take them.
+ * Refusals, before any device work, in this order: MSNAKE_E_HANDLE; MSNAKE_E_ARG for new_world, a flag bit other than
+ * MSNAKE_GEN_COMPACT, len_dev NULL or len_stride < S, words_dev with stride <= 0, words_dev, count_dev and got_dev all
+ * NULL; MSNAKE_E_ALIGN for an int32 pointer that is not 4-byte aligned. */
+#define MSNAKE_GEN_COMPACT 1u
+int msnake_generate_states(msnake_handle h, const uint8_t* mask_dev, const int32_t* len_dev, int32_t len_stride,
+                           uint32_t flags, uint64_t salt, int32_t* words_dev, int32_t stride, int32_t* count_dev,
+                           int32_t* got_dev, void* stream);
 
 /* Copy the aggregate statistics to the host.  Blocking: waits for the device (every step issued so
  * far, on any stream) before it sums the per-env totals.  episodes / ep_len_sum / ep_return_sum /

@@ -52,6 +52,7 @@ CAUSE_WALL, CAUSE_SELF, CAUSE_HEAD_ON, CAUSE_BODY = 1, 2, 4, 8  # MSNAKE_CAUSE_*
 HASH_WHAT = {"full": 0, "board": 1}  # MSNAKE_HASH_FULL, MSNAKE_HASH_BOARD: msnake_hash_states
 # MSNAKE_STATE_*: the status bytes of msnake_import_states
 STATE_OK, STATE_TOO_SHORT, STATE_SNAKE_COUNT, STATE_FRUIT_COUNT, STATE_CELL, STATE_LENGTH, STATE_SCALAR, STATE_SKIPPED = 0, 1, 2, 3, 4, 5, 6, 0xFF
+GEN_COMPACT = 1  # MSNAKE_GEN_COMPACT: msnake_generate_states grows bodies by Warnsdorff's rule
 # the words of a tracker row: grow_to, alive, then the totals of the env's current episode
 AGENT_TRACK_WORDS = ("grow_to", "alive", "ep_fruit", "ep_alive_steps", "first_death", "ep_steps", "ep_return", "zero")
 
@@ -137,6 +138,9 @@ PROTOTYPES = {
     # h, mask_dev (uint8 [num_envs] or NULL), words_dev, stride, count_dev (or NULL), status_dev (uint8 [num_envs]), stream
     "msnake_import_states": (_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "msnake_hash_states": (_int, [_vp, _u32, _vp, _vp]),  # h, what (HASH_WHAT), hash_dev (uint64 [num_envs]), stream
+    # h, mask_dev (uint8 [num_envs] or NULL), len_dev (int32 [num_envs][len_stride]), len_stride, flags (GEN_COMPACT or 0), salt,
+    # words_dev (int32 [num_envs][stride] or NULL), stride, count_dev (int32 [num_envs] or NULL), got_dev (int32 [num_envs][n_snakes] or NULL), stream
+    "msnake_generate_states": (_int, [_vp, _vp, _vp, _i32, _u32, ctypes.c_uint64, _vp, _i32, _vp, _vp, _vp]),
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -896,6 +896,31 @@ int msnake_import_states(msnake_handle h, const uint8_t* mask_dev, const int32_t
     return rc;
 }
 
+int msnake_generate_states(msnake_handle h, const uint8_t* mask_dev, const int32_t* len_dev, int32_t len_stride, uint32_t flags,
+                           uint64_t salt, int32_t* words_dev, int32_t stride, int32_t* count_dev, int32_t* got_dev, void* stream) {
+    if (int rc = check(h)) return rc;
+    const int ns = h->p.n_snakes;
+    if (h->cfg.rules == MSNAKE_RULES_NEW_WORLD)
+        return fail(MSNAKE_E_ARG, "msnake_generate_states: new_world keeps alive and in_dead bits per snake and draws its first "
+                                  "positions by another contract; snake_env and adversarial handles only");
+    if (flags & ~MSNAKE_GEN_COMPACT) return fail(MSNAKE_E_ARG, "msnake_generate_states: unknown flag bits 0x%x", flags & ~MSNAKE_GEN_COMPACT);
+    if (!len_dev) return fail(MSNAKE_E_ARG, "msnake_generate_states: len_dev is NULL");
+    if (len_stride < ns) return fail(MSNAKE_E_ARG, "msnake_generate_states: len_stride %d must be >= n_snakes=%d", len_stride, ns);
+    if (words_dev && stride <= 0) return fail(MSNAKE_E_ARG, "msnake_generate_states: words_dev is given but stride is %d", stride);
+    if (!words_dev && !count_dev && !got_dev)
+        return fail(MSNAKE_E_ARG, "msnake_generate_states: nothing to write (words_dev, count_dev and got_dev are NULL)");
+    if (((uintptr_t)len_dev | (uintptr_t)words_dev | (uintptr_t)count_dev | (uintptr_t)got_dev) & 3)
+        return fail(MSNAKE_E_ALIGN, "len_dev, words_dev, count_dev and got_dev must be 4-byte aligned");
+    auto mix64 = [](uint64_t z) {  // the splitmix64 finaliser (msnake_hash_states)
+        z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    };
+    const uint64_t gseed = mix64(h->cfg.seed ^ mix64(salt ^ 0x67656E6572617465ull));  // "generate"
+    DeviceGuard guard(h->cfg.device);
+    return launched(msnake::launch_generate(h->p, mask_dev, len_dev, len_stride, (flags & MSNAKE_GEN_COMPACT) != 0, gseed, words_dev,
+                                            words_dev ? stride : 0, count_dev, got_dev, static_cast<hipStream_t>(stream)));
+}
+
 int msnake_hash_states(msnake_handle h, uint32_t what, uint64_t* hash_dev, void* stream) {
     if (int rc = check(h)) return rc;
     if (what != MSNAKE_HASH_FULL && what != MSNAKE_HASH_BOARD)

@@ -216,6 +216,10 @@ hipError_t launch_state_unpack(const StepParams& p, int rules, int env0, int cou
 hipError_t launch_state_export(const StepParams& p, int rules, int32_t* words, int32_t stride, int32_t* count, hipStream_t stream);
 hipError_t launch_state_import(const StepParams& p, int rules, const uint8_t* mask, const int32_t* words, int32_t stride,
                                const int32_t* count, uint8_t* status, bool refuse_offgrid_head, hipStream_t stream);
+// random legal positions as such rows, for the envs `mask` selects (msnake_generate.inc): len holds the requested body
+// lengths, gseed is the generator's Philox key; words, count and got may be NULL.  Reads the handle's state only
+hipError_t launch_generate(const StepParams& p, const uint8_t* mask, const int32_t* len, int32_t len_stride, bool compact,
+                           uint64_t gseed, int32_t* words, int32_t stride, int32_t* count, int32_t* got, hipStream_t stream);
 // MSNAKE_HASH_FULL / MSNAKE_HASH_BOARD of every env's canonical words (msnake_hash.inc); reads the handle's state only
 hipError_t launch_state_hash(const StepParams& p, int rules, bool board, uint64_t* hash, hipStream_t stream);
 // scripted opponents / safe-move masks from the state in HBM (msnake_scripted.inc); reads the handle's state only

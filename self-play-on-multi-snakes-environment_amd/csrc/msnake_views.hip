@@ -7,7 +7,8 @@
 #include "msnake_device.h"
 
 #include "msnake_state.inc"   // msnake_get_state / msnake_set_state: the canonical state words <-> the device layout
-#include "msnake_hash.inc"    // msnake_hash_states: a 64-bit hash of every env's canonical words
+#include "msnake_generate.inc"  // msnake_generate_states: random legal positions in those words, built on the device
+#include "msnake_hash.inc"   // msnake_hash_states: a 64-bit hash of every env's canonical words
 #include "msnake_copy.inc"   // msnake_copy_envs: env state copied between two handles on the device
 #include "msnake_causes.inc"  // msnake_death_causes: why each snake died and on whose body, from two states one step apart
 #include "msnake_cells.inc"   // msnake_render_cells: the observation as cell codes and the per-snake table

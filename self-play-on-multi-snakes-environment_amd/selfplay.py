@@ -37,6 +37,7 @@ from ._capi import SCRIPTED_PLAYER_NAMES as SCRIPTED_PLAYERS  # SCRIPTED_OPPONEN
 from ._capi import SCRIPTED_NAMES  # SCRIPTED_PLAYERS and wary_greedy: what a ScriptedOpponent may play
 from ._capi import AGENT_ENDED, AGENT_WAS_ALIVE
 from ._capi import CAUSE_BODY, CAUSE_HEAD_ON, CAUSE_SELF, CAUSE_WALL
+from ._capi import RULES
 from .vec_env import check_radius, relative_to_absolute
 
 
@@ -535,17 +536,40 @@ def body_kills(victims):
     return (v & 1) + ((v >> 1) & 1) + ((v >> 2) & 1) + ((v >> 3) & 1)
 
 
+def check_random_starts(random_starts, start_lengths, env=None):
+    """(p, (lo, hi)) of Runner / learn: a probability and a range of body lengths, lo <= hi, as the generator takes them.
+    With p > 0 a new_world `env` is refused here, before the first rollout (scatter_device would refuse it in its first step)."""
+    p = float(random_starts)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"random_starts must be a probability in [0, 1], got {random_starts!r}")
+    try:
+        lo, hi = (int(x) for x in start_lengths)
+    except (TypeError, ValueError):
+        raise ValueError(f"start_lengths must be two ints (lo, hi), got {start_lengths!r}") from None
+    if not 0 <= lo <= hi < 2 ** 31 or (lo, hi) != tuple(start_lengths):
+        raise ValueError(f"start_lengths must be two ints with 0 <= lo <= hi, got {start_lengths!r}")
+    if p > 0.0 and getattr(getattr(env, "cfg", None), "rules", None) == RULES["new_world"]:
+        raise ValueError("random_starts > 0 needs a snake_env or adversarial env: new_world positions cannot be generated")
+    return p, (lo, hi)
+
+
 class Runner:
     """ppo_multi_agent.py:145-216 with everything on the device."""
 
     def __init__(self, env, model, opponents, nsteps, gamma, lam, local_radius=None, oriented=True, rays=False, all_snakes=False,
-                 kill_bonus=0.0):
+                 kill_bonus=0.0, random_starts=0.0, start_lengths=(3, 3)):
         """all_snakes=True: every snake of every env is played by `model` on its own window or rays, and run() returns the
         samples of all of them (agent_targets over env.step_agents_device).  Needs rays=True or local_radius, no
         opponents, and an env created with auto_reset=False.
         kill_bonus != 0 (all_snakes only; snake_env and adversarial): every step also asks why each snake died
         (step_agents_device(causes=True)), and a snake's reward grows by kill_bonus for every snake that ran into its body
-        in that step.  With 0 the rollout is what it is without the argument."""
+        in that step.  With 0 the rollout is what it is without the argument.
+        random_starts = p > 0 (snake_env and adversarial): after each step, every env whose episode just ended starts its
+        next one, with probability p, from a generated position (env.scatter_device) whose per-snake body lengths are
+        uniform in start_lengths = (lo, hi) instead of from the reset; see scatter_done().  With 0 the rollout is what it
+        is without the argument, and torch's generator is not asked."""
+        self.random_starts, self.start_lengths = check_random_starts(random_starts, start_lengths, env)
+        self.start_salt = 0  # the generator's salt: moves with every scatter_device() call
         if rays and local_radius is not None:
             raise ValueError("rays=True and local_radius are mutually exclusive: a run trains on rays or on windows")
         self.all_snakes, self.kill_bonus = bool(all_snakes), float(kill_bonus)
@@ -577,6 +601,25 @@ class Runner:
             self.observe_local()
         self.dones = torch.zeros(env.num_envs, dtype=torch.float32, device=self.obs.device)
         self.tstart = time.time()
+
+    def scatter_done(self, done):
+        """Exploring starts: the envs of `done` (the step's done tensor), each with probability random_starts, are put onto
+        a generated position.  Probability and lengths come from torch's generator on the env's device; nothing is
+        synchronised, so the call is made whether or not an env was picked.  The frame is rendered again behind it; a
+        window / ray runner reads its observation behind this anyway.  (On an all_snakes env the installed states make
+        the next step arm the outcome tracker again: rewards and flags are unaffected, the tracker's episode totals of
+        every env start over.)"""
+        if self.random_starts == 0.0:
+            return
+        env, (lo, hi) = self.env, self.start_lengths
+        pick = done.bool() & (torch.rand(env.num_envs, device=done.device) < self.random_starts)
+        lengths = torch.randint(lo, hi + 1, (env.num_envs, env.n_snakes), dtype=torch.int32, device=done.device)
+        self.start_salt += 1
+        # compact=False: Warnsdorff's rule coils the body round its first piece, the head, and at 40 pieces on 19x19x3 leaves
+        # every snake a safe move in 9 % of the positions against 66 % without it (README); a body that ends short is no loss here
+        env.scatter_device(lengths, mask=pick, salt=self.start_salt, compact=False)
+        if not self.per_snake:
+            self.obs = env.render_device()
 
     def observe_local(self):
         if self.rays:
@@ -640,6 +683,7 @@ class Runner:
                 mb_cause[t], mb_victims[t] = why.cause, why.victims
             else:
                 self.obs, rew, done, info, agents = self.env.step_agents_device(full.to(torch.int32))
+            self.scatter_done(done)
             self.observe_local()
             mb_rew[t], mb_flags[t] = agents.rew, agents.flags  # (copies: the next step overwrites the env's tensors)
             self.dones = done.float()
@@ -680,6 +724,7 @@ class Runner:
             mb_obs[t] = self.learner_obs()
             mb_act[t], mb_val[t], mb_nlp[t], mb_done[t] = a, v, nlp, self.dones
             self.obs, rew, done, info = self.env.step_device(full)
+            self.scatter_done(done)
             if self.per_snake:
                 self.observe_local()
             mb_rew[t] = rew
@@ -702,7 +747,7 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
           cliprange=lambda f: f * 0.1, opponent_save_interval=50, max_saved_opponents=1000, csv_path=None,
           monitor_path=None, seed=0, log_fn=print, amp_dtype=None, json_path=None, tb_dir=None,
           save_dir=None, save_interval=0, load_path=None, resume=False, scripted_opponents=None, local_radius=None,
-          oriented=True, rays=False, all_snakes=False, kill_bonus=0.0):
+          oriented=True, rays=False, all_snakes=False, kill_bonus=0.0, random_starts=0.0, start_lengths=(3, 3)):
     """ppo_multi_agent.py:231-404 (hyper-parameters of test/ppo1_single_test.py:42-47 as defaults).
 
     Checkpoints (ppo_multi_agent.py:112-133, 296-306, 349-364, 392-404), weights only, under `save_dir`
@@ -729,7 +774,12 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
     the log gains agent_samples (the batch size) and sample_fps.
     `kill_bonus` != 0 (all_snakes only): a snake's reward grows by that much for every snake that ran into its body in
     the step (Runner, msnake_death_causes), and every update's log gains deaths_wall, deaths_self, deaths_head_on,
-    deaths_body and kills, counted over its rollout."""
+    deaths_body and kills, counted over its rollout.
+    `random_starts` = p > 0 (snake_env and adversarial): an env whose episode just ended starts the next one, with
+    probability p, from a position generated on the device with per-snake body lengths uniform in `start_lengths` = (lo,
+    hi) (Runner.scatter_done, env.scatter_device): the late game as a place to start from.  Works with the frame, window,
+    ray and all_snakes runners; with 0 the rollout is what it is without the argument."""
+    check_random_starts(random_starts, start_lengths, env)
     if rays and local_radius is not None:
         raise ValueError("rays=True and local_radius are mutually exclusive: a run trains on rays or on windows")
     if all_snakes and not rays and local_radius is None:
@@ -800,7 +850,7 @@ def learn(env, nsteps=64, total_timesteps=int(1e6), ent_coef=0.01, lr=lambda f: 
         if save_dir:  # from the first pool file on there is a state a resume can start from
             save_trainer_state(0)
     runner = Runner(env, model, opponents, nsteps, gamma, lam, local_radius=local_radius, oriented=oriented, rays=rays,
-                    all_snakes=all_snakes, kill_bonus=kill_bonus)
+                    all_snakes=all_snakes, kill_bonus=kill_bonus, random_starts=random_starts, start_lengths=start_lengths)
     nbatch = env.num_envs * nsteps
     nbatch_train = nbatch // nminibatches
     assert nbatch % nminibatches == 0

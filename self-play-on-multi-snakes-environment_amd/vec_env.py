@@ -13,6 +13,7 @@ PyTorch-ROCm policy (device tensors in, device tensors out, asynchronous on the 
 `step()` is the NumPy-returning reference-compatible wrapper around it.
 """
 import collections
+import contextlib
 import ctypes
 import time
 
@@ -388,6 +389,7 @@ class MultiSnakeVecEnv:
         self._causes_fn = self._L.msnake_death_causes
         self._causes_own = self._snapshot = None
         self._fates_fn = self._L.msnake_fate_actions
+        self._scatter_own = None  # scatter_device(): words, count, got and status, allocated on first use
 
     # ------------------------------------------------------------------ device-side API
     def _stream(self):
@@ -1109,6 +1111,107 @@ class MultiSnakeVecEnv:
         if rc < 0:
             _capi.check(rc, "msnake_import_states")
         return status_out
+
+    def _gen_lengths(self, lengths):
+        """lengths -> contiguous int32 [num_envs, >= n_snakes] tensor on this device: an int (every snake), a sequence of
+        n_snakes ints (every env), or such a tensor, used as it is.  An int or a sequence is expanded on the host and copied
+        to the device once; the tensor of the last such request is kept, so repeating it costs no transfer."""
+        torch = self._torch
+        ns = self.n_snakes
+        if isinstance(lengths, torch.Tensor):
+            if (lengths.dtype != torch.int32 or lengths.device != self.device or lengths.dim() != 2 or lengths.shape[0] != self.num_envs or
+                    lengths.shape[1] < ns or not lengths.is_contiguous()):
+                raise ValueError(f"a lengths tensor must be contiguous int32 of shape ({self.num_envs}, >= {ns}) on {self.device}")
+            return lengths
+        if isinstance(lengths, (bool, np.bool_)):
+            raise ValueError("lengths must be an int, a sequence of ints or an int32 tensor, got a bool")
+        if isinstance(lengths, (int, np.integer)):
+            row = [int(lengths)] * ns
+        else:
+            try:
+                row = [int(x) for x in lengths]
+            except (TypeError, ValueError):
+                raise ValueError(f"lengths must be an int, a sequence of {ns} ints or an int32 tensor, got {lengths!r}") from None
+            if len(row) != ns or any(isinstance(x, (bool, np.bool_, float, np.floating)) for x in lengths):
+                raise ValueError(f"lengths must be one int per snake ({ns}), got {lengths!r}")
+        if any(not -2 ** 31 <= x < 2 ** 31 for x in row):
+            raise ValueError(f"lengths must fit an int32, got {lengths!r}")
+        kept = getattr(self, "_gen_len_own", None)
+        if kept is None or kept[0] != row:
+            with self._alloc_ctx():
+                kept = self._gen_len_own = (row, torch.tensor(row, dtype=torch.int32).repeat(self.num_envs, 1).to(self.device))
+        return kept[1]
+
+    def _alloc_ctx(self):
+        """The context the env allocates its own tensors in: its HIP device (nothing on a host stand-in)."""
+        return self._torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
+
+    def _gen_args(self, lengths, mask, salt):
+        """The checks generate_states_device() and scatter_device() share -> (lengths tensor, mask tensor or None)."""
+        if self.cfg.rules == _capi.RULES["new_world"]:
+            raise ValueError("generate_states_device(): new_world is not supported (its alive / in_dead bookkeeping and its "
+                             "init draws are another contract)")
+        if isinstance(salt, (bool, np.bool_)) or not isinstance(salt, (int, np.integer)) or not 0 <= int(salt) < 2 ** 64:
+            raise ValueError(f"salt must be an int in [0, 2^64), got {salt!r}")
+        return self._gen_lengths(lengths), None if mask is None else self._mask(mask)
+
+    def generate_states_device(self, lengths, mask=None, salt=0, compact=True, out=None, count_out=None, got_out=None):
+        """Random legal positions in canonical words, built on the device for the envs `mask` selects
+        (msnake_generate_states: one launch, no host round trip; snake_env and adversarial): non-overlapping snakes of
+        the requested body lengths and fruits off the bodies.  `lengths`: an int, one int per snake, or an int32
+        [num_envs, >= n_snakes] device tensor; below 0 counts as 0, snake 0 gets at least 1, 0 gives a dead snake.  mask as
+        for reset_device(), None = every env; rows, counts and lengths of unselected envs are not written.  salt (0 ..
+        2^64 - 1) picks the generator's stream, which is keyed by the global env id and never touches the env's own;
+        compact=True grows bodies by Warnsdorff's rule, which is what lets long bodies reach their length.  out int32
+        [num_envs, stride] (state_words_max columns when allocated here; a row that does not fit its stride is not
+        written, its count says so), count_out int32 [num_envs], got_out int32 [num_envs, n_snakes]: the lengths reached.
+        Returns (words, count, got), ready for import_states_device(words, mask=mask, count=count).  The env is only
+        read.  With `lengths` (and `mask`) as device tensors and the three outputs given, the call is one launch: nothing
+        is allocated, copied or synchronised, and it can be captured into a graph.  An int or a sequence of lengths, or
+        a mask that is not a uint8 device tensor, is first copied from the host (a pageable transfer, not capturable;
+        the lengths tensor of the last such request is kept and reused)."""
+        torch = self._torch
+        p_len, p_mask = self._gen_args(lengths, mask, salt)
+        with self._alloc_ctx():
+            if out is None:
+                out = torch.zeros((self.num_envs, self.state_words_max), dtype=torch.int32, device=self.device)
+            if count_out is None:
+                count_out = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+            if got_out is None:
+                got_out = torch.zeros((self.num_envs, self.n_snakes), dtype=torch.int32, device=self.device)
+        out, stride = self._state_words(out, "out")
+        if stride < 1:
+            raise ValueError("out must have at least one column")
+        count_out = self._checked(count_out, "count_out", torch.int32, (self.num_envs,))
+        got_out = self._checked(got_out, "got_out", torch.int32, (self.num_envs, self.n_snakes))
+        rc = self._L.msnake_generate_states(self._h, None if p_mask is None else p_mask.data_ptr(), p_len.data_ptr(),
+                                            int(p_len.shape[1]), _capi.GEN_COMPACT if compact else 0, int(salt), out.data_ptr(),
+                                            stride, count_out.data_ptr(), got_out.data_ptr(),
+                                            self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_generate_states")
+        return out, count_out, got_out
+
+    def scatter_device(self, lengths, mask=None, salt=0, compact=True):
+        """Put the envs `mask` selects (None = every env) onto generated positions: generate_states_device() followed by
+        import_states_device(words, mask=mask, count=count) on the same stream, with buffers the env keeps (overwritten
+        by the next call).  Returns (status, got): the status bytes of the import -- _capi.STATE_OK for every selected
+        env, _capi.STATE_SKIPPED elsewhere -- and the lengths reached.  Two launches and nothing else when `lengths` and
+        `mask` are device tensors (see generate_states_device() for what an int, a sequence or a host mask adds)."""
+        torch = self._torch
+        if self._pending is not None:
+            raise RuntimeError("scatter_device() between step_async() and step_wait(): the pending step's results would no "
+                               "longer belong to the state")
+        p_len, p_mask = self._gen_args(lengths, mask, salt)
+        if self._scatter_own is None:
+            with self._alloc_ctx():
+                self._scatter_own = (torch.zeros((self.num_envs, self.state_words_max), dtype=torch.int32, device=self.device),
+                                     torch.zeros(self.num_envs, dtype=torch.int32, device=self.device),
+                                     torch.zeros((self.num_envs, self.n_snakes), dtype=torch.int32, device=self.device),
+                                     torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device))
+        words, count, got, status = self._scatter_own
+        self.generate_states_device(p_len, mask=p_mask, salt=salt, compact=compact, out=words, count_out=count, got_out=got)
+        return self.import_states_device(words, mask=p_mask, count=count, status_out=status), got
 
     def hash_states_device(self, what="full", out=None):
         """A 64-bit hash of every env's canonical words (msnake_hash_states): int64 [num_envs] holding the 64 bits, equal

@@ -42,7 +42,18 @@ def main():
     ap.add_argument("--kill-bonus", type=float, default=0.0, metavar="B",
                     help="with --all-snakes (snake_env, adversarial): add B to a snake's reward for every snake that ran into its "
                          "body in the step, and log the deaths of every update by cause")
+    ap.add_argument("--random-starts", type=float, default=0.0, metavar="P",
+                    help="(snake_env, adversarial) an env whose episode ended starts its next one, with probability P, from a position "
+                         "generated on the device instead of from the reset")
+    ap.add_argument("--start-lengths", type=int, nargs=2, default=(3, 3), metavar=("LO", "HI"),
+                    help="with --random-starts: every snake's body length in a generated position is uniform in [LO, HI]")
     args = ap.parse_args()
+    if not 0.0 <= args.random_starts <= 1.0:
+        ap.error("--random-starts needs a probability in [0, 1]")
+    if not 0 <= args.start_lengths[0] <= args.start_lengths[1]:
+        ap.error("--start-lengths needs 0 <= LO <= HI")
+    if args.random_starts > 0.0 and args.rules == "new_world":
+        ap.error("--random-starts needs snake_env or adversarial rules")
     if args.rays and args.local_radius is not None:
         ap.error("--rays and --local-radius are mutually exclusive")
     if args.no_orient and args.local_radius is None and not args.rays:
@@ -61,7 +72,8 @@ def main():
                    monitor_path=args.monitor, json_path=args.json, tb_dir=args.tensorboard,
                    amp_dtype=torch.bfloat16 if args.bf16 else None, save_dir=args.save, save_interval=args.save_interval,
                    load_path=args.load, resume=args.resume, local_radius=args.local_radius, oriented=not args.no_orient, rays=args.rays,
-                   all_snakes=args.all_snakes, kill_bonus=args.kill_bonus, scripted_opponents=None if args.opponent == "pool" else {s: args.opponent for s in range(1, args.snakes)})
+                   all_snakes=args.all_snakes, kill_bonus=args.kill_bonus, random_starts=args.random_starts,
+                   start_lengths=tuple(args.start_lengths), scripted_opponents=None if args.opponent == "pool" else {s: args.opponent for s in range(1, args.snakes)})
     print(env.stats())
     env.close()
 
