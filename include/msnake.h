@@ -204,7 +204,11 @@ int msnake_step_tape(msnake_handle h, const int32_t* actions_dev, int32_t action
  * its env in registers across the n_steps steps, so there is no per-step launch boundary and no
  * per-step state round trip.  For callers that have the actions of several steps up front
  * (scripted / random opponents, evaluation replays, benchmarks); a policy in the loop needs
- * msnake_step. */
+ * msnake_step.  At obs_scale 1 the persistent kernel keeps a second copy of the observation image in
+ * LDS; on a handle whose two images and occupancy bytes pass 64 KB (with 9 channels from dim 57, with
+ * the 12 of a 4-snake new_world handle from dim 49: msnake_launch_shape_for_config reports it) the call
+ * is served by the per-step launches of msnake_step_tape instead, decided on the host before anything
+ * is launched: the same results and the same env_steps, nothing allocated, still capturable. */
 int msnake_rollout_tape(msnake_handle h, const int32_t* actions_dev, int32_t action_stride, int32_t n_steps,
                         uint8_t* obs_dev, size_t obs_step_stride, float* rew_dev, uint8_t* done_dev,
                         msnake_info* info_dev, size_t scalar_step_stride, void* stream);
@@ -933,6 +937,14 @@ int msnake_set_generic_kernels(int32_t on);
 #define MSNAKE_CALL_PLAIN 2
 int msnake_call_shape_for_config(const msnake_config* cfg, int32_t action_stride, const void* obs_dev, const void* rew_dev,
                                  const void* done_dev, const void* info_dev, int32_t* out);
+/* How the launches of a handle with this configuration are laid out, decided on the host exactly as msnake_create and
+ * msnake_rollout_tape decide it, without a handle and without touching a GPU (tests, tools).  *step_epb: envs (=
+ * wavefronts) per workgroup of msnake_step's launches -- 8 up to 8 192 envs and 4 above, halved until that many LDS
+ * images (padded observation + occupancy bytes) fit 64 KB, and never above envs_per_block.  *tape_epb: the same for
+ * msnake_rollout_tape's persistent launch, whose image is twice as large at obs_scale 1; 0 where not even one env fits,
+ * and the call runs per-step launches.  Either pointer may be NULL.  MSNAKE_E_ARG for a configuration msnake_create
+ * would refuse.  Never a result: every value gives the same outputs. */
+int msnake_launch_shape_for_config(const msnake_config* cfg, int32_t* step_epb, int32_t* tape_epb);
 int64_t msnake_algorithmic_bytes_per_env_step(msnake_handle h);
 
 #ifdef __cplusplus

@@ -141,6 +141,7 @@ PROTOTYPES = {
     # h, mask_dev (uint8 [num_envs] or NULL), len_dev (int32 [num_envs][len_stride]), len_stride, flags (GEN_COMPACT or 0), salt,
     # words_dev (int32 [num_envs][stride] or NULL), stride, count_dev (int32 [num_envs] or NULL), got_dev (int32 [num_envs][n_snakes] or NULL), stream
     "msnake_generate_states": (_int, [_vp, _vp, _vp, _i32, _u32, ctypes.c_uint64, _vp, _i32, _vp, _vp, _vp]),
+    "msnake_launch_shape_for_config": (_int, [_cfg, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),  # cfg, step_epb, tape_epb
 }
 SYMBOLS = list(PROTOTYPES)
 
@@ -200,6 +201,16 @@ def call_shape_for_config(cfg, action_stride, obs, rew, done, info):
     check(load().msnake_call_shape_for_config(ctypes.byref(cfg), action_stride, obs or None, rew or None, done or None,
                                               info or None, ctypes.byref(out)), "msnake_call_shape_for_config")
     return CALL_SHAPE[out.value]
+
+
+def launch_shape_for_config(cfg):
+    """(envs per workgroup of msnake_step's launches, envs per workgroup of msnake_rollout_tape's persistent launch) of a
+    handle created from `cfg` (a MsnakeConfig); the second is 0 where the persistent kernel's two LDS images do not fit
+    and the call runs per-step launches.  Decided by the library's host glue without a GPU."""
+    step, tape = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    check(load().msnake_launch_shape_for_config(ctypes.byref(cfg), ctypes.byref(step), ctypes.byref(tape)),
+          "msnake_launch_shape_for_config")
+    return step.value, tape.value
 
 
 def check(rc, what="msnake call"):

@@ -278,6 +278,21 @@ int pick_spec_dim(const msnake::StepParams& p, int rules) {
     return msnake::spec_dim_of(p, rules);
 }
 
+// envs (= waves) per workgroup of the handle's per-step launches: 8 up to 8 192 envs (512 workgroups at 4 096 envs start
+// 3 % sooner than 1 024: 7.63 -> 7.40 us per launch), 4 above (an 8-wave workgroup needs 8 free wave slots on one CU at
+// once: 29.5 vs 30.9 us at 32 768 envs), fewer where the LDS images need it, and never above cfg->envs_per_block
+int pick_epb(const msnake_config* cfg, const msnake::StepParams& p) {
+    int epb = msnake::shape::epb_that_fits(p.nenv <= 8192 ? MSNAKE_MAX_ENVS_PER_BLOCK : 4, p.lds_per_wave);
+    if (cfg->envs_per_block > 0 && cfg->envs_per_block < epb) epb = cfg->envs_per_block;  // (never above what LDS allows)
+    return epb;
+}
+
+// envs per workgroup of the handle's persistent tape launch (msnake_rollout_tape); 0: the kernel's second image does not
+// fit in LDS beside the first, and the call is served by per-step launches
+int pick_tape_epb(const msnake::StepParams& p, int epb) {
+    return msnake::shape::tape_epb(epb, p.img_bytes, p.dim * p.dim, p.obs_scale);
+}
+
 // what a handle created from *cfg_in right now would step with, without a GPU: the *_for_config calls
 int shape_for_config(const msnake_config* cfg_in, msnake_config* cfg, msnake::StepParams& p) {
     if (int rc = validate_config(cfg_in, cfg)) return rc;
@@ -315,11 +330,7 @@ int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
     p.rest.seed_lo = (uint32_t)cfg->seed;
     p.rest.seed_hi = (uint32_t)(cfg->seed >> 32);
     p.rest.env_id_base = cfg->env_id_base;
-    // envs (= waves) per workgroup: 8 up to 8 192 envs (512 workgroups at 4 096 envs start 3 % sooner
-    // than 1 024: 7.63 -> 7.40 us per launch), 4 above (an 8-wave workgroup needs 8 free wave slots on
-    // one CU at once: 29.5 vs 30.9 us at 32 768 envs)
-    h->epb = p.nenv <= 8192 ? MSNAKE_MAX_ENVS_PER_BLOCK : 4;
-    while (h->epb > 1 && (size_t)h->epb * p.lds_per_wave > 64 * 1024) h->epb >>= 1;
+    h->epb = pick_epb(cfg, p);
 
     const int tmpl_copies = K == 1 ? MSNAKE_TMPL_COPIES : 1;
     const size_t tmpl_bytes = (size_t)p.img_bytes * tmpl_copies;
@@ -347,7 +358,6 @@ int msnake_create(const msnake_config* cfg_in, msnake_handle* out) {
                     memset(&tmpl[(size_t)copy * p.img_bytes + copy + ((size_t)r * W + c) * p.C * K], 255, (size_t)p.C * K);
     if ((e = hipMemcpy(const_cast<uint8_t*>(p.tmpl), tmpl.data(), tmpl_bytes, hipMemcpyHostToDevice)) != hipSuccess)
         return fail(MSNAKE_E_HIP, "uploading the background image failed: %s", hipGetErrorString(e));
-    if (cfg->envs_per_block > 0 && cfg->envs_per_block < h->epb) h->epb = cfg->envs_per_block;  // (never above what LDS allows)
     // obs_store_policy: should the observation stores carry the nt (streaming) hint?  Measured on
     // MI355X with the native 16-byte-per-lane copy-out (tools/kbench.py --store-policy plain/stream), per launch:
     //   <= 32 MiB of observations (<= 8 192 envs at 19x19x3; fits the 8 L2s): 2-3 % faster with nt
@@ -467,6 +477,11 @@ int msnake_rollout_tape(msnake_handle h, const int32_t* actions_dev, int32_t act
     if (int rc = check(h)) return rc;
     if (n_steps < 1) return fail(MSNAKE_E_ARG, "n_steps must be >= 1");
     if (int rc = check_step_args("msnake_rollout_tape", h->p.n_snakes, actions_dev, action_stride, rew_dev, done_dev, info_dev)) return rc;
+    // the persistent kernel keeps a second image in LDS; where that does not fit (decided here, before any launch, with
+    // launch_k's arithmetic) the same steps go out as per-step launches: same results, same env_steps
+    if (pick_tape_epb(h->p, h->epb) == 0)
+        return msnake_step_tape(h, actions_dev, action_stride, n_steps, obs_dev, obs_step_stride, rew_dev, done_dev, info_dev,
+                                scalar_step_stride, stream);
     msnake::StepParams p = h->p;
     fill_call(p, actions_dev, action_stride, obs_dev, rew_dev, done_dev, info_dev);
     p.rest.n_steps = n_steps;
@@ -976,6 +991,17 @@ int msnake_call_shape_for_config(const msnake_config* cfg_in, int32_t action_str
     fill_call(p, nullptr, action_stride, static_cast<uint8_t*>(const_cast<void*>(obs_dev)), static_cast<float*>(const_cast<void*>(rew_dev)),
               static_cast<uint8_t*>(const_cast<void*>(done_dev)), static_cast<msnake_info*>(const_cast<void*>(info_dev)));
     *out = msnake::call_shape_of(p, 0);
+    return MSNAKE_OK;
+}
+
+int msnake_launch_shape_for_config(const msnake_config* cfg_in, int32_t* step_epb, int32_t* tape_epb) {
+    if (!cfg_in) return fail(MSNAKE_E_ARG, "msnake_launch_shape_for_config: NULL argument");
+    msnake_config cfg;
+    msnake::StepParams p;
+    if (int rc = shape_for_config(cfg_in, &cfg, p)) return rc;
+    const int epb = pick_epb(&cfg, p);
+    if (step_epb) *step_epb = epb;
+    if (tape_epb) *tape_epb = pick_tape_epb(p, epb);
     return MSNAKE_OK;
 }
 

@@ -88,6 +88,18 @@ MSNAKE_HD int img_bytes(int S, int K) { return (S * K + (K == 1 ? 15 : 0) + 1023
 MSNAKE_HD int occ_bytes(int n2) { return (n2 + 15) & ~15; }  // respawn occupancy behind the image
 // LDS per env: the image being composed, the occupancy, and (the tape kernel at native size) the pristine background
 MSNAKE_HD int lds_per_wave(int img, int n2, bool ldsbg) { return img + occ_bytes(n2) + (ldsbg ? img : 0); }
+// LDS one workgroup may use, and the envs (= waves) per workgroup that fit it: `epb` halved until epb * per_wave fits,
+// 0 when one env alone does not.  THE arithmetic of msnake_create (per-step launches: lds_per_wave(.., false)), of
+// launch_k (the persistent tape kernel at native size: lds_per_wave(.., true)) and of msnake_rollout_tape, which
+// decides with it before any launch whether the persistent kernel can serve the handle at all.
+constexpr int kLdsBytes = 64 * 1024;
+MSNAKE_HD int epb_that_fits(int epb, int per_wave) {
+    while (epb > 1 && (long long)epb * per_wave > kLdsBytes) epb >>= 1;
+    return per_wave > kLdsBytes ? 0 : epb;
+}
+// envs per workgroup of the persistent tape launch of a handle whose per-step launches run `epb`; 0 = no such launch.
+// A fused frame (K > 1) keeps no background copy: the image alone, as in the per-step kernel.
+MSNAKE_HD int tape_epb(int epb, int img, int n2, int K) { return epb_that_fits(epb, lds_per_wave(img, n2, K == 1)); }
 MSNAKE_HD int fruit_cap(int ns, int n2) { return (ns + ns * (n2 + 2) + 63) & ~63; }  // [A] list: n fruits + every body of one episode
 MSNAKE_HD int fixed_bytes(int ns) { return MSNAKE_HDR_WORDS * 4 + ns * 128; }  // per env: record + the 64-slot ring of every snake
 
@@ -104,6 +116,10 @@ static_assert(obs_bytes(19, 9) == 3969 && img_bytes(3969, 1) == 4096 && ring_cap
 static_assert(lds_per_wave(4096, 361, false) == 4464 && lds_per_wave(4096, 361, true) == 8560 && fruit_cap(3, 361) == 1152 && fruit_cap(2, 361) == 768, "19x19x9");
 static_assert(obs_bytes(10, 9) == 1296 && img_bytes(1296, 1) == 2048 && ring_cap(10 * 10 + 2) == 128 && occ_bytes(100) == 112, "10x10x9");
 static_assert(lds_per_wave(2048, 100, false) == 2160 && fruit_cap(1, 100) == 128 && img_bytes(3969, 4) == 16384, "10x10x9, fused x4");
+// the last boards whose persistent tape launch exists: 56x56 with 9 channels, 48x48 with 12 (new_world, 4 snakes)
+static_assert(tape_epb(8, img_bytes(obs_bytes(56, 9), 1), 56 * 56, 1) == 1 && tape_epb(8, img_bytes(obs_bytes(57, 9), 1), 57 * 57, 1) == 0, "tape limit, 9 channels");
+static_assert(tape_epb(8, img_bytes(obs_bytes(48, 12), 1), 48 * 48, 1) == 1 && tape_epb(8, img_bytes(obs_bytes(49, 12), 1), 49 * 49, 1) == 0, "tape limit, 12 channels");
+static_assert(epb_that_fits(8, lds_per_wave(4096, 361, false)) == 8 && tape_epb(8, 4096, 361, 1) == 4 && tape_epb(2, img_bytes(3969, 4), 361, 4) == 2, "19x19x9");
 static_assert(fixed_bytes(3) == 640 && fixed_bytes(MSNAKE_MAX_SNAKES) == 768, "record + rings");
 constexpr Sections kPinned = sections(2, 3, 16 * 4096, 384, 1152, MSNAKE_RULES_ADVERSARIAL);
 static_assert(kPinned.hdr == 0 && kPinned.body0 == 512 && kPinned.tmpl == 1280 && kPinned.ovf == 66816 && kPinned.fl0 == 71424 &&

@@ -1812,8 +1812,8 @@ static hipError_t launch_k(const StepParams& p, int mode, int epb, hipStream_t s
     size_t lds_wave = (size_t)p.lds_per_wave;  // (derive_shape: shape::lds_per_wave without the background copy)
     if (mode == 3 && K == 1) {  // + the pristine background copy = shape::lds_per_wave(.., true); fewer envs per workgroup if that needs it
         lds_wave += (size_t)p.img_bytes;
-        while (epb > 1 && lds_wave * (size_t)epb > 64 * 1024) epb >>= 1;
-        if (lds_wave > 64 * 1024) return hipErrorInvalidValue;
+        epb = shape::epb_that_fits(epb, (int)lds_wave);
+        if (epb == 0) return hipErrorInvalidValue;  // (a backstop: msnake_rollout_tape serves such a handle with per-step launches)
     }
     const size_t lds = lds_wave * (size_t)epb;
     // fused x4 / x7 frames stream only in the flat 16-byte shape, which needs every frame 16-byte aligned (the dword stores

@@ -533,7 +533,8 @@ def test_respawn_with_and_without_shared_cells(dim):
                                               (30, 3, 3, "snake_env"), (62, 3, 3, "snake_env"), (62, 4, 32, "new_world"),
                                               (45, 4, 0, "new_world"), (7, 1, 9, "new_world")])
 def test_unusual_grid_sizes(dim, ns, nf, rules):
-    """Grid sizes from 2x2 to the 62x62 maximum (LDS image up to 48 KB: one env per workgroup),
+    """Grid sizes from 2x2 to the 62x62 maximum (a 62x62 observation is 36 KB with 9 channels and 48 KB with 12, its
+    padded LDS image 37 / 49 KB plus 3.8 KB of occupancy bytes: one env per workgroup from 56x56 / 48x48 on),
     fruit counts 0..32, against the oracle."""
     n = 37
     _run_vs_oracle(n, dim, ns, nf, rules, 60, seed=31, greedy=0.5)

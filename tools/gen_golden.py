@@ -24,6 +24,7 @@ not installed (TF / mpi4py / cloudpickle imports in baselines/__init__ chain).
 
 Usage: python tools/gen_golden.py            (rewrites tests/golden/*)
        python tools/gen_golden.py long_play  (only tests/golden/long_play.npz)
+       python tools/gen_golden.py big_boards (only tests/golden/big_boards.npz)
 """
 import contextlib
 import hashlib
@@ -789,10 +790,98 @@ def gen_long_play():
     print("\n".join(lines))
 
 
+# ----------------------------------------------------------------------------- the top of the ranges
+def big_board_run(cfg):
+    """One run of tests/big_boards.py RUNS on the reference -> its arrays (see gen_big_boards)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from golden_util import crc_rows, feed_step
+    import big_boards as bb
+    rules, E, ns, T = cfg["rules"], cfg["num_envs"], cfg["n_snakes"], cfg["steps"]
+    vec = VecHarness(rules, cfg["dim"], ns, cfg["n_fruits"], cfg["seed"], E, env_id_base=cfg["env_id_base"],
+                     auto_reset=cfg["auto_reset"])
+    obs = vec.reset()
+    if cfg["kind"] == "late":
+        for env, st in zip(vec.envs, bb.start_states(cfg)):
+            set_state(env, st)
+        obs = np.stack([current_obs(e) for e in vec.envs])
+    states = [canon_state(e) for e in vec.envs]
+    resets = bb.hand_resets(cfg)
+    R = 1 + len(resets)
+    r = dict(actions=np.zeros((T, E, ns), np.int8), reward=np.zeros((T, E), np.float32), done=np.zeros((T, E), np.uint8),
+             num_snakes=np.zeros((T, E), np.int8), ep_return=np.zeros((T, E), np.float32), ep_len=np.zeros((T, E), np.int16),
+             tag=np.zeros(T, np.uint32), state_tag=np.zeros(T, np.uint32), obs_crc=np.zeros((T, E), np.uint32),
+             body_max=np.zeros((T, E), np.int16), n_fruits=np.zeros((T, E), np.int16), reset_tag=np.zeros(R, np.uint32),
+             reset_state_tag=np.zeros(R, np.uint32), reset_crc=np.zeros((R, E), np.uint32))
+    h = hashlib.blake2b(digest_size=32)
+
+    def at_reset(k, obs, states):
+        r["reset_tag"][k] = feed_step(h, obs, states, rules)
+        r["reset_state_tag"][k] = bb.state_tag(states, rules)
+        r["reset_crc"][k] = crc_rows(obs)
+    at_reset(0, obs, states)
+    rs = np.random.default_rng(cfg["seed"] % 9973)
+    for t in range(T):
+        if cfg["kind"] == "random":
+            a = np.array([policy_actions(e, ns, rs, cfg["eps"]) for e in vec.envs], np.int32)
+            if t % 11 == 5:
+                a[rs.integers(0, E), rs.integers(0, ns)] = int(rs.choice([-1, 5, 7]))
+        else:
+            a = bb.late_actions(cfg, states, t)
+        ob, rew, d, n_, er, el = vec.step(a)
+        states = [canon_state(e) for e in vec.envs]
+        r["actions"][t] = a
+        for key, v in zip(("reward", "done", "num_snakes", "ep_return", "ep_len"), (rew, d, n_, er, el)):
+            r[key][t] = v
+        r["tag"][t] = feed_step(h, ob, states, rules)
+        r["state_tag"][t] = bb.state_tag(states, rules)
+        r["obs_crc"][t] = crc_rows(ob)
+        r["body_max"][t] = [max(len(b) for b in st["snakes"]) for st in states]
+        r["n_fruits"][t] = [len(st["fruits"]) for st in states]
+        if t in resets:
+            obs = vec.reset()
+            states = [canon_state(e) for e in vec.envs]
+            at_reset(1 + resets.index(t), obs, states)
+    r["digest"] = np.frombuffer(h.digest(), np.uint8)
+    return r
+
+
+def gen_big_boards():
+    """big_boards.npz: the runs of tests/big_boards.py RUNS -- boards up to 62x62 on both sides of every size at which a
+    step kernel changes its envs per workgroup, up to 32 new_world fruits, and late-game states installed with set_state
+    and played by scripted policies from the REFERENCE's canonical state.  Random runs follow gen_random_configs' recipe.
+    Per run <name>, per step and env what long_play.npz holds (_actions, _reward, _done, _num_snakes, _ep_return,
+    _ep_len, _body_max, _n_fruits; _tag per step and _digest: the running BLAKE2b-256 of golden_util.feed_step) and
+    _obs_crc (CRC32 of every env's observation) and _state_tag (big_boards.state_tag: the states alone) per step; the
+    same three for the first reset (late-game runs: the installed state) and every reset by hand: _reset_tag,
+    _reset_state_tag [R], _reset_crc [R, E]."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import big_boards as bb
+    out, covs = {}, {}
+    for name, cfg in bb.RUNS.items():
+        r = big_board_run(cfg)
+        E, T = cfg["num_envs"], cfg["steps"]
+        covs[name] = bb.coverage(cfg, r["reward"], r["done"], r["body_max"], r["n_fruits"])
+        print(f"  {name}: {E} envs x {T} steps, {covs[name]}", flush=True)
+        bb.check_coverage(cfg, covs[name])
+        out.update({f"{name}_{k}": v for k, v in r.items()})
+    bb.check_table_coverage(covs)
+    out["meta"] = np.array(json.dumps(dict(runs=bb.RUNS)))
+    path = os.path.join(OUT, "big_boards.npz")
+    np.savez_compressed(path, **out)
+    limit = os.path.getsize(os.path.join(OUT, "tape_S_19x19_3.npz"))
+    size = os.path.getsize(path)
+    print(f"big_boards.npz: {len(bb.RUNS)} runs, {size} bytes (limit {limit})")
+    if size > limit:
+        os.remove(path)
+        raise SystemExit("big_boards.npz is larger than the largest committed fixture")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     if sys.argv[1:] == ["long_play"]:
         return gen_long_play()
+    if sys.argv[1:] == ["big_boards"]:
+        return gen_big_boards()
     gen_philox_kat()
     gen_edges()
     S, N, A = RULES_SNAKE_ENV, RULES_NEW_WORLD, RULES_ADVERSARIAL
@@ -818,6 +907,7 @@ def main():
     gen_tape("tape_A_19x19_1", A, 19, 1, 1, seed=14, num_envs=8, steps=64)
     gen_random_configs()
     gen_long_play()
+    gen_big_boards()
 
 
 if __name__ == "__main__":
