@@ -65,6 +65,8 @@
  *                      follow, and the opponent that plays by them.
  *   msnake_generate_states: no reference counterpart (a reference env starts from its reset and nowhere else); random legal
  *                      positions with the body lengths the caller asks for, built on the device -- exploring starts.
+ *   msnake_explore_actions, msnake_playout_explore: no reference counterpart (its opponents are networks, which sample);
+ *                      epsilon-random moves of scripted players from a documented stream, standalone and inside the playout.
  *   msnake_get_stats <- the epinfobuf aggregation in ppo_multi_agent.py:288,331,366-390
  *
  * RNG contract (shared with oracle/ and tests/golden): draw i of global env g is word (i & 3) of
@@ -847,6 +849,58 @@ int msnake_agent_outcomes(msnake_handle h, int32_t flags, int32_t* track_dev, co
 int msnake_playout(msnake_handle h, const int32_t policies[MSNAKE_MAX_SNAKES], int32_t n_steps, const int32_t* first_dev,
                    int32_t first_stride, uint32_t first_mask, int32_t* steps_dev, uint8_t* end_dev, float* ret_dev,
                    int32_t* info_dev, int32_t* words_dev, int32_t words_stride, int32_t* count_dev, void* stream);
+
+/* Exploring play: with a probability per snake, a uniformly random legal move in place of the policy's own, drawn from a
+ * documented stream of its own -- inside the one-launch playout (msnake_playout_explore: Monte-Carlo rollouts without
+ * leaving the device) and as the standalone call that writes the very word such a playout plays (msnake_explore_actions:
+ * what a search assumes about an opponent can be played against it, captured in a graph, with no host RNG).
+ * The exploration rule.  S = n_snakes.  policies[s] is in 0..3 as msnake_playout takes them; eps_q16[s] is in [0, 65536]
+ * and is snake s's exploration probability in units of 1 / 65536; salt is any uint64.  For an env with global id
+ * G = env_id_base + e whose canonical state has t = word 0 and ctr = words 1, 2 as one uint64:
+ *   Base action: b_s is what policies[s] writes for that state: MSNAKE_POLICY_NONE the constant 0, MSNAKE_POLICY_SAFE_GREEDY
+ *     and MSNAKE_POLICY_HAMILTONIAN what msnake_scripted_actions writes, MSNAKE_POLICY_WARY_GREEDY what msnake_fate_actions
+ *     writes.
+ *   Candidate set C_s, moves in 1..4: under MSNAKE_POLICY_WARY_GREEDY wary_greedy's own candidates -- the a in 1..4 with bit a
+ *     of mask[1] set, and if there are none those with bit a of mask[0] set (msnake_fate_actions' mask_dev); under every
+ *     other policy the open moves, bits 1..4 of msnake_scripted_actions' safe_dev byte.  An empty body gives an empty set.
+ *     n = |C_s|.
+ *   The stream never touches the env's own.  xseed = mix64(seed ^ mix64(salt ^ 0x6578706C6F726521)) ("explore!"), mix64 the
+ *     splitmix64 finaliser (see msnake_hash_states), seed the handle's.  k64 = mix64(xseed ^ ctr).  Draw j is word (j & 3)
+ *     of Philox4x32-10(counter = {lo(j >> 2), hi(j >> 2), lo(G), hi(G)}, key = {lo(k64), hi(k64)}) -- the RNG contract at the
+ *     top of this file under another key.  For snake s: u0 = draw 8 t + 2 s and u1 = draw 8 t + 2 s + 1, with t zero-extended
+ *     from uint32.
+ *   The action: if eps_q16[s] > 0, (u0 >> 16) < eps_q16[s] and n > 0, the snake explores: its action is the
+ *     ((u1 * n) >> 32)-th member of C_s in the order 1, 2, 3, 4.  Otherwise it is b_s.  eps_q16 = 65536 always explores when
+ *     n > 0 (a uniform random legal mover); eps_q16 = 0 never draws.
+ * The draw depends on (seed, salt, G, t, ctr, s) only: it is stateless, a shard draws what the unsharded handle draws for
+ * the same global ids, and nothing in the arguments has to change between the replays of a graph.  It does not repeat over
+ * an env's life: ctr only grows, and t grows between two changes of ctr.
+ *
+ * msnake_explore_actions: entry s of every row of actions_dev (int32 [num_envs][action_stride]) is written for each s with
+ * bit s of snake_mask set, all other entries are left untouched.  explored_dev (may be NULL): uint8 [num_envs][S], written
+ * for every snake whatever snake_mask is: 1 iff that snake's action was drawn.  All three rule sets for policies 0..2;
+ * MSNAKE_POLICY_WARY_GREEDY needs snake_env or adversarial, as msnake_fate_actions does.  Like its siblings the call only
+ * reads the handle's state, draws none of the env's random numbers (the Philox counter stays), allocates nothing, never
+ * synchronises and adds nothing to env_steps; asynchronous on `stream`, and it can be captured into a HIP graph in front of
+ * the step.  Refusals, before any device work, in this order: MSNAKE_E_HANDLE; MSNAKE_E_ARG for policies NULL or
+ * policies[s] outside 0..3 for an s < S; for MSNAKE_POLICY_WARY_GREEDY on a new_world handle; for MSNAKE_POLICY_HAMILTONIAN
+ * on an odd board; for eps_q16 NULL or an entry > 65536 for an s < S; for snake_mask 0 or with a bit >= S; for actions_dev
+ * NULL or action_stride < S; MSNAKE_E_ALIGN for actions_dev not 4-byte aligned.
+ *
+ * msnake_playout_explore: the contract of msnake_playout word for word, with one change: the action of snake s in step k is
+ * the rule above applied to s_(k-1), with that state's t and ctr -- the draw counter moves with the respawns inside the
+ * playout, as it does there.  A forced first action wins over exploring; info[..][3] reports the word played, explored or
+ * not.  Refusals: msnake_playout's list, with "eps_q16 NULL or an entry > 65536 for an s < S" directly behind "policies NULL
+ * or policies[s] outside 0..3" and in front of the odd board.  msnake_playout(h, ...) is msnake_playout_explore with every
+ * eps 0, for any salt. */
+int msnake_explore_actions(msnake_handle h, const int32_t policies[MSNAKE_MAX_SNAKES],
+                           const uint32_t eps_q16[MSNAKE_MAX_SNAKES], uint64_t salt, uint32_t snake_mask,
+                           int32_t* actions_dev, int32_t action_stride, uint8_t* explored_dev, void* stream);
+int msnake_playout_explore(msnake_handle h, const int32_t policies[MSNAKE_MAX_SNAKES],
+                           const uint32_t eps_q16[MSNAKE_MAX_SNAKES], uint64_t salt, int32_t n_steps,
+                           const int32_t* first_dev, int32_t first_stride, uint32_t first_mask, int32_t* steps_dev,
+                           uint8_t* end_dev, float* ret_dev, int32_t* info_dev, int32_t* words_dev, int32_t words_stride,
+                           int32_t* count_dev, void* stream);
 
 /* Random legal positions, built on the device: for the envs a mask selects, non-overlapping snakes of the body lengths the
  * caller asks for and fruits off the bodies, as canonical words (see msnake_get_state) that msnake_import_states installs

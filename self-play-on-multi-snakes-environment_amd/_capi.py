@@ -39,6 +39,7 @@ WARY_POLICY = "wary_greedy"  # likewise (msnake_fate_actions)
 SCRIPTED_NAMES = SCRIPTED_PLAYER_NAMES + (WARY_POLICY,)  # ... and the one that plays by the fates of its moves
 # MSNAKE_POLICY_* as msnake_playout takes them: the scripted ids and wary_greedy (msnake_scripted_actions keeps refusing 3)
 PLAYOUT_POLICY = {None: 0, "safe_greedy": 1, "hamiltonian": 2, "wary_greedy": 3}
+EXPLORE_ONE = 65536  # eps_q16 of probability 1: msnake_explore_actions and msnake_playout_explore take round(p * 65536)
 PLAYOUT_MAX_STEPS = 4096  # MSNAKE_PLAYOUT_MAX_STEPS
 PLAYOUT_HORIZON, PLAYOUT_DEAD, PLAYOUT_CAP, PLAYOUT_FINISHED = 0, 1, 2, 3  # MSNAKE_PLAYOUT_*: msnake_playout's end codes
 MAX_SNAKES = 4  # MSNAKE_MAX_SNAKES
@@ -132,6 +133,12 @@ PROTOTYPES = {
     # first_mask, steps_dev (int32 [num_envs]), end_dev (uint8 [num_envs]), ret_dev (float32 [num_envs][n_snakes]),
     # info_dev (int32 [num_envs][n_snakes][4]), words_dev (int32 [num_envs][words_stride]), words_stride, count_dev, stream
     "msnake_playout": (_int, [_vp, ctypes.POINTER(_i32), _i32, _vp, _i32, _u32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    # h, policies (int32 [MSNAKE_MAX_SNAKES], host), eps_q16 (uint32 [MSNAKE_MAX_SNAKES], host), salt, snake_mask, actions_dev,
+    # action_stride, explored_dev (uint8 [num_envs][n_snakes] or NULL), stream
+    "msnake_explore_actions": (_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_u32), ctypes.c_uint64, _u32, _vp, _i32, _vp, _vp]),
+    # h, policies, eps_q16, salt, then msnake_playout's arguments from n_steps on
+    "msnake_playout_explore": (_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_u32), ctypes.c_uint64, _i32, _vp, _i32, _u32, _vp, _vp,
+                                      _vp, _vp, _vp, _i32, _vp, _vp]),
     "msnake_state_words_max": (_i32, [_vp]),  # h
     # h, words_dev (int32 [num_envs][stride] or NULL), stride, count_dev (int32 [num_envs] or NULL), stream
     "msnake_export_states": (_int, [_vp, _vp, _i32, _vp, _vp]),
@@ -148,8 +155,10 @@ SYMBOLS = list(PROTOTYPES)
 _lib = None
 
 
-def load():
-    """Load libmsnake.so, declare prototypes. Raises RuntimeError if it was never built."""
+def load(optional=()):
+    """Load libmsnake.so, declare prototypes. Raises RuntimeError if it was never built.  `optional`: entry points that the
+    library named by MSNAKE_LIB may lack (an older build in a same-box A/B run, tools/playout_cost.py); they are left unbound,
+    and calling one fails.  Every other symbol must be there."""
     global _lib
     if _lib is not None:
         return _lib
@@ -167,6 +176,8 @@ def load():
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in PROTOTYPES.items():
+        if name in optional and not hasattr(L, name):
+            continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

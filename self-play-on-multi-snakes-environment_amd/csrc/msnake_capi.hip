@@ -587,37 +587,106 @@ int msnake_fate_actions(msnake_handle h, uint32_t snake_mask, int32_t* actions_d
                                          static_cast<hipStream_t>(stream)));
 }
 
-int msnake_playout(msnake_handle h, const int32_t policies[MSNAKE_MAX_SNAKES], int32_t n_steps, const int32_t* first_dev,
-                   int32_t first_stride, uint32_t first_mask, int32_t* steps_dev, uint8_t* end_dev, float* ret_dev, int32_t* info_dev,
-                   int32_t* words_dev, int32_t words_stride, int32_t* count_dev, void* stream) {
+namespace {
+
+uint64_t mix64(uint64_t z) {  // the splitmix64 finaliser (msnake_hash_states)
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// the seed of the exploration stream (msnake_explore_actions, msnake_playout_explore)
+uint64_t explore_seed(uint64_t seed, uint64_t salt) { return mix64(seed ^ mix64(salt ^ 0x6578706C6F726521ull)); }  // "explore!"
+
+// policies[s] for s < ns: one of MSNAKE_POLICY_* as msnake_playout takes them
+int check_playout_policies(const char* fn, const int32_t* policies, int ns) {
+    if (!policies) return fail(MSNAKE_E_ARG, "%s: policies is NULL", fn);
+    for (int s = 0; s < ns; ++s)
+        if (policies[s] < MSNAKE_POLICY_NONE || policies[s] > MSNAKE_POLICY_WARY_GREEDY)
+            return fail(MSNAKE_E_ARG, "%s: policies[%d] = %d is not one of MSNAKE_POLICY_*", fn, s, policies[s]);
+    return MSNAKE_OK;
+}
+
+int check_hamiltonian_board(const char* fn, const int32_t* policies, int ns, int dim) {
+    for (int s = 0; s < ns; ++s)
+        if (policies[s] == MSNAKE_POLICY_HAMILTONIAN && (dim & 1))
+            return fail(MSNAKE_E_ARG, "%s: policy HAMILTONIAN needs an even dim (the cycle), got dim %d", fn, dim);
+    return MSNAKE_OK;
+}
+
+// eps_q16[s] for s < ns: an exploration probability in units of 1 / 65536
+int check_eps(const char* fn, const uint32_t* eps_q16, int ns) {
+    if (!eps_q16) return fail(MSNAKE_E_ARG, "%s: eps_q16 is NULL", fn);
+    for (int s = 0; s < ns; ++s)
+        if (eps_q16[s] > 65536u) return fail(MSNAKE_E_ARG, "%s: eps_q16[%d] = %u is above 65536", fn, s, eps_q16[s]);
+    return MSNAKE_OK;
+}
+
+// msnake_playout (eps_q16 NULL, not looked at) and msnake_playout_explore (explores = true)
+int playout(const char* fn, msnake_handle h, const int32_t* policies, bool explores, const uint32_t* eps_q16, uint64_t salt, int32_t n_steps,
+            const int32_t* first_dev, int32_t first_stride, uint32_t first_mask, int32_t* steps_dev, uint8_t* end_dev, float* ret_dev,
+            int32_t* info_dev, int32_t* words_dev, int32_t words_stride, int32_t* count_dev, void* stream) {
     if (int rc = check(h)) return rc;
     const int ns = h->p.n_snakes;
     if (h->cfg.rules != MSNAKE_RULES_SNAKE_ENV)
-        return fail(MSNAKE_E_ARG, "msnake_playout: snake_env handles only (rules %d): new_world judges its snakes one after the other, "
-                                  "and the adversarial fruit list can grow to fcap entries", h->cfg.rules);
+        return fail(MSNAKE_E_ARG, "%s: snake_env handles only (rules %d): new_world judges its snakes one after the other, "
+                                  "and the adversarial fruit list can grow to fcap entries", fn, h->cfg.rules);
     if (n_steps < 1 || n_steps > MSNAKE_PLAYOUT_MAX_STEPS)
-        return fail(MSNAKE_E_ARG, "msnake_playout: n_steps %d must lie in [1, %d]", n_steps, MSNAKE_PLAYOUT_MAX_STEPS);
-    if (!policies) return fail(MSNAKE_E_ARG, "msnake_playout: policies is NULL");
-    for (int s = 0; s < ns; ++s)
-        if (policies[s] < MSNAKE_POLICY_NONE || policies[s] > MSNAKE_POLICY_WARY_GREEDY)
-            return fail(MSNAKE_E_ARG, "msnake_playout: policies[%d] = %d is not one of MSNAKE_POLICY_*", s, policies[s]);
-    for (int s = 0; s < ns; ++s)
-        if (policies[s] == MSNAKE_POLICY_HAMILTONIAN && (h->p.dim & 1))
-            return fail(MSNAKE_E_ARG, "msnake_playout: policy HAMILTONIAN needs an even dim (the cycle), got dim %d", h->p.dim);
-    if (first_mask >> ns) return fail(MSNAKE_E_ARG, "msnake_playout: first_mask 0x%x has a bit >= n_snakes=%d", first_mask, ns);
-    if (first_mask && !first_dev) return fail(MSNAKE_E_ARG, "msnake_playout: first_mask is 0x%x but first_dev is NULL", first_mask);
+        return fail(MSNAKE_E_ARG, "%s: n_steps %d must lie in [1, %d]", fn, n_steps, MSNAKE_PLAYOUT_MAX_STEPS);
+    if (int rc = check_playout_policies(fn, policies, ns)) return rc;
+    if (explores)
+        if (int rc = check_eps(fn, eps_q16, ns)) return rc;
+    if (int rc = check_hamiltonian_board(fn, policies, ns, h->p.dim)) return rc;
+    if (first_mask >> ns) return fail(MSNAKE_E_ARG, "%s: first_mask 0x%x has a bit >= n_snakes=%d", fn, first_mask, ns);
+    if (first_mask && !first_dev) return fail(MSNAKE_E_ARG, "%s: first_mask is 0x%x but first_dev is NULL", fn, first_mask);
     if (first_mask && first_stride < ns)
-        return fail(MSNAKE_E_ARG, "msnake_playout: first_stride %d must be >= n_snakes=%d", first_stride, ns);
-    if (words_dev && words_stride <= 0) return fail(MSNAKE_E_ARG, "msnake_playout: words_dev is given but words_stride is %d", words_stride);
+        return fail(MSNAKE_E_ARG, "%s: first_stride %d must be >= n_snakes=%d", fn, first_stride, ns);
+    if (words_dev && words_stride <= 0) return fail(MSNAKE_E_ARG, "%s: words_dev is given but words_stride is %d", fn, words_stride);
     if (!steps_dev && !end_dev && !ret_dev && !info_dev && !words_dev && !count_dev)
-        return fail(MSNAKE_E_ARG, "msnake_playout: nothing to write (steps_dev, end_dev, ret_dev, info_dev, words_dev and count_dev are NULL)");
+        return fail(MSNAKE_E_ARG, "%s: nothing to write (steps_dev, end_dev, ret_dev, info_dev, words_dev and count_dev are NULL)", fn);
     if (((uintptr_t)first_dev & 3) || ((uintptr_t)steps_dev & 3) || ((uintptr_t)ret_dev & 3) || ((uintptr_t)info_dev & 3) ||
         ((uintptr_t)words_dev & 3) || ((uintptr_t)count_dev & 3))
         return fail(MSNAKE_E_ALIGN, "first_dev, steps_dev, ret_dev, info_dev, words_dev and count_dev must be 4-byte aligned");
     DeviceGuard guard(h->cfg.device);
-    return launched(msnake::launch_playout(h->p, h->cfg.rules, policies, n_steps, first_mask ? first_dev : nullptr, first_stride, first_mask,
-                                           steps_dev, end_dev, ret_dev, info_dev, words_dev, words_stride, count_dev,
-                                           static_cast<hipStream_t>(stream)));
+    return launched(msnake::launch_playout(h->p, h->cfg.rules, policies, explores ? eps_q16 : nullptr, explore_seed(h->cfg.seed, salt), n_steps,
+                                           first_mask ? first_dev : nullptr, first_stride, first_mask, steps_dev, end_dev, ret_dev, info_dev,
+                                           words_dev, words_stride, count_dev, static_cast<hipStream_t>(stream)));
+}
+
+}  // namespace
+
+int msnake_playout(msnake_handle h, const int32_t policies[MSNAKE_MAX_SNAKES], int32_t n_steps, const int32_t* first_dev,
+                   int32_t first_stride, uint32_t first_mask, int32_t* steps_dev, uint8_t* end_dev, float* ret_dev, int32_t* info_dev,
+                   int32_t* words_dev, int32_t words_stride, int32_t* count_dev, void* stream) {
+    return playout("msnake_playout", h, policies, false, nullptr, 0, n_steps, first_dev, first_stride, first_mask, steps_dev, end_dev, ret_dev,
+                   info_dev, words_dev, words_stride, count_dev, stream);
+}
+
+int msnake_playout_explore(msnake_handle h, const int32_t policies[MSNAKE_MAX_SNAKES], const uint32_t eps_q16[MSNAKE_MAX_SNAKES],
+                           uint64_t salt, int32_t n_steps, const int32_t* first_dev, int32_t first_stride, uint32_t first_mask,
+                           int32_t* steps_dev, uint8_t* end_dev, float* ret_dev, int32_t* info_dev, int32_t* words_dev,
+                           int32_t words_stride, int32_t* count_dev, void* stream) {
+    return playout("msnake_playout_explore", h, policies, true, eps_q16, salt, n_steps, first_dev, first_stride, first_mask, steps_dev, end_dev,
+                   ret_dev, info_dev, words_dev, words_stride, count_dev, stream);
+}
+
+int msnake_explore_actions(msnake_handle h, const int32_t policies[MSNAKE_MAX_SNAKES], const uint32_t eps_q16[MSNAKE_MAX_SNAKES],
+                           uint64_t salt, uint32_t snake_mask, int32_t* actions_dev, int32_t action_stride, uint8_t* explored_dev,
+                           void* stream) {
+    const char* fn = "msnake_explore_actions";
+    if (int rc = check(h)) return rc;
+    const int ns = h->p.n_snakes;
+    if (int rc = check_playout_policies(fn, policies, ns)) return rc;
+    for (int s = 0; s < ns; ++s)
+        if (policies[s] == MSNAKE_POLICY_WARY_GREEDY && h->cfg.rules == MSNAKE_RULES_NEW_WORLD)
+            return fail(MSNAKE_E_ARG, "%s: policy WARY_GREEDY needs snake_env or adversarial rules: new_world judges its snakes one after "
+                                      "the other, so the fate of a move does not follow from the state", fn);
+    if (int rc = check_hamiltonian_board(fn, policies, ns, h->p.dim)) return rc;
+    if (int rc = check_eps(fn, eps_q16, ns)) return rc;
+    if (!snake_mask) return fail(MSNAKE_E_ARG, "%s: snake_mask is 0 (no action to write)", fn);
+    if (int rc = check_action_writer(fn, ns, true, snake_mask, actions_dev, action_stride)) return rc;
+    DeviceGuard guard(h->cfg.device);
+    return launched(msnake::launch_explore(h->p, h->cfg.rules, policies, eps_q16, explore_seed(h->cfg.seed, salt), snake_mask, actions_dev,
+                                           action_stride, explored_dev, static_cast<hipStream_t>(stream)));
 }
 
 int msnake_head_fields(msnake_handle h, uint32_t snake_mask, uint16_t* dist_dev, uint8_t* owner_dev, uint16_t* counts_dev, void* stream) {
@@ -926,10 +995,6 @@ int msnake_generate_states(msnake_handle h, const uint8_t* mask_dev, const int32
         return fail(MSNAKE_E_ARG, "msnake_generate_states: nothing to write (words_dev, count_dev and got_dev are NULL)");
     if (((uintptr_t)len_dev | (uintptr_t)words_dev | (uintptr_t)count_dev | (uintptr_t)got_dev) & 3)
         return fail(MSNAKE_E_ALIGN, "len_dev, words_dev, count_dev and got_dev must be 4-byte aligned");
-    auto mix64 = [](uint64_t z) {  // the splitmix64 finaliser (msnake_hash_states)
-        z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    };
     const uint64_t gseed = mix64(h->cfg.seed ^ mix64(salt ^ 0x67656E6572617465ull));  // "generate"
     DeviceGuard guard(h->cfg.device);
     return launched(msnake::launch_generate(h->p, mask_dev, len_dev, len_stride, (flags & MSNAKE_GEN_COMPACT) != 0, gseed, words_dev,

@@ -262,10 +262,16 @@ hipError_t launch_timed(const StepParams& p, int rules, uint32_t snake_mask, int
 hipError_t launch_fates(const StepParams& p, int rules, uint32_t snake_mask, int32_t* actions, int32_t action_stride, uint8_t* fate,
                         uint8_t* by, uint8_t* eat, uint8_t* mask, hipStream_t stream);
 // n_steps of [policies -> step] per env in one launch, the env held in LDS (msnake_playout.inc); snake_env only, any of the
-// six outputs may be NULL.  Reads the handle's state only
-hipError_t launch_playout(const StepParams& p, int rules, const int32_t* policies, int32_t n_steps, const int32_t* first,
-                          int32_t first_stride, uint32_t first_mask, int32_t* steps, uint8_t* end, float* ret, int32_t* info,
-                          int32_t* words, int32_t words_stride, int32_t* count, hipStream_t stream);
+// six outputs may be NULL.  eps NULL: nobody explores (msnake_playout); else eps_q16 per snake and the exploration stream's
+// seed xseed (msnake_playout_explore).  Reads the handle's state only
+hipError_t launch_playout(const StepParams& p, int rules, const int32_t* policies, const uint32_t* eps, uint64_t xseed,
+                          int32_t n_steps, const int32_t* first, int32_t first_stride, uint32_t first_mask, int32_t* steps,
+                          uint8_t* end, float* ret, int32_t* info, int32_t* words, int32_t words_stride, int32_t* count,
+                          hipStream_t stream);
+// the action every snake's policy writes, or with probability eps_q16 / 65536 a uniform draw from its candidate set, under the
+// exploration stream's seed xseed (msnake_explore.inc); explored may be NULL.  Reads the handle's state only
+hipError_t launch_explore(const StepParams& p, int rules, const int32_t* policies, const uint32_t* eps, uint64_t xseed,
+                          uint32_t snake_mask, int32_t* actions, int32_t action_stride, uint8_t* explored, hipStream_t stream);
 // env state of `src` into `dst`, one wave per destination env (msnake_copy.inc); src_index NULL = the identity.  Reads `src` only
 hipError_t launch_copy_envs(const StepParams& dst, const StepParams& src, int rules, const int32_t* src_index, hipStream_t stream);
 // why each snake died in the step between `before` and `after`, and on whose body (msnake_causes.inc); any of the four

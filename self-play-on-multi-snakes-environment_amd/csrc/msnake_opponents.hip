@@ -22,4 +22,5 @@
 #include "msnake_local.inc"      // msnake_render_local: head-centred cell-code windows per snake
 #include "msnake_rays.inc"       // msnake_render_rays: eight-direction ray observations per snake
 #include "msnake_fates.inc"      // msnake_fate_actions: the fate of every move, the masks and wary_greedy
+#include "msnake_explore.inc"    // msnake_explore_actions: epsilon-random moves from a stream of their own, and the draw itself
 #include "msnake_playout.inc"    // msnake_playout: scripted playouts of every env in one launch, the env held in LDS

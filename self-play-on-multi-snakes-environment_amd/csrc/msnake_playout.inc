@@ -1,6 +1,7 @@
 // msnake_playout.inc -- scripted playouts of every env in ONE launch (msnake_playout): up to MSNAKE_PLAYOUT_MAX_STEPS steps
 // of [policy of every snake -> step] per env, the env held in LDS from the first step to the last.  Included last by
-// msnake_opponents.hip: it uses msnake_scripted.inc's wave_reduce and hamiltonian_move and msnake_fates.inc's fate_cell.
+// msnake_opponents.hip: it uses msnake_scripted.inc's wave_reduce and hamiltonian_move, msnake_fates.inc's fate_cell and
+// msnake_explore.inc's lane_from, explore_draws and explore_pick (msnake_playout_explore: epsilon-random moves per step).
 // Off the step path, snake_env rules only.
 //
 // One wavefront per env; the wave only READS the handle's state, once, in EnvReader's layout and bounds.
@@ -32,7 +33,9 @@ struct PlayoutArgs {
     uint32_t seed_lo, seed_hi; uint64_t env_id_base;
     int32_t* steps; uint8_t* end; float* ret; int32_t* info; int32_t* words; int32_t words_stride; int32_t* count;
     int32_t lds_per_wave;
-    int32_t which;       // bit 0: some snake plays safe_greedy, bit 1: some snake plays wary_greedy
+    int32_t which;       // EXPLORE_* (msnake_explore.inc): which blocks a step runs
+    uint32_t eps[MSNAKE_MAX_SNAKES];  // eps_q16 of snake s (msnake_playout_explore; all 0 for msnake_playout)
+    uint32_t xseed_lo, xseed_hi;      // the exploration stream's seed, formed on the host
 };
 
 constexpr int PLAYOUT_OCC_BYTES = 512;  // 64 rows of 64 bits
@@ -55,15 +58,13 @@ __device__ __forceinline__ uint32_t playout_philox(uint32_t seed_lo, uint32_t se
     return w == 0 ? c0 : w == 1 ? c1 : w == 2 ? c2 : c3;
 }
 
-__device__ __forceinline__ uint32_t lane_from(uint32_t v, int src_lane) {  // lane l <- lane src_lane(l): ds_bpermute
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
-}
 __device__ __forceinline__ uint32_t rdl(uint32_t v, int l) { return rdlane(v, (int)uni((uint32_t)l)); }  // run-time lane
 
-// ONE kernel, not one per set of policies: a.which (bit 0: some snake plays safe_greedy, bit 1: some snake plays wary_greedy)
-// is tested per step, wave-uniformly.  As a template over those two bits the kernel was the same code per instantiation, but
-// with more than one instantiation in the unit every sibling kernel that reads through EnvReader came out with other
-// instructions (tools/isa_diff.py: 87 of 93 differed); with one, all 93 are as they were (DESIGN.md, section 26).
+// ONE kernel, not one per set of policies: a.which (bit 0: the open moves and safe_greedy, bit 1: the verdicts and
+// wary_greedy, bit 2: some snake explores) is tested per step, wave-uniformly.  As a template over the first two bits the
+// kernel was the same code per instantiation, but with more than one instantiation in the unit every sibling kernel that
+// reads through EnvReader came out with other instructions (tools/isa_diff.py: 87 of 93 differed); with one, every
+// sibling is as it was (DESIGN.md, sections 26 and 28).
 __global__ __launch_bounds__(256) void msnake_playout_kernel(PlayoutArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t playout_lds[];
     const int wave_lane = (int)(threadIdx.x & 63u), lane = wave_lane;
@@ -91,7 +92,8 @@ __global__ __launch_bounds__(256) void msnake_playout_kernel(PlayoutArgs a) {
     uint32_t V_len, V_hd = 0u, V_grow, V_vel, V_head = 0u, V_fruit;
     uint32_t V_rec;  // lane REC_*: the env's scalars (kept in one VGPR: as scalar registers they are what spills)
     enum { REC_T = 0, REC_CTR_LO = 1, REC_CTR_HI = 2, REC_FLAGS = 3, REC_EP_LEN = 4, REC_EP_RET = 5, REC_SPARE = 6,
-           REC_SEED_LO = 8, REC_SEED_HI = 9, REC_ENV_LO = 10, REC_ENV_HI = 11, REC_N_STEPS = 12, REC_MAX_STEPS = 13 };
+           REC_SEED_LO = 8, REC_SEED_HI = 9, REC_ENV_LO = 10, REC_ENV_HI = 11, REC_N_STEPS = 12, REC_MAX_STEPS = 13,
+           REC_XSEED_LO = 14, REC_XSEED_HI = 15, REC_EPS0 = 16 };  // REC_EPS0 + s: eps_q16 of snake s
     {
         // The layout and the bounds are EnvReader's (msnake_envread.inc), spelled out here: the compiler specialises that
         // reader's helpers by what all their callers in the unit pass, so one more caller changes the instructions of every
@@ -111,6 +113,9 @@ __global__ __launch_bounds__(256) void msnake_playout_kernel(PlayoutArgs a) {
             V_rec = lane == REC_SEED_LO ? a.seed_lo : lane == REC_SEED_HI ? a.seed_hi : lane == REC_ENV_LO ? (uint32_t)env_id :
                     lane == REC_ENV_HI ? (uint32_t)(env_id >> 32) : lane == REC_N_STEPS ? (uint32_t)a.n_steps :
                     lane == REC_MAX_STEPS ? (uint32_t)a.max_steps : V_rec;
+            if (a.which & EXPLORE_DRAWS)
+                V_rec = lane == REC_XSEED_LO ? a.xseed_lo : lane == REC_XSEED_HI ? a.xseed_hi : lane == REC_EPS0 ? a.eps[0] :
+                        lane == REC_EPS0 + 1 ? a.eps[1] : lane == REC_EPS0 + 2 ? a.eps[2] : lane == REC_EPS0 + 3 ? a.eps[3] : V_rec;
         }
 #pragma unroll
         for (int s = 0; s < MSNAKE_MAX_SNAKES; ++s) {
@@ -182,11 +187,12 @@ __global__ __launch_bounds__(256) void msnake_playout_kernel(PlayoutArgs a) {
             const int lane = lane_of_step;
             uint32_t V_act = 0u, my_pol = pol_of_lane;
             asm volatile("" : "+v"(my_pol));
+            uint32_t V_cand = 0u;  // lane s: the candidate set of snake s, bit m: move m + 1 (read only when some snake explores)
             if (my_pol == MSNAKE_POLICY_HAMILTONIAN) {
                 const int hx = cell_c0(V_head), hy = cell_c1(V_head);
                 if (V_len > 0u && hx >= 0 && hx < dim && hy >= 0 && hy < dim) V_act = hamiltonian_move(hx, hy, dim);
             }
-            if (a.which & 1) {
+            if (a.which & EXPLORE_NEEDS_OPEN) {
                 // ---- safe_greedy (msnake_scripted_kernel): lane q = 4 s + m holds the target of move m + 1 of snake s
                 const int qs = (lane >> 2) & 3, qm = lane & 3;
                 const uint32_t qhead = lane_from(V_head, qs), qlen = lane_from(V_len, qs);
@@ -217,8 +223,9 @@ __global__ __launch_bounds__(256) void msnake_playout_kernel(PlayoutArgs a) {
                 key = mn(key, (uint32_t)__builtin_amdgcn_update_dpp((int)key, (int)key, 0x118, 0xF, 0xF, false));
                 const uint32_t mine = lane_from(key, 16 * (lane & 3) + 15);  // lane s <- the minimum of row s
                 if (my_pol == MSNAKE_POLICY_SAFE_GREEDY) V_act = mine == 0xFFFFFFFFu ? 0u : mine & 7u;
+                if (a.which & EXPLORE_DRAWS) V_cand = (open >> (4 * (lane & 3))) & 15u;
             }
-            if (a.which & 2) {
+            if (a.which & EXPLORE_NEEDS_WARY) {
                 // ---- wary_greedy (msnake_fates_kernel): lane 5 s + a holds the target of action a of snake s
                 const int my_s = (lane >= 5) + (lane >= 10) + (lane >= 15), my_a = lane - 5 * my_s;
                 const int my_len = (int)lane_from(V_len, my_s), my_vel = (int)lane_from(V_vel, my_s);
@@ -294,6 +301,18 @@ __global__ __launch_bounds__(256) void msnake_playout_kernel(PlayoutArgs a) {
                     wact = lane == s ? (m == 0xFFFFFFFFu ? 0u : m & 7u) : wact;
                 }
                 if (my_pol == MSNAKE_POLICY_WARY_GREEDY) V_act = wact;
+                if ((a.which & EXPLORE_DRAWS) && my_pol == MSNAKE_POLICY_WARY_GREEDY) V_cand = (candbits >> (5 * (lane & 3) + 1)) & 15u;
+            }
+            if (a.which & EXPLORE_DRAWS) {
+                // ---- the exploration rule (msnake_explore.inc), lane s <-> snake s: one Philox block per lane under the key
+                // mix64(xseed ^ ctr), on the state's own t and ctr
+                const uint64_t xseed = ((uint64_t)rdlane(V_rec, REC_XSEED_HI) << 32) | rdlane(V_rec, REC_XSEED_LO);
+                const uint64_t ctr = ((uint64_t)rdlane(V_rec, REC_CTR_HI) << 32) | rdlane(V_rec, REC_CTR_LO);
+                const uint64_t env_id = ((uint64_t)rdlane(V_rec, REC_ENV_HI) << 32) | rdlane(V_rec, REC_ENV_LO);
+                const ExploreDraws d = explore_draws(xseed, ctr, env_id, rdlane(V_rec, REC_T), lane & 3);
+                bool explored;
+                const uint32_t drawn = explore_pick(V_act, V_cand, lane_from(V_rec, REC_EPS0 + (lane & 3)), d, &explored);
+                V_act = lane < ns ? drawn : V_act;
             }
             if (k == 1) {
                 V_act = V_forced != 0u ? V_force : V_act;
@@ -477,21 +496,21 @@ __global__ __launch_bounds__(256) void msnake_playout_kernel(PlayoutArgs a) {
     }
 }
 
-hipError_t launch_playout(const StepParams& p, int rules, const int32_t* policies, int32_t n_steps, const int32_t* first,
+hipError_t launch_playout(const StepParams& p, int rules, const int32_t* policies, const uint32_t* eps, uint64_t xseed,
+                          int32_t n_steps, const int32_t* first,
                           int32_t first_stride, uint32_t first_mask, int32_t* steps, uint8_t* end, float* ret, int32_t* info,
                           int32_t* words, int32_t words_stride, int32_t* count, hipStream_t stream) {
     uint32_t pol = 0u;
-    int which = 0;
-    for (int s = 0; s < p.n_snakes; ++s) {
-        pol |= (uint32_t)policies[s] << (4 * s);
-        which |= policies[s] == MSNAKE_POLICY_SAFE_GREEDY ? 1 : policies[s] == MSNAKE_POLICY_WARY_GREEDY ? 2 : 0;
-    }
+    for (int s = 0; s < p.n_snakes; ++s) pol |= (uint32_t)policies[s] << (4 * s);
+    const int which = explore_which(policies, eps, p.n_snakes);  // eps NULL: msnake_playout, nobody explores
     const int per_wave = playout_lds_per_wave(p.n_snakes, p.rest.cap);
     int waves = 65536 / per_wave;  // the block stays within 64 KiB of LDS
     waves = waves > 4 ? 4 : waves;
     if (waves < 1) return hipErrorInvalidValue;
-    const PlayoutArgs a{state_view(p, rules), first, first_stride, first_mask, pol, n_steps, p.rest.max_steps, p.rest.seed_lo,
-                        p.rest.seed_hi, p.rest.env_id_base, steps, end, ret, info, words, words_stride, count, per_wave, which};
+    PlayoutArgs a{state_view(p, rules), first, first_stride, first_mask, pol, n_steps, p.rest.max_steps, p.rest.seed_lo,
+                  p.rest.seed_hi, p.rest.env_id_base, steps, end, ret, info, words, words_stride, count, per_wave, which,
+                  {0u, 0u, 0u, 0u}, (uint32_t)xseed, (uint32_t)(xseed >> 32)};
+    for (int s = 0; s < p.n_snakes && eps != nullptr; ++s) a.eps[s] = eps[s];
     const dim3 grid((unsigned)((p.nenv + waves - 1) / waves)), block((unsigned)(64 * waves));
     const size_t lds = (size_t)waves * (size_t)per_wave;
     hipLaunchKernelGGL(msnake_playout_kernel, grid, block, lds, stream, a);

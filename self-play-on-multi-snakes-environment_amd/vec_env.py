@@ -1246,7 +1246,72 @@ class MultiSnakeVecEnv:
             ids.append(_capi.PLAYOUT_POLICY[name])
         return (ctypes.c_int32 * _capi.MAX_SNAKES)(*ids), ids
 
-    def playout_device(self, n_steps, policies="safe_greedy", first_actions=None, first_snakes=None, end_state=False, out=None):
+    def _explore_args(self, explore, salt):
+        """`explore`, a probability in [0, 1] for every snake or one per snake, and `salt` -> (ctypes uint32 [MAX_SNAKES] of
+        eps_q16 = round(p * 65536), the salt as an int)."""
+        if isinstance(salt, (bool, np.bool_)) or not isinstance(salt, (int, np.integer)) or not 0 <= int(salt) < 2 ** 64:
+            raise ValueError(f"salt must be an int in [0, 2^64), got {salt!r}")
+        if isinstance(explore, (int, float, np.integer, np.floating)) and not isinstance(explore, (bool, np.bool_)):
+            explore = [explore] * self.n_snakes
+        try:
+            explore = list(explore)
+        except TypeError:
+            raise ValueError(f"explore must be a probability in [0, 1] or one per snake, got {explore!r}") from None
+        if len(explore) != self.n_snakes:
+            raise ValueError(f"explore must be one probability or one per snake ({self.n_snakes}), got {len(explore)}")
+        eps = []
+        for x in explore:
+            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)) or not 0.0 <= float(x) <= 1.0:
+                raise ValueError(f"explore: a probability must lie in [0, 1], got {x!r}")
+            eps.append(int(round(float(x) * _capi.EXPLORE_ONE)))
+        return (ctypes.c_uint32 * _capi.MAX_SNAKES)(*eps), int(salt)
+
+    def explore_actions_device(self, policies, explore, salt=0, snakes=None, out=None, explored_out=None):
+        """Exploring scripted players (msnake_explore_actions): for the snakes in `snakes` (indices; default every snake)
+        the action of its policy -- `policies` as playout_device() takes them -- or, with probability `explore` (a float in
+        [0, 1] for all snakes or one per snake, taken as round(p * 65536) / 65536), a uniformly random member of its
+        candidate set: the open moves, under "wary_greedy" that policy's own candidates.  The draw comes from a stream
+        keyed by the env's seed, `salt` (0 .. 2^64 - 1), the global env id and the state's step and draw counters; it never
+        touches the env's own, needs no torch RNG and repeats exactly for the same state: the very word
+        playout_device(explore=..., salt=...) plays for that state.  Actions go to columns `snakes` of `out`, an int32
+        [num_envs, >= n_snakes] device tensor as step_device() takes it (None: the cached tensor of
+        scripted_actions_device()); `explored_out`, a uint8 [num_envs, n_snakes] device tensor, gets 1 where the action was
+        drawn, for every snake.  Returns `out`, or (out, explored_out) when that was given.  "wary_greedy" needs snake_env
+        or adversarial rules.  One launch; nothing is synchronised and the env is only read."""
+        torch = self._torch
+        pol, ids = self._playout_policies(policies)
+        if _capi.PLAYOUT_POLICY[_capi.WARY_POLICY] in ids and self.cfg.rules == _capi.RULES["new_world"]:
+            raise ValueError(f"policies: {_capi.WARY_POLICY!r} needs snake_env or adversarial rules, got 'new_world'")
+        eps, salt = self._explore_args(explore, salt)
+        if snakes is None:
+            bits = (1 << self.n_snakes) - 1
+        else:
+            bits = 0
+            for s in snakes:
+                if int(s) != s or not 0 <= int(s) < self.n_snakes:
+                    raise ValueError(f"snake indices must lie in [0, {self.n_snakes}), got {s!r}")
+                bits |= 1 << int(s)
+        if not bits:
+            raise ValueError("snakes: no snake selected (no action to write)")
+        if out is None:
+            if getattr(self, "_scripted_out", None) is None:
+                with self._alloc_ctx():
+                    self._scripted_out = torch.zeros((self.num_envs, self.n_snakes), dtype=torch.int32, device=self.device)
+            out = self._scripted_out
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.device != self.device or out.dim() != 2 or
+              out.shape[0] != self.num_envs or out.shape[1] < self.n_snakes or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous int32 tensor of shape ({self.num_envs}, >= {self.n_snakes}) on {self.device}")
+        p_explored = None
+        if explored_out is not None:
+            p_explored = self._checked(explored_out, "explored_out", torch.uint8, (self.num_envs, self.n_snakes)).data_ptr()
+        rc = self._L.msnake_explore_actions(self._h, pol, eps, salt, bits, out.data_ptr(), int(out.shape[1]), p_explored,
+                                            self._cur_stream(self.device).cuda_stream)
+        if rc < 0:
+            _capi.check(rc, "msnake_explore_actions")
+        return out if explored_out is None else (out, explored_out)
+
+    def playout_device(self, n_steps, policies="safe_greedy", first_actions=None, first_snakes=None, end_state=False, out=None,
+                       explore=None, salt=0):
         """Play every env on for up to `n_steps` steps with a scripted policy per snake, in one launch, without touching
         the env (msnake_playout; snake_env): the value of a position.  `policies`: one of "safe_greedy", "hamiltonian",
         "wary_greedy" or None (the constant action 0) for all snakes, or one per snake.  `first_actions`, an int32
@@ -1259,7 +1324,11 @@ class MultiSnakeVecEnv:
         words int32 [num_envs, state_words_max] and count int32 [num_envs], the state each playout ended in, as
         export_states_device() writes them and import_states_device() takes them -- else None.  `out`: a Playout (or
         six-entry sequence) of tensors to write into, None for what is not wanted; `end_state` is then ignored and
-        words may have any stride.  Nothing is synchronised; no random number of the env is consumed."""
+        words may have any stride.  `explore` (None: nobody explores, msnake_playout): a probability in [0, 1] for all
+        snakes or one per snake with which a snake plays, in any step, a uniformly random member of its candidate set in
+        place of its policy's move (msnake_playout_explore; the rule and the stream, keyed by `salt`, are those of
+        explore_actions_device()); a forced first action wins over it.  Nothing is synchronised; no random number of the
+        env is consumed."""
         torch = self._torch
         n, ns, dev = self.num_envs, self.n_snakes, self.device
         if int(n_steps) != n_steps or not 1 <= int(n_steps) <= _capi.PLAYOUT_MAX_STEPS:
@@ -1267,6 +1336,7 @@ class MultiSnakeVecEnv:
         if self.cfg.rules != _capi.RULES["snake_env"]:
             raise ValueError(f"playout_device() needs a snake_env env, got rules {_capi.RULE_NAMES[int(self.cfg.rules)]!r}")
         pol, _ = self._playout_policies(policies)
+        eps, salt = (None, 0) if explore is None else self._explore_args(explore, salt)
         bits, p_first, stride = 0, None, 0
         if first_actions is None:
             if first_snakes is not None:
@@ -1303,21 +1373,26 @@ class MultiSnakeVecEnv:
         res = Playout(*res, words, count)
         if all(t is None for t in res):
             raise ValueError("out: nothing to write (all six entries are None)")
-        rc = self._L.msnake_playout(self._h, pol, int(n_steps), p_first, stride, bits,
-                                    *[None if t is None else t.data_ptr() for t in res[:5]], wstride,
-                                    None if count is None else count.data_ptr(), self._cur_stream(dev).cuda_stream)
+        rest = (int(n_steps), p_first, stride, bits, *[None if t is None else t.data_ptr() for t in res[:5]], wstride,
+                None if count is None else count.data_ptr(), self._cur_stream(dev).cuda_stream)
+        if eps is None:
+            rc = self._L.msnake_playout(self._h, pol, *rest)
+        else:
+            rc = self._L.msnake_playout_explore(self._h, pol, eps, salt, *rest)
         if rc < 0:
-            _capi.check(rc, "msnake_playout")
+            _capi.check(rc, "msnake_playout" if eps is None else "msnake_playout_explore")
         return res
 
-    def playout_values_device(self, scratch, n_steps, snake=0, reps=1, policies="safe_greedy"):
+    def playout_values_device(self, scratch, n_steps, snake=0, reps=1, policies="safe_greedy", explore=None, salt=0):
         """The value of each of `snake`'s four moves in every env, by playouts on forks: (value, survive), both float32
         [num_envs, 4].  `scratch`: an env of the same board with num_envs * 4 * reps envs; env e is copied into its slots
         (e * 4 + m) * reps + r (copy_envs_device), and one playout_device() of n_steps steps there forces `snake`'s first
         action to m + 1, everything else following `policies`.  value[e, m] is the mean over r of the snake's summed
         reward, survive[e, m] the share of the reps in which it did not die.  The slots draw from their own random
-        streams at the copied counter, which is what makes the reps differ.  Two launches and a few torch reductions;
-        nothing is synchronised and this env is only read."""
+        streams at the copied counter, which is what makes the reps differ once somebody eats; with `explore` (and
+        `salt`, both as playout_device() takes them) the snakes also explore inside the playouts, every slot from its own
+        stream, so the reps differ from the first step on.  Two launches and a few torch reductions; nothing is
+        synchronised and this env is only read."""
         torch = self._torch
         n, ns = self.num_envs, self.n_snakes
         if int(snake) != snake or not 0 <= int(snake) < ns:
@@ -1325,6 +1400,9 @@ class MultiSnakeVecEnv:
         if int(reps) != reps or int(reps) < 1:
             raise ValueError(f"reps must be >= 1, got {reps!r}")
         snake, reps = int(snake), int(reps)
+        more = {} if explore is None else dict(explore=explore, salt=salt)
+        if more:
+            self._explore_args(explore, salt)  # (refused here, before the copy)
         if not isinstance(scratch, MultiSnakeVecEnv):
             raise TypeError(f"scratch must be a MultiSnakeVecEnv, got {type(scratch).__name__}")
         if scratch.num_envs != n * 4 * reps:
@@ -1337,7 +1415,7 @@ class MultiSnakeVecEnv:
             self._playout_plan = (key, (slot // (4 * reps)).to(torch.int32), first)
         _, index, first = self._playout_plan
         scratch.copy_envs_device(self, index)
-        res = scratch.playout_device(n_steps, policies, first_actions=first, first_snakes=[snake])
+        res = scratch.playout_device(n_steps, policies, first_actions=first, first_snakes=[snake], **more)
         value = res.ret[:, snake].reshape(n, 4, reps).mean(dim=2)
         survive = (res.info[:, snake, 2] == 0).to(torch.float32).reshape(n, 4, reps).mean(dim=2)
         return value, survive

@@ -11,8 +11,24 @@ between HIP events after a warm-up, the legs alternating over the rounds:
   step:       the same loop with the step alone (constant action 1), shown next to it as the sibling tools do.
 Reported in us per call (one playout / one K-step loop) and per playout step.  At K = 64 the playout's time per step has to
 be below the yardstick's at both batch sizes and for both policies: "below_yardstick_at_K64"; the tool exits 1 if not.
-    python tools/playout_cost.py --out profiles/playout_cost.json"""
+    python tools/playout_cost.py --out profiles/playout_cost.json
+
+--explore measures what exploring playouts (msnake_playout_explore) cost, into a file of its own:
+  (a) with --ab-libs OLD NEW ("default" = the in-tree libmsnake.so): msnake_playout, every snake on safe_greedy, on two
+      builds of the library, one fresh process per build and round, alternating on the same box (the way tools/ab_libs.sh
+      runs two libraries); both medians and the spread of the processes' medians are recorded, and whether NEW is slower
+      than OLD beyond that spread;
+  (b) in this process: msnake_playout next to msnake_playout_explore with eps 0.25 and 1.0 for all snakes, safe_greedy and
+      wary_greedy.
+The older build: check the parent commit out next to the tree and build it as a variant, which leaves
+<parent tree>/self-play-on-multi-snakes-environment_amd/libmsnake_parent.so:
+    git worktree add ../parent HEAD~1 && make -C ../parent/self-play-on-multi-snakes-environment_amd/csrc variant NAME=parent
+    python tools/playout_cost.py --explore --ab-libs <parent tree>/self-play-on-multi-snakes-environment_amd/libmsnake_parent.so default \
+        --out profiles/playout_explore_cost.json"""
 import argparse
+import json
+import os
+import subprocess
 import sys
 
 import cost_harness as ch
@@ -33,8 +49,84 @@ def capture(fn, groups):
     return g
 
 
+def explore_legs(env, K, out, policies=("safe_greedy", "wary_greedy"), eps=(0.25, 1.0)):
+    legs = {}
+    for pol in policies:
+        legs[f"playout {pol}"] = lambda pol=pol: env.playout_device(K, pol, out=out)
+        for x in eps:
+            legs[f"playout {pol}, explore {x}"] = lambda pol=pol, x=x: env.playout_device(K, pol, out=out, explore=x, salt=1)
+    return legs
+
+
+def measure(args, legs_of):
+    """legs_of(env, K, out) -> {name: fn}; us per call and per step of every leg, the legs alternating over the rounds."""
+    import msnake
+    res = {}
+    for n in args.envs:
+        env, _ = ch.played_env(n, args.play_steps)
+        blob = env.get_state_all()
+        small = msnake.Playout(*env.playout_device(1)[:4], None, None)
+        out = {}
+        for K in args.ks:
+            groups = max(2, args.launches // (2 * K))
+            legs = legs_of(env, K, small)
+            graphs = {name: capture(fn, groups) for name, fn in legs.items()}
+            times = {name: [] for name in legs}
+            for _ in range(args.rounds):
+                for name, g in graphs.items():
+                    times[name].append(ch.timed(g.replay, groups))
+            ch.assert_unchanged(env, blob)
+            out[f"K={K}"] = {name: {"per_call_us": ch.med(v), "per_step_us": ch.med([x / K for x in v])} for name, v in times.items()}
+            print(f"{n} envs, K={K}: done", file=sys.stderr, flush=True)
+        res[str(n)] = out
+        env.close()
+    return res
+
+
+def explore_main(args):
+    import torch
+    if args.ab_child:                                    # one process of leg (a): msnake_playout, all safe_greedy, on MSNAKE_LIB
+        import msnake
+        msnake._capi.load(optional=("msnake_explore_actions", "msnake_playout_explore"))  # the older build lacks them; the leg calls neither
+        print(json.dumps(measure(args, lambda env, K, out: {"playout safe_greedy": lambda: env.playout_device(K, "safe_greedy", out=out)})))
+        return
+    res = {"device": torch.cuda.get_device_name(0), "config": "snake_env 19x19, 3 snakes", "rounds": args.rounds,
+           "start_states": f"{args.play_steps} steps into safe_greedy play",
+           "unit": "us: median (min, max) over the rounds; per_call = one playout, per_step = per_call / K"}
+    if args.ab_libs:
+        old, new = args.ab_libs
+        runs = {old: [], new: []}
+        base = [sys.executable, os.path.abspath(__file__), "--explore", "--ab-child", "--rounds", str(args.rounds), "--play-steps", str(args.play_steps),
+                "--launches", str(args.launches), "--envs", *map(str, args.envs), "--ks", *map(str, args.ks)]
+        for i in range(args.ab_rounds):
+            for lib in (old, new):
+                env = dict(os.environ, MSNAKE_LIB="" if lib == "default" else os.path.abspath(lib))
+                r = subprocess.run(base, env=env, capture_output=True, text=True, timeout=600)
+                if r.returncode != 0:
+                    sys.exit(f"A/B process on {lib} failed ({r.returncode}):\n{r.stderr[-2000:]}")
+                runs[lib].append(json.loads(r.stdout.strip().split("\n")[-1]))
+                print(f"A/B round {i}, {lib}: done", file=sys.stderr, flush=True)
+        ab = {}
+        for n in map(str, args.envs):
+            for K in args.ks:
+                per = {lib: [run[n][f"K={K}"]["playout safe_greedy"]["per_step_us"][0] for run in runs[lib]] for lib in (old, new)}
+                spread = max(max(v) - min(v) for v in per.values())
+                m = {lib: sorted(v)[len(v) // 2] for lib, v in per.items()}
+                ab[f"{n} envs, K={K}"] = {"old_per_step_us": ch.med(per[old]), "new_per_step_us": ch.med(per[new]), "spread_us": round(spread, 3),
+                                          "new_slower_beyond_spread": bool(m[new] - m[old] > spread)}
+        res["a_msnake_playout_old_vs_new"] = {"old": old, "new": new, "processes_per_library": args.ab_rounds,
+                                              "figures": "median (min, max) over the processes of each process's median us per playout step; "
+                                                         "spread = the larger max - min of the two libraries", "legs": ab}
+    res["b_explore_vs_none"] = measure(args, explore_legs)
+    ch.write_json(res, args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--explore", action="store_true", help="the cost of exploring playouts (see the module docstring)")
+    ap.add_argument("--ab-libs", nargs=2, default=None, metavar=("OLD", "NEW"), help="--explore: two builds of libmsnake.so to compare")
+    ap.add_argument("--ab-rounds", type=int, default=3, help="--explore: processes per library")
+    ap.add_argument("--ab-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launches", type=int, default=256, help="kernel launches per yardstick graph, about")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 32768])
@@ -42,6 +134,8 @@ def main():
     ap.add_argument("--play-steps", type=int, default=500)
     ap.add_argument("--out", default=None, help="also write the JSON to this file")
     args = ap.parse_args()
+    if args.explore:
+        return explore_main(args)
     import torch
     import msnake
 
